@@ -11,10 +11,12 @@ Workload (BASELINE.json configs[1], the config the metric is quoted on):
 Heat-maps are handed over the way this repo's backbone emits them (PoseResNet.forward_views: (B,15,h,w) views of one
 channels-last (V,B,h,w,16) buffer), so the step has no re-tiling pass; `--planar-input` gives the reference's planar
 (B,15,h,w) hand-over instead (one extra pack kernel per step).  Samples 0,1 of rank 0's batch are the inputs of the
-reference golden tests/golden/rootnet_full.npz and the weights are that golden's: after the timed loop the step's own
-output is checked against the reference's root cubes and proposals (`output_check`).
+reference golden tests/golden/rootnet_full.npz and the weights are that golden's: with --full, after the timed loop the
+step's own output is checked against the reference's root cubes and proposals (`output_check`).
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with three extra objects:
+Prints ONE JSON line on rank 0 (contract in the task statement).  A plain run only sets up, warms up, times the K steps,
+writes the last step's outputs if --dump-outputs DIR is given, and prints the headline.  --full adds box_spread, output_check,
+the fp32-matrix-instruction leg, the default legs and three extra objects:
   roofline      - the unprojection kernel: algorithmic bytes / HIP-event time vs 8 TB/s HBM peak (+ path time, cold inputs)
   cpu_baseline  - the CPU oracle (C port, OpenMP) + torch-CPU V2V on a bounded sample of the same workload, all cores and 1
   cpu_reference - the reference's own Python timed in the build container (static: profiles/cpu_reference.json)
@@ -25,7 +27,7 @@ measurement run under --leg-deadline (600 s): if a collective never returns, ran
 (top level: legs_complete / scaling_valid = false) and every rank exits with status 3 - a hang can neither lose the headline nor pass
 as a finished scaling run.  config.rccl_ranks_seen = the sum of an all-reduce of ones on the data-plane communicator (must equal N).
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 """
@@ -57,6 +59,15 @@ def parse():
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--batch", type=int, default=4, help="frames per GPU per step (configs[1]: 4)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run everything else the line can carry: box_spread repeats, the output check "
+                         "against the reference golden, the fp32-matrix-instruction leg, roofline (+ in-step stamps), cpu_baseline, "
+                         "cpu_reference and the default legs.  Without it a run only sets up, warms up, times the K steps and "
+                         "prints the headline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last timed step's outputs (root_cubes, grid_centers) as float32 "
+                         "DIR/<name>.npy (ranks > 0: DIR/<name>_rank<r>.npy); the inputs are seeded, so two builds can be "
+                         "compared output for output")
     ap.add_argument("--roofline-iters", type=int, default=300)
     ap.add_argument("--no-fp32-leg", action="store_true",
                     help="skip the extra leg that re-times the step with every 3^3 product on fp32 matrix instructions")
@@ -84,7 +95,8 @@ def parse():
                          "returns must not lose the headline - and must not read as a finished scaling run either); 0 disables")
     ap.add_argument("--legs", default="auto",
                     help="extra legs next to the headline: comma list of pose_stage, train_step, planar_handover, unprojection_grids, unprojection_backward, or 'auto' "
-                         "(all four: train_step = BASELINE configs[2], at every N) or 'none'")
+                         "(with --full all of them + host_contention: train_step = BASELINE configs[2], at every N; without "
+                         "--full none) or 'none'")
     ap.add_argument("--share-gpu", action="store_true",
                     help="smoke mode for boxes with ONE GPU: every rank uses cuda:0 and the process group is gloo (the whole "
                          "multi-rank code path - sharding, DDP gradient all-reduce, max-over-ranks timing - without RCCL); the "
@@ -169,6 +181,22 @@ def check_output(out, golden, tol=5e-5):
     return {"ok": bool(ok), "reference": "tests/golden/rootnet_full.npz (reference CuboidProposalNet, CPU fp32)",
             "root_cubes_max_abs_err": err, "root_cubes_range": scale, "checksum_rel_err": sum_err,
             "proposal_indices_checked": checked, "proposal_indices_wrong": bad}
+
+
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(out, directory, rank, world):
+    """--dump-outputs: what a caller of the timed step receives from its last timed call, (root_cubes, grid_centers), as
+    float32 .npy files.  Each rank writes its own frames; an output larger than the rank's share of 64 MB keeps its
+    leading frames (a fixed sample: the inputs are seeded, so runs with the same arguments compare frame for frame)."""
+    os.makedirs(directory, exist_ok=True)
+    suffix = "" if rank == 0 else f"_rank{rank}"
+    share = DUMP_BUDGET_BYTES // max(1, world) // len(out)
+    for name, t in zip(("root_cubes", "grid_centers"), out):
+        a = t.detach().float().cpu().numpy()
+        keep = max(1, share // max(1, a[0].nbytes))
+        np.save(os.path.join(directory, f"{name}{suffix}.npy"), a[:keep])
 
 
 def use_shipped_miopen_db():
@@ -863,11 +891,25 @@ def cpu_reference_record():
             "host": rec["host"], "detail": c1, "source": "profiles/cpu_reference.json (tools/time_reference_cpu.py)"}
 
 
+def _term_with_parent():
+    """preexec hook of the launcher child: SIGTERM it when this process dies (Linux PR_SET_PDEATHSIG = 1), so that
+    torch.distributed.run still stops its ranks when the parent is killed"""
+    try:
+        import ctypes
+        import signal
+        ctypes.CDLL("libc.so.6", use_errno=True).prctl(1, int(signal.SIGTERM), 0, 0, 0)
+    except Exception:
+        pass
+
+
 def self_launch(args):
-    """`python bench.py --gpus N` (N > 1) started WITHOUT a launcher: re-exec under torch.distributed.run, one rank per
-    GPU, rendezvous on 127.0.0.1 - the command line the task statement gives for N > 1.  Never returns.  (Round-3 review:
-    a plain `python bench.py --gpus 8` ran ONE rank and printed n_gpus = 1.)"""
+    """`python bench.py --gpus N` (N > 1) started WITHOUT a launcher: run torch.distributed.run as a child process, one
+    rank per GPU, rendezvous on 127.0.0.1 - the command line the task statement gives for N > 1 - and exit with its status.
+    Never returns.  A child process, not an exec: this process has already asked HIP for the device count, and a process
+    that has opened the GPU must not replace its own program.  (Round-3 review: a plain `python bench.py --gpus 8` ran ONE
+    rank and printed n_gpus = 1.)"""
     import socket
+    import subprocess
     n = torch.cuda.device_count() if torch.cuda.is_available() else 0
     if not args.share_gpu and n < args.gpus:
         raise SystemExit(f"bench.py --gpus {args.gpus}: {n} GPU(s) visible on this box (one rank per GPU; "
@@ -878,8 +920,9 @@ def self_launch(args):
     s.close()
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}",
            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
-    print("[bench] --gpus %d without a launcher: exec %s" % (args.gpus, " ".join(cmd)), file=sys.stderr, flush=True)
-    os.execv(sys.executable, cmd)
+    print("[bench] --gpus %d without a launcher: running %s" % (args.gpus, " ".join(cmd)), file=sys.stderr, flush=True)
+    rc = subprocess.run(cmd, preexec_fn=_term_with_parent).returncode
+    raise SystemExit(rc if rc >= 0 else 128 - rc)           # killed by signal s: 128 + s, as a shell reports it
 
 
 def main():
@@ -919,8 +962,8 @@ def main():
     cfg, meta, hms, model, golden = build_workload(args.batch, rank, dev, args.v2v_layout, args.front_conv,
                                                    not args.no_winograd, args.planar_input, not args.no_gemm_tuning)
     legs = args.legs.split(",") if args.legs not in ("auto", "none") else \
-        ([] if args.legs == "none" else ["pose_stage", "planar_handover", "unprojection_grids", "unprojection_backward", "train_step",
-                                         "host_contention"])
+        ([] if args.legs == "none" or not args.full else
+         ["pose_stage", "planar_handover", "unprojection_grids", "unprojection_backward", "train_step", "host_contention"])
     args.legs_list = legs
 
     from selfpose3d_amd.project_layer import clear_pack_cache
@@ -948,11 +991,13 @@ def main():
 
     # W untimed warm-up steps, then EXACTLY K steps between two barrier+synchronise points, slowest rank counts
     elapsed, out = D.timed_steps(step, args.steps, args.warmup, dev)
-    # box_spread: the same K steps again (same barrier rule), so that the line carries its own noise figure - 20 steps of
-    # 1.6 ms differ by 1-3 % from repeat to repeat and box to box, and a leg that does MORE work must not read faster than
-    # the headline without that being visible (round-3 review).  `value` stays the first K steps, as the contract says.
+    if args.dump_outputs:                          # before anything else replays the step's graph into the same buffers
+        dump_outputs(out, args.dump_outputs, rank, world)
+    # box_spread (--full): the same K steps again (same barrier rule), so that the line carries its own noise figure - 20
+    # steps of 1.6 ms differ by 1-3 % from repeat to repeat and box to box, and a leg that does MORE work must not read faster
+    # than the headline without that being visible (round-3 review).  `value` stays the first K steps, as the contract says.
     spread = [1e3 * elapsed / args.steps]
-    for _ in range(max(0, args.spread_repeats - 1)):
+    for _ in range(max(0, args.spread_repeats - 1) if args.full else 0):
         el_r, _ = D.timed_steps(step, args.steps, 0, dev)
         spread.append(1e3 * el_r / args.steps)
 
@@ -998,13 +1043,15 @@ def main():
                        "v2v_layout": args.v2v_layout, "front_conv": args.front_conv, "winograd": not args.no_winograd, "launch": mode,
                        "graph_executables": (args.graph_copies if mode == "hipgraph" else 0)},
             "views_x_frames_per_s": round(value * V, 3),
-            "value_window": (f"first of {len(spread)} windows of {args.steps} steps; by ms_per_step it ranks "
-                             f"{1 + sorted(spread).index(spread[0])} of {len(spread)} (1 = fastest): legs measured later in the run may read "
-                             f"faster than `value` by up to the box_spread"),
-            "box_spread": {"ms_per_step_min": round(min(spread), 4), "ms_per_step_max": round(max(spread), 4),
-                           "repeats": len(spread), "steps_each": args.steps,
-                           "what": "the timed K steps (= value) and further repeats of K steps on the same box, same rule"},
+            "full": args.full,
         }
+        if args.full:
+            result["value_window"] = (f"first of {len(spread)} windows of {args.steps} steps; by ms_per_step it ranks "
+                                      f"{1 + sorted(spread).index(spread[0])} of {len(spread)} (1 = fastest): legs measured later in "
+                                      f"the run may read faster than `value` by up to the box_spread")
+            result["box_spread"] = {"ms_per_step_min": round(min(spread), 4), "ms_per_step_max": round(max(spread), 4),
+                                    "repeats": len(spread), "steps_each": args.steps,
+                                    "what": "the timed K steps (= value) and further repeats of K steps on the same box, same rule"}
         if args.share_gpu:
             result["share_gpu_note"] = ("ranks that share a GPU run libsp3d_nopk.so (SP3D_SHARED_GPU=1: no packed-fp32 instructions), "
                                         "which is immune to the matrix-instruction / packed-fp32 interaction of "
@@ -1123,7 +1170,7 @@ def main():
         except Exception as e:
             extra["train_step_ssv"] = {"error": f"{type(e).__name__}: {e}"}
 
-    if rank == 0:
+    if rank == 0 and args.full:
         B = args.batch
         if golden is not None and not args.no_check:
             result["output_check"] = check_output(out, golden)
@@ -1187,6 +1234,7 @@ def main():
         else:
             result["cpu_baseline"] = None
         result["cpu_reference"] = cpu_reference_record()
+    if rank == 0:
         if "pose_stage" in legs:
             try:
                 extra["pose_stage"] = pose_stage_leg(dev)

@@ -59,7 +59,27 @@ def test_cpu_reference_record_and_defaults():
     finally:
         sys.argv = argv
     assert (a.gpus, a.batch) == (1, 4) and a.steps >= 20 and a.warmup >= 1 and not a.planar_input
+    assert not a.full and a.dump_outputs is None               # a plain run measures the headline only
     assert bench.HBM_PEAK_GBS == 8000.0
+
+
+def test_dump_outputs_writes_float32_arrays_within_the_budget(tmp_path, monkeypatch):
+    """--dump-outputs: one .npy per output of the step, float32, rank-suffixed beyond rank 0, a fixed leading sample of an
+    output larger than the 64 MB budget"""
+    bench = _bench()
+    g = torch.Generator().manual_seed(5)
+    cubes = torch.rand(4, 80, 80, 20, generator=g)
+    centers = torch.rand(4, 10, 5, generator=g, dtype=torch.float64)
+    bench.dump_outputs((cubes, centers), str(tmp_path / "a"), 0, 1)
+    rc, gc = np.load(tmp_path / "a" / "root_cubes.npy"), np.load(tmp_path / "a" / "grid_centers.npy")
+    assert rc.dtype == np.float32 and gc.dtype == np.float32
+    assert np.array_equal(rc, cubes.numpy()) and np.array_equal(gc, centers.float().numpy())
+    bench.dump_outputs((cubes, centers), str(tmp_path / "a"), 1, 2)
+    assert np.array_equal(np.load(tmp_path / "a" / "root_cubes_rank1.npy"), rc)
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 4 * cubes[0].numel() * 4)    # room for 2 frames per output
+    bench.dump_outputs((cubes, centers), str(tmp_path / "b"), 0, 1)
+    small = np.load(tmp_path / "b" / "root_cubes.npy")
+    assert small.shape == (2, 80, 80, 20) and np.array_equal(small, rc[:2])
 
 
 def test_gpus_flag_never_runs_fewer_ranks_silently(monkeypatch):
@@ -74,17 +94,25 @@ def test_gpus_flag_never_runs_fewer_ranks_silently(monkeypatch):
     with pytest.raises(SystemExit) as e:
         bench.main()
     assert "--gpus 8" in str(e.value) and "GPU(s) visible" in str(e.value)
-    # (b) no launcher, --share-gpu (or enough GPUs): the exec'd command is the task statement's launch line
+    # (b) no launcher, --share-gpu (or enough GPUs): the child process runs the task statement's launch line (never an exec
+    # of a process that has opened the GPU) and bench.py exits with the launcher's status
+    import subprocess
     seen = {}
 
-    def fake_execv(exe, cmd):
+    def fake_run(cmd, **kw):
         seen["cmd"] = cmd
-        raise SystemExit("exec")
-    monkeypatch.setattr(os, "execv", fake_execv)
+        return subprocess.CompletedProcess(cmd, 7)
+
+    def no_exec(*a, **kw):
+        raise AssertionError("bench.py must not replace its own process")
+    monkeypatch.setattr(subprocess, "run", fake_run)
+    monkeypatch.setattr(os, "execv", no_exec)
     monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "2", "--share-gpu", "--steps", "3"])
-    with pytest.raises(SystemExit):
+    with pytest.raises(SystemExit) as e:
         bench.main()
+    assert e.value.code == 7
     cmd = seen["cmd"]
+    assert cmd[0] == sys.executable
     assert cmd[1:4] == ["-m", "torch.distributed.run", "--nnodes=1"] and "--nproc-per-node=2" in cmd
     assert cmd[cmd.index("--master-addr") + 1] == "127.0.0.1" and cmd[-5:] == ["--gpus", "2", "--share-gpu", "--steps", "3"]
     # (c) launcher with another world size: refused, never a line with the wrong n_gpus

@@ -6,6 +6,6 @@ rm -rf $O/miopen_db; mkdir -p $O/miopen_db
 export MIOPEN_USER_DB_PATH=$O/miopen_db
 export SP3D_NO_SHIPPED_MIOPEN_DB=1
 s=$(date +%s)
-python $R/bench.py --steps 20 --no-cpu-baseline --legs pose_stage,planar_handover,train_step --train-steps 3 --train-warmup 2 2>/dev/null | cut -c1-120
+python $R/bench.py --full --steps 20 --no-cpu-baseline --legs pose_stage,planar_handover,train_step --train-steps 3 --train-warmup 2 2>/dev/null | cut -c1-120
 e=$(date +%s); echo "populate wall $((e-s)) s"
 ls -la $O/miopen_db; du -sh $O/miopen_db
