@@ -84,11 +84,11 @@ enum {
 /* heat-map layouts accepted by the unprojection kernels (per-view pointers in both) */
 enum {
     SP3D_LAYOUT_PLANAR = 0,  /* view c: (B, J, h, w) fp32 - the reference's layout (pose_resnet.py:203) */
-    SP3D_LAYOUT_NHWC = 1,    /* view c: (B, h, w, Jp) fp32, Jp%4==0, channels >= J are ignored padding */
+    SP3D_LAYOUT_NHWC = 1,    /* view c: (B, h, w, Jp) fp32, Jp in 4/8/12/16/32, channels >= J are ignored padding */
     /* OR-ed into hm_layout: write `cubes` channels-last, (B, X, Y, Z, J) with J%4==0 (NHWC input
-     * only) - the layout MIOpen's 3D convolutions consume without an internal transpose. */
+     * only, Jp <= 16) - the layout MIOpen's 3D convolutions consume without an internal transpose. */
     SP3D_OUT_CHANNELS_LAST = 0x100,
-    /* OR-ed into hm_layout (NHWC, Jp == 16): the packed heat-maps / the cubes are stored as bf16
+    /* OR-ed into hm_layout (NHWC, Jp == 16 or 32): the packed heat-maps / the cubes are stored as bf16
      * (BASELINE configs[4] "mixed bf16": storage only - projection, interpolation and view fusion
      * stay fp32; cubes are rounded to nearest-even on the final store). */
     SP3D_HM_BF16 = 0x200,
@@ -110,9 +110,19 @@ const char *sp3d_error_string(int code);
 int sp3d_pack_heatmaps(const float *const *hm_views, float *packed, int B, int V, int J, int Jp, int h, int w,
                        void *stream);
 /* same with explicit storage types: in_bf16 / out_bf16 = 1 when the planar inputs / the packed output
- * hold bf16 instead of fp32 (bf16 needs Jp == 16) */
+ * hold bf16 instead of fp32 (bf16 needs Jp == 16 or 32) */
 int sp3d_pack_heatmaps_ex(const void *const *hm_views, void *packed, int in_bf16, int out_bf16, int B, int V, int J,
                           int Jp, int h, int w, void *stream);
+
+/*
+ * Channel strides: Jp in 4/8/12/16 for J <= Jp, and Jp = 32 for 17 <= J <= 32 (the 17 COCO joints of the Shelf / Campus
+ * configurations).  A 32-float pixel is one 128-byte line, gathered as two channel groups (channels 0-15, 16..J-1) by
+ * one launch each of the 16-channel kernels; each group is bit-identical to the oracle.  At Jp = 32 the NHWC forward
+ * entries (_fwd, _fwd_indexed, _fwd_strided) take fp32 or bf16 maps and cubes, with or without sample_of and grids, for
+ * heat-maps of at least 2x2 pixels; SP3D_EUNSUPPORTED for a channels-last result, for sp3d_unproject_fwd_train (the pass
+ * mask holds 16 bits per voxel), for sp3d_unproject_fwd_zdft and for both sp3d_unproject_bwd_packed entries.  Any other
+ * Jp, or J > Jp: SP3D_EUNSUPPORTED, before any launch.
+ */
 
 /*
  * ProjectLayer.get_voxel forward (project_layer.py:42-102; math: DESIGN.md §3).

@@ -388,7 +388,7 @@ __device__ __forceinline__ Rec make_record(bool use, float ix, float iy, int w, 
 // mymask = number of views that see the lane's own voxel (+ bit 31: NaN sample position).
 // Round 3: the projection runs on packed fp32 pairs (sp3d_proj_pk.h), a tap record is one 16-byte weight quad + one
 // offset word (2 LDS instructions per slot instead of 5), the interpolation is written on channel pairs.
-template <int JP, typename TI, int U = 4>
+template <int JP, typename TI, int U = 4, int PS = JP>
 __device__ __forceinline__ void pipe_views(const Views &hm, const float *__restrict__ cam, const Geom &g, int bs, float x,
                                            float y, float z, bool inb, float *ws, int lane, float (&acc)[4][4],
                                            uint32_t &mymask, unsigned long long *tl, bool vsync = false)
@@ -413,7 +413,7 @@ __device__ __forceinline__ void pipe_views(const Views &hm, const float *__restr
         if (SP3D_DIAG_ON(4)) {      // no projection: a fixed record per lane (distinct pixels, in range)
             if (inb) mymask += 1u;
             const int v = (c & 1) * 64 + lane;
-            wsi[WOFF + v] = (int)((unsigned)(lane * 37 + c * 4001 + 1000 + (int)(x * 0.01f)) % (unsigned)(g.w * (g.h - 2))) * (JP * (int)sizeof(TI));
+            wsi[WOFF + v] = (int)((unsigned)(lane * 37 + c * 4001 + 1000 + (int)(x * 0.01f)) % (unsigned)(g.w * (g.h - 2))) * (PS * (int)sizeof(TI));
             ws4[v] = make_float4(0.25f, 0.25f, 0.25f, 0.25f);
             return true;
         }
@@ -427,7 +427,7 @@ __device__ __forceinline__ void pipe_views(const Views &hm, const float *__restr
         if (um == 0ull) return false;           // no voxel of this wave sees camera c
         const RecPk r = make_record_pk(lane_of(um), st.i, g.w, g.h);
         const int v = (c & 1) * 64 + lane;
-        wsi[WOFF + v] = (int)__umul24((unsigned)(JP * (int)sizeof(TI)), __umul24((unsigned)r.y0, (unsigned)g.w) + (unsigned)r.x0);
+        wsi[WOFF + v] = (int)__umul24((unsigned)(PS * (int)sizeof(TI)), __umul24((unsigned)r.y0, (unsigned)g.w) + (unsigned)r.x0);
         ws4[v] = make_float4(r.wt.x, r.wt.y, r.wb.x, r.wb.y);
         return true;
     };
@@ -436,7 +436,7 @@ __device__ __forceinline__ void pipe_views(const Views &hm, const float *__restr
     const int g16 = lane >> 2, q = lane & 3;
     const bool qact = q < NQ;
     const uint32_t qoff = qact ? 4u * (uint32_t)sizeof(TI) * (uint32_t)q : 0u;      // this lane's channel quad, bytes
-    const size_t rowf = (size_t)g.w * JP;
+    const size_t rowf = (size_t)g.w * PS;
     bool have = P1(0);
     SP3D_STAMP(1);
 #pragma unroll 1
@@ -445,7 +445,7 @@ __device__ __forceinline__ void pipe_views(const Views &hm, const float *__restr
         if (vsync) __builtin_amdgcn_s_barrier();
         const bool cur = have;
         // wave-uniform row bases (SGPR pairs) + one 32-bit element offset per lane: the four taps of a slot are
-        // {vb, vb2} + off (+ JP as an immediate), no 64-bit VALU address arithmetic
+        // {vb, vb2} + off (+ PS as an immediate), no 64-bit VALU address arithmetic
         const char *vb = reinterpret_cast<const char *>(reinterpret_cast<const TI *>(hm.p[c]) + (size_t)bs * g.h * rowf);
         const char *vb2 = vb + rowf * sizeof(TI);
         const int rb = (c & 1) * 64 + g16;
@@ -470,9 +470,9 @@ __device__ __forceinline__ void pipe_views(const Views &hm, const float *__restr
                     const uint32_t off = (uint32_t)wsi[WOFF + rb + 16 * (gi * U + k)] + qoff;      // bytes
                     // (issued in the reverse of the order the interpolation consumes them: loads return in order, so
                     // the wait for t00 covers the slot's other three and the chain needs one s_waitcnt per slot, not four)
-                    t11[k] = Store4<TI>::load(reinterpret_cast<const TI *>(vb2 + off) + JP);
+                    t11[k] = Store4<TI>::load(reinterpret_cast<const TI *>(vb2 + off) + PS);
                     t01[k] = Store4<TI>::load(reinterpret_cast<const TI *>(vb2 + off));
-                    t10[k] = Store4<TI>::load(reinterpret_cast<const TI *>(vb + off) + JP);
+                    t10[k] = Store4<TI>::load(reinterpret_cast<const TI *>(vb + off) + PS);
                     t00[k] = Store4<TI>::load(reinterpret_cast<const TI *>(vb + off));
                 }
             }
@@ -501,7 +501,7 @@ __device__ __forceinline__ void pipe_views(const Views &hm, const float *__restr
     }
 }
 
-template <int JP, int NW, bool OUTCL, typename TI, typename TO, int U = 4>
+template <int JP, int NW, bool OUTCL, typename TI, typename TO, int U = 4, int PS = JP>
 __device__ __forceinline__ void pipe_tile(const Views &hm, const float *__restrict__ cam, const float *__restrict__ centers,
                                           const uint8_t *__restrict__ valid, float *__restrict__ cubes,
                                           float *__restrict__ grids, const Geom &g, int b, int tile, float *smem,
@@ -569,7 +569,7 @@ __device__ __forceinline__ void pipe_tile(const Views &hm, const float *__restri
 #ifdef SP3D_TIMELINE
     if (tl && lane == 0) tl[26] = wall_clock64();       // chip-wide 100 MHz clock (cycle counters are per XCD)
 #endif
-    pipe_views<JP, TI, U>(hm, cam, g, bs, x, y, z, inb, ws, lane, acc, mymask, tl);
+    pipe_views<JP, TI, U, PS>(hm, cam, g, bs, x, y, z, inb, ws, lane, acc, mymask, tl);
 
     // view fusion (project_layer.py:96-99) on the gather mapping, result tile -> LDS
     __builtin_amdgcn_wave_barrier();
@@ -646,7 +646,9 @@ __device__ __forceinline__ void pipe_tile(const Views &hm, const float *__restri
 
 // NW = waves per workgroup (waves are independent; NW only sets the dispatch granularity)
 // TI / TO: storage type of the packed heat-maps / of the cubes (float or bf16_t); math is fp32.
-template <int JP, bool XCD, int NW, bool OUTCL, typename TI = float, typename TO = float>
+// PS: elements per packed pixel (the buffer's channel stride); JP channels from the pixel start are gathered.  PS > JP is one
+// channel group of a wider pixel (launch_nhwc_wide: `hm` then points at the group's first channel).
+template <int JP, bool XCD, int NW, bool OUTCL, typename TI = float, typename TO = float, int PS = JP>
 __global__ __launch_bounds__(64 * NW) void unproject_pipe_kernel(Views hm, const float *__restrict__ cam,
                                                              const float *__restrict__ centers,
                                                              const uint8_t *__restrict__ valid,
@@ -663,7 +665,7 @@ __global__ __launch_bounds__(64 * NW) void unproject_pipe_kernel(Views hm, const
         tile = blockIdx.x - b * tiles_per_sample;
     }
     (void)total_tiles;
-    pipe_tile<JP, NW, OUTCL, TI, TO>(hm, cam, centers, valid, cubes, grids, g, b, tile, smem, blockIdx.x);
+    pipe_tile<JP, NW, OUTCL, TI, TO, 4, PS>(hm, cam, centers, valid, cubes, grids, g, b, tile, smem, blockIdx.x);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -711,7 +713,7 @@ constexpr int BR = 4;
 constexpr int ZDZ = 20, ZDSZ = 28;
 constexpr int SP3D_VARIANT_ZD = 1 << 24;        // launch_nhwc `variant` bit: brick stacks emit the z-spectrum
 constexpr int SP3D_VARIANT_CHUNKS = 1 << 22;    // launch_nhwc `variant` bit: round-5 chunk map of the bricks instead of blocks / octants
-template <int JP, bool OUTCL, typename TI = float, typename TO = float, bool ZD = false>
+template <int JP, bool OUTCL, typename TI = float, typename TO = float, bool ZD = false, int PS = JP>
 __global__ __launch_bounds__(512, ZD ? SP3D_ZD_MINW : SP3D_BRICK_MINW) void unproject_brick_kernel(Views hm, const float *__restrict__ cam,
                                                                 const float *__restrict__ centers,
                                                                 const uint8_t *__restrict__ valid,
@@ -787,7 +789,7 @@ __global__ __launch_bounds__(512, ZD ? SP3D_ZD_MINW : SP3D_BRICK_MINW) void unpr
 #else
         unsigned long long *tl = nullptr;
 #endif
-        pipe_views<JP, TI, ZD ? SP3D_ZD_U : SP3D_BRICK_U>(hm, cam, g, bs, x, y, z, inb, ws, lane, acc, mymask, tl, (g.xcd_order & 4) != 0);
+        pipe_views<JP, TI, ZD ? SP3D_ZD_U : SP3D_BRICK_U, PS>(hm, cam, g, bs, x, y, z, inb, ws, lane, acc, mymask, tl, (g.xcd_order & 4) != 0);
 
         // view fusion (project_layer.py:96-99) on the gather mapping
         __builtin_amdgcn_wave_barrier();
@@ -905,11 +907,12 @@ __device__ __forceinline__ void bf16x8_to_f32(const uint4 r, float (&f)[8])
     f[6] = __uint_as_float(r.w << 16); f[7] = __uint_as_float(r.w & 0xffff0000u);
 }
 
+template <int PS = 16>
 __device__ __forceinline__ void pipe_views_h(const Views &hm, const float *__restrict__ cam, const Geom &g, int bs, float x,
                                              float y, float z, bool inb, float *ws, int lane, float (&acc)[2][8],
                                              uint32_t &mymask)
 {
-    constexpr int JP = 16;
+    // 16 channels per pixel gathered; PS = bf16 elements per packed pixel (16, or 32 for one group of a 32-channel pixel)
     int *wsi = reinterpret_cast<int *>(ws);
     float4 *ws4 = reinterpret_cast<float4 *>(ws);
     const unsigned long long inbm = __builtin_amdgcn_ballot_w64(inb);
@@ -924,13 +927,13 @@ __device__ __forceinline__ void pipe_views_h(const Views &hm, const float *__res
         if (um == 0ull) return false;
         const RecPk r = make_record_pk(lane_of(um), st.i, g.w, g.h);
         const int v = (c & 1) * 64 + lane;
-        wsi[WOFF + v] = (int)__umul24((unsigned)(JP * 2), __umul24((unsigned)r.y0, (unsigned)g.w) + (unsigned)r.x0);     // bytes
+        wsi[WOFF + v] = (int)__umul24((unsigned)(PS * 2), __umul24((unsigned)r.y0, (unsigned)g.w) + (unsigned)r.x0);     // bytes
         ws4[v] = make_float4(r.wt.x, r.wt.y, r.wb.x, r.wb.y);
         return true;
     };
     const int g32 = lane >> 1, q = lane & 1;
     const uint32_t qoff = 16u * (uint32_t)q;                    // this lane's 8 channels, bytes
-    const size_t row_bytes = (size_t)g.w * JP * 2;
+    const size_t row_bytes = (size_t)g.w * PS * 2;
     bool have = P1(0);
 #pragma unroll 1
     for (int c = 0; c < g.V; ++c) {
@@ -947,9 +950,9 @@ __device__ __forceinline__ void pipe_views_h(const Views &hm, const float *__res
 #pragma unroll
             for (int i = 0; i < 2; ++i) {
                 const uint32_t off = (uint32_t)wsi[WOFF + rb + 32 * i] + qoff;
-                t11[i] = *reinterpret_cast<const uint4 *>(vb2 + off + JP * 2);
+                t11[i] = *reinterpret_cast<const uint4 *>(vb2 + off + PS * 2);
                 t01[i] = *reinterpret_cast<const uint4 *>(vb2 + off);
-                t10[i] = *reinterpret_cast<const uint4 *>(vb + off + JP * 2);
+                t10[i] = *reinterpret_cast<const uint4 *>(vb + off + PS * 2);
                 t00[i] = *reinterpret_cast<const uint4 *>(vb + off);
             }
         }
@@ -977,7 +980,7 @@ __device__ __forceinline__ void pipe_views_h(const Views &hm, const float *__res
     }
 }
 
-template <bool OUTCL, typename TO>
+template <bool OUTCL, typename TO, int PS = 16>
 __global__ __launch_bounds__(512, SP3D_BRICK_MINW) void unproject_brick_h_kernel(Views hm, const float *__restrict__ cam,
                                                                   const float *__restrict__ centers,
                                                                   const uint8_t *__restrict__ valid,
@@ -1035,7 +1038,7 @@ __global__ __launch_bounds__(512, SP3D_BRICK_MINW) void unproject_brick_h_kernel
         for (int i = 0; i < 2; ++i)
 #pragma unroll
             for (int k = 0; k < 8; ++k) acc[i][k] = 0.0f;
-        pipe_views_h(hm, cam, g, bs, x, y, z, inb, ws, lane, acc, mymask);
+        pipe_views_h<PS>(hm, cam, g, bs, x, y, z, inb, ws, lane, acc, mymask);
 
         __builtin_amdgcn_wave_barrier();
         const float den_l = (float)(mymask & 0x7fffffffu) + 1e-6f;
@@ -1608,6 +1611,40 @@ static int default_variant(const Geom &g, bool out_cl)
     return (g.Z % 32 == 0) ? 56 : 24;
 }
 
+// workgroup geometry of the brick kernels (4x4x4 voxels per wave, a z-stack of `zw` bricks per workgroup)
+struct BrickPlan {
+    Geom gb;
+    int wgs, nby, nzc, zw, block_grid;
+    size_t blds;
+};
+
+static void plan_bricks(const Geom &g, int variant, int wlds, BrickPlan &p)
+{
+    const int nbx = (g.X + BR - 1) / BR, nby = (g.Y + BR - 1) / BR, nwz = (g.Z + BR - 1) / BR;
+    int nzc = (nwz + 7) / 8, zw = (nwz + nzc - 1) / nzc;
+    if (variant & 64) { zw = 1; nzc = nwz; }                  // tuning: every brick its own workgroup
+    const int wgs = nbx * nby * nzc;
+    Geom gb = g;
+    {   // 2-4 chunks of consecutive workgroups (x-slabs of the volume) per serving XCD
+        const int xps = (g.B <= 8 && (8 % g.B) == 0) ? 8 / g.B : 1;
+        int k = 1;
+        while (k * 2 * xps * 2 <= wgs) k *= 2;
+        if ((variant >> 17) & 15) k = 1 << (((variant >> 17) & 15) - 1);
+        gb.xcd_chunk = k;
+    }
+    set_xcd_fields(gb, wgs);
+    set_brick_fields(gb, nbx * nby, nby);
+    // default since round 6 (B in {1, 2, 4}): one block of brick columns per XCD - octants at B = 1, quadrants at B = 2,
+    // halves at B = 4 - instead of round-robin chunks; same results, L2 fills 138 -> 60 MB on the 160x160x40 grid,
+    // 75 -> 56 MB on the root grid at B = 4 (profiles/r06_pmc_blocks.json).  Tuning bit 22 restores the chunk map.
+    p.block_grid = (variant & SP3D_VARIANT_CHUNKS) || (variant & 256) ? 0 : set_block_fields(gb, nbx, nby, nzc);
+    p.blds = (size_t)zw * wlds * sizeof(float);
+    // round-5 L1-residency experiment (measurement only): tuning bit 10 = view-synchronous workgroups (only when every
+    // wave of every workgroup lies inside the volume, so that all of them reach the per-view barrier)
+    if (((variant >> 10) & 1) && nwz % zw == 0 && nzc * zw == nwz) gb.xcd_order |= 4;
+    p.gb = gb; p.wgs = wgs; p.nby = nby; p.nzc = nzc; p.zw = zw;
+}
+
 template <int JP>
 static int launch_nhwc_jp(const Views &v, const float *cam, const float *centers, const uint8_t *valid, float *cubes,
                           float *grids, const Geom &g, int variant, bool out_cl, int io, hipStream_t s)
@@ -1618,30 +1655,14 @@ static int launch_nhwc_jp(const Views &v, const float *cam, const float *centers
     const bool xcd = !(variant & 4);
     dim3 grid(xcd ? xcd_grid_blocks(g.B, tiles, g.xcd_chunk) : total), block(TILE);
     if (variant & 32) {      // brick kernel: 4x4x4 voxels per wave, a z-stack of bricks per workgroup
-        const int nbx = (g.X + BR - 1) / BR, nby = (g.Y + BR - 1) / BR, nwz = (g.Z + BR - 1) / BR;
-        int nzc = (nwz + 7) / 8, zw = (nwz + nzc - 1) / nzc;
-        if (variant & 64) { zw = 1; nzc = nwz; }                  // tuning: every brick its own workgroup
-        const int wgs = nbx * nby * nzc;
-        Geom gb = g;
-        {   // 2-4 chunks of consecutive workgroups (x-slabs of the volume) per serving XCD
-            const int xps = (g.B <= 8 && (8 % g.B) == 0) ? 8 / g.B : 1;
-            int k = 1;
-            while (k * 2 * xps * 2 <= wgs) k *= 2;
-            if ((variant >> 17) & 15) k = 1 << (((variant >> 17) & 15) - 1);
-            gb.xcd_chunk = k;
-        }
-        set_xcd_fields(gb, wgs);
-        set_brick_fields(gb, nbx * nby, nby);
-        // default since round 6 (B in {1, 2, 4}): one block of brick columns per XCD - octants at B = 1, quadrants at B = 2,
-        // halves at B = 4 - instead of round-robin chunks; same results, L2 fills 138 -> 60 MB on the 160x160x40 grid,
-        // 75 -> 56 MB on the root grid at B = 4 (profiles/r06_pmc_blocks.json).  Tuning bit 22 restores the chunk map.
-        const int block_grid = (variant & SP3D_VARIANT_CHUNKS) || (variant & 256) ? 0 : set_block_fields(gb, nbx, nby, nzc);
         constexpr int WLDS = (JP * WOSTR > WREC) ? JP * WOSTR : WREC;
-        size_t blds = (size_t)zw * WLDS * sizeof(float);
-        // round-5 L1-residency experiment (measurement only): tuning bit 10 = view-synchronous workgroups (only when every
-        // wave of every workgroup lies inside the volume, so that all of them reach the per-view barrier), bits 11-13 = n:
-        // n * 20 KB of unused LDS per workgroup, which caps the workgroups resident on a CU
-        if (((variant >> 10) & 1) && nwz % zw == 0 && nzc * zw == nwz) gb.xcd_order |= 4;
+        BrickPlan bp;
+        plan_bricks(g, variant, WLDS, bp);
+        Geom &gb = bp.gb;
+        const int wgs = bp.wgs, nby = bp.nby, nzc = bp.nzc, zw = bp.zw, block_grid = bp.block_grid;
+        size_t blds = bp.blds;
+        // (round-5 L1-residency experiment, measurement only) tuning bits 11-13 = n: n * 20 KB of unused LDS per
+        // workgroup, which caps the workgroups resident on a CU
         const int ballast = (variant >> 11) & 7;
         if (ballast) {
             blds += (size_t)ballast * 20480;
@@ -1751,6 +1772,92 @@ static int launch_nhwc_jp(const Views &v, const float *cam, const float *centers
     return SP3D_OK;
 }
 
+// ------------------------------------------------------------------------------------------
+// Jp = 32 (17..32 joints: the 17 COCO joints of the Shelf / Campus configurations).  A packed fp32 pixel is exactly one
+// 128-byte line.  It is gathered as two channel groups, one launch each, both reading pixels at a stride of PS = 32:
+//   group 0   channels 0-15 through the JP = 16 kernel;
+//   group 1   channels 16..J-1 through a launch of width JPG = ceil4(J - 16) (16 with bf16 maps or cubes, whose kernels
+//             exist at JP = 16 only).  Its view pointers start 16 channels into the pixel (the wave-uniform row base moves,
+//             no VGPR does), its result pointer 16 channel planes further, and its Geom has J - 16 channels.
+// The per-channel arithmetic is the 16-channel kernels', so each group is bit-identical to the oracle by construction.  Only
+// group 0 writes grids; a sample that `valid` skips gets zeros in each group.  Planar results only (dense or strided: the
+// strided path already carries full-volume strides), default kernels only (pipe / brick stacks), no pass mask.
+// ------------------------------------------------------------------------------------------
+constexpr int WIDE_PS = 32;
+
+template <int JPG>
+static int launch_wide_group(const Views &v, const float *cam, const float *centers, const uint8_t *valid, float *cubes,
+                             float *grids, const Geom &g, int variant, int io, hipStream_t s)
+{
+    constexpr int PS = WIDE_PS;
+    if (variant & 32) {
+        constexpr int WLDS = (JPG * WOSTR > WREC) ? JPG * WOSTR : WREC;
+        BrickPlan bp;
+        plan_bricks(g, variant, WLDS, bp);
+        dim3 bgrid(bp.block_grid ? bp.block_grid : xcd_grid_blocks(bp.gb.B, bp.wgs, bp.gb.xcd_chunk)), bblock(64 * bp.zw);
+#define SP3D_WBRICK(K_) hipLaunchKernelGGL(K_, bgrid, bblock, bp.blds, s, v, cam, centers, valid, cubes, grids, bp.gb, bp.wgs, bp.nby, bp.nzc, bp.zw)
+        if constexpr (JPG == 16) {
+            switch (io) {
+            case 0: SP3D_WBRICK((unproject_brick_kernel<16, false, float, float, false, PS>)); break;
+            case 1: SP3D_WBRICK((unproject_brick_h_kernel<false, float, PS>)); break;          // bf16 maps: two lanes per pixel
+            case 2: SP3D_WBRICK((unproject_brick_kernel<16, false, float, bf16_t, false, PS>)); break;
+            default: SP3D_WBRICK((unproject_brick_h_kernel<false, bf16_t, PS>)); break;
+            }
+        } else {
+            if (io) return SP3D_EUNSUPPORTED;
+            SP3D_WBRICK((unproject_brick_kernel<JPG, false, float, float, false, PS>));
+        }
+#undef SP3D_WBRICK
+        return SP3D_OK;
+    }
+    // pipe kernel, one wave per workgroup, XCD-aware tile map (default_variant 24)
+    const int ptiles = (g.N + 63) / 64;
+    dim3 pgrid(xcd_grid_blocks(g.B, ptiles, g.xcd_chunk)), pblock(64);
+    Geom gp = g;
+    set_xcd_fields(gp, ptiles);
+#define SP3D_WPIPE(TI_, TO_) \
+    hipLaunchKernelGGL((unproject_pipe_kernel<JPG, true, 1, false, TI_, TO_, PS>), pgrid, pblock, 0, s, v, cam, centers, valid, cubes, grids, gp, ptiles, ptiles * g.B)
+    if constexpr (JPG == 16) {
+        switch (io) {
+        case 0: SP3D_WPIPE(float, float); break;
+        case 1: SP3D_WPIPE(bf16_t, float); break;
+        case 2: SP3D_WPIPE(float, bf16_t); break;
+        default: SP3D_WPIPE(bf16_t, bf16_t); break;
+        }
+    } else {
+        if (io) return SP3D_EUNSUPPORTED;
+        SP3D_WPIPE(float, float);
+    }
+#undef SP3D_WPIPE
+    return SP3D_OK;
+}
+
+static int launch_nhwc_wide(const Views &v, const float *cam, const float *centers, const uint8_t *valid, float *cubes,
+                            float *grids, const Geom &g, int variant, int io, hipStream_t s)
+{
+    // the default planar variants only: 24 (pipe, one wave per workgroup, XCD map) and 56 (brick stacks)
+    if (variant != 24 && variant != 56) return SP3D_EUNSUPPORTED;
+    const size_t esz = (io & 1) ? 2 : 4, osz = (io & 2) ? 2 : 4;
+    const int J0 = g.J < 16 ? g.J : 16, J1 = g.J - J0;
+    Geom g0 = g;
+    g0.J = J0;
+    int rc = launch_wide_group<16>(v, cam, centers, valid, cubes, grids, g0, variant, io, s);
+    if (rc || J1 == 0) return rc;
+    Views v1;
+    for (int c = 0; c < SP3D_MAX_VIEWS; ++c)
+        v1.p[c] = v.p[c] ? reinterpret_cast<const float *>(reinterpret_cast<const char *>(v.p[c]) + 16 * esz) : nullptr;
+    float *cubes1 = reinterpret_cast<float *>(reinterpret_cast<char *>(cubes) + (size_t)16 * g.sJ * osz);
+    Geom g1 = g;
+    g1.J = J1;
+    if (io) return launch_wide_group<16>(v1, cam, centers, valid, cubes1, nullptr, g1, variant, io, s);
+    switch ((J1 + 3) / 4) {
+    case 1: return launch_wide_group<4>(v1, cam, centers, valid, cubes1, nullptr, g1, variant, io, s);
+    case 2: return launch_wide_group<8>(v1, cam, centers, valid, cubes1, nullptr, g1, variant, io, s);
+    case 3: return launch_wide_group<12>(v1, cam, centers, valid, cubes1, nullptr, g1, variant, io, s);
+    default: return launch_wide_group<16>(v1, cam, centers, valid, cubes1, nullptr, g1, variant, io, s);
+    }
+}
+
 // io: bit 0 = packed heat-maps are bf16, bit 1 = cubes are bf16
 static int launch_nhwc(const Views &v, int Jp, const float *cam, const float *centers, const uint8_t *valid,
                        float *cubes, float *grids, const Geom &g_in, int variant, bool out_cl, int io, hipStream_t s)
@@ -1770,6 +1877,16 @@ static int launch_nhwc(const Views &v, int Jp, const float *cam, const float *ce
         int k = 1;
         while (k * 2 * xps * 2 <= t64) k *= 2;
         g.xcd_chunk = k;
+    }
+    if (Jp == WIDE_PS) {
+        // 17..32 channels (see launch_nhwc_wide): planar results of the default kernels; no channels-last result, no pass
+        // mask, no z-spectrum, and the pipelined kernels' limits on the image (2x2 block, 24-bit pixel indices)
+        if (g.J > WIDE_PS || out_cl || g.pass_mask || (variant & SP3D_VARIANT_ZD) || g.w < 2 || g.h < 2 ||
+            (int64_t)g.h * g.w > (1 << 24))
+            return SP3D_EUNSUPPORTED;
+        if (io) variant |= 16;
+        const int rc = launch_nhwc_wide(v, cam, centers, valid, cubes, grids, g, variant, io, s);
+        return rc ? rc : launch_status();
     }
     if (Jp < g.J || (Jp & 3) || Jp > 16) return SP3D_EUNSUPPORTED;
     if (out_cl && (g.J & 3)) return SP3D_EUNSUPPORTED;           // channels-last rows must be 16-B multiples
@@ -1858,13 +1975,21 @@ extern "C" int sp3d_pack_heatmaps_ex(const void *const *hm_views, void *packed, 
         case 8: hipLaunchKernelGGL(pack_nhwc_kernel<8>, grid, block, 0, s, v, pk, B, J, HW); break;
         case 12: hipLaunchKernelGGL(pack_nhwc_kernel<12>, grid, block, 0, s, v, pk, B, J, HW); break;
         case 16: hipLaunchKernelGGL(pack_nhwc_kernel<16>, grid, block, 0, s, v, pk, B, J, HW); break;
+        case 32: hipLaunchKernelGGL(pack_nhwc_kernel<32>, grid, block, 0, s, v, pk, B, J, HW); break;
         default: return SP3D_EUNSUPPORTED;
         }
     } else {
-        if (Jp != 16) return SP3D_EUNSUPPORTED;
-        if (in_bf16 && out_bf16) hipLaunchKernelGGL((pack_nhwc_kernel<16, bf16_t, bf16_t>), grid, block, 0, s, v, pk, B, J, HW);
-        else if (in_bf16) hipLaunchKernelGGL((pack_nhwc_kernel<16, bf16_t, float>), grid, block, 0, s, v, pk, B, J, HW);
-        else hipLaunchKernelGGL((pack_nhwc_kernel<16, float, bf16_t>), grid, block, 0, s, v, pk, B, J, HW);
+        if (Jp == 16) {
+            if (in_bf16 && out_bf16) hipLaunchKernelGGL((pack_nhwc_kernel<16, bf16_t, bf16_t>), grid, block, 0, s, v, pk, B, J, HW);
+            else if (in_bf16) hipLaunchKernelGGL((pack_nhwc_kernel<16, bf16_t, float>), grid, block, 0, s, v, pk, B, J, HW);
+            else hipLaunchKernelGGL((pack_nhwc_kernel<16, float, bf16_t>), grid, block, 0, s, v, pk, B, J, HW);
+        } else if (Jp == 32) {
+            if (in_bf16 && out_bf16) hipLaunchKernelGGL((pack_nhwc_kernel<32, bf16_t, bf16_t>), grid, block, 0, s, v, pk, B, J, HW);
+            else if (in_bf16) hipLaunchKernelGGL((pack_nhwc_kernel<32, bf16_t, float>), grid, block, 0, s, v, pk, B, J, HW);
+            else hipLaunchKernelGGL((pack_nhwc_kernel<32, float, bf16_t>), grid, block, 0, s, v, pk, B, J, HW);
+        } else {
+            return SP3D_EUNSUPPORTED;
+        }
     }
     return launch_status();
 }

@@ -8,7 +8,7 @@ from __future__ import annotations
 import torch
 import torch.nn as nn
 
-from .project_layer import ProjectLayer
+from .project_layer import ProjectLayer, nhwc_direct_ok
 from .proposal import nms_with_locations
 from .v2v_net import V2VNet
 
@@ -79,7 +79,7 @@ class CuboidProposalNet(nn.Module):
             hms = all_heatmaps
         planar = self.v2v_net.wants_planar_input() and hms[0].is_cuda      # FFT opening conv: plain J-channel cubes
         # ... which the unprojection kernel writes straight into that conv's zero-padded input buffer
-        direct = planar and hms[0].shape[1] <= 16 and not torch.is_grad_enabled()
+        direct = planar and nhwc_direct_ok(hms, self.project_layer) and not torch.is_grad_enabled()
         # ... on this grid as channels-last 16-channel cubes (its z pass is a HIP kernel that reads them as they are),
         cl16 = direct and self.v2v_net.wants_channels_last_cubes(*self.cube_size)
         # ... otherwise straight into that conv's zero-padded planar input buffer

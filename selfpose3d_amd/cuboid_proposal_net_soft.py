@@ -17,7 +17,7 @@ import torch
 import torch.nn as nn
 
 from .cuboid_proposal_net import ProposalLayer
-from .project_layer import ProjectLayer
+from .project_layer import ProjectLayer, nhwc_direct_ok
 from .v2v_net import V2VNet
 
 
@@ -67,7 +67,7 @@ class CuboidProposalNetSoft(nn.Module):
     def _root_cubes(self, hms, meta, flip_xcoords):
         planar = self.v2v_net.wants_planar_input() and hms[0].is_cuda      # FFT opening conv: plain J-channel cubes
         out = self.v2v_net.input_view(hms[0].shape[0], *self.cube_size, hms[0].device) \
-            if planar and hms[0].shape[1] <= 16 and not torch.is_grad_enabled() else None
+            if planar and nhwc_direct_ok(hms, self.project_layer) and not torch.is_grad_enabled() else None
         cubes, _ = self.project_layer.get_voxel(hms, meta, self.grid_size, [self.grid_center], self.cube_size,
                                                 flip_xcoords=flip_xcoords, want_grids=False, pad_channels=not planar,
                                                 channels_last=self.channels_last and not planar, out=out)

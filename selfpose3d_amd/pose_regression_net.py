@@ -11,7 +11,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import _lib
-from .project_layer import ProjectLayer
+from .project_layer import ProjectLayer, nhwc_direct_ok
 from .v2v_net import V2VNet
 
 
@@ -65,7 +65,7 @@ class PoseRegressionNet(nn.Module):
         flip = None if flip_xcoords is None else flip_xcoords
         planar = self.v2v_net.wants_planar_input()                       # FFT opening conv: plain J-channel cubes
         direct = self.v2v_net.input_chunk_views(P, max_cubes_per_call, *self.cube_size, device) \
-            if planar and J <= 16 else None
+            if planar and nhwc_direct_ok(all_heatmaps, self.project_layer) else None
         if direct is not None:
             # the kernel writes every cube straight into the zero-padded input buffer of the FFT opening conv
             whole, chunks = direct

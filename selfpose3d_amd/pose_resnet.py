@@ -202,7 +202,8 @@ class PoseResNet(nn.Module):
         each view's B images apart, so both are the per-view loop's numbers (the loop itself remains for CPU tensors,
         channels_last weights, partly frozen BatchNorm or ``batch_views_in_training = False``).
 
-        On the GPU the 1x1 head runs with its filter bank zero-padded to ceil4(J) outputs in channels_last, so its
+        On the GPU the 1x1 head runs with its filter bank zero-padded to ProjectLayer.jp_for(J) outputs (ceil4(J) up to 16
+        joints, 32 for 17..32) in channels_last, so its
         result IS the (V,B,h,w,Jp) buffer the unprojection kernel gathers from; the returned per-view tensors are
         (B,J,h,w) views of it (``project_layer.nhwc_heatmap_views``) and the re-tiling pass disappears."""
         V, B = len(views), views[0].shape[0]
@@ -243,7 +244,7 @@ class PoseResNet(nn.Module):
         x = torch.cat(list(views), 0).contiguous(memory_format=torch.channels_last)
         fl = self.final_layer
         J = fl.out_channels
-        if not x.is_cuda or J > 16:
+        if not x.is_cuda or J > 32:
             y = self.forward(x).contiguous()
             return list(y.view(V, B, *y.shape[1:]).unbind(0))
         from .project_layer import ProjectLayer, nhwc_heatmap_views

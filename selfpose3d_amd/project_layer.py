@@ -53,7 +53,7 @@ def clear_pack_cache():
 def nhwc_heatmap_views(packed: torch.Tensor, num_joints: int) -> "list[torch.Tensor]":
     """``packed`` (V,B,h,w,Jp), channels >= num_joints ZERO  ->  list[V] of (B,J,h,w) tensors that are strided views
     of it (no copy).  This is how a producer that already works channels-last (``PoseResNet.forward_views``: the
-    1x1 head emits 16 channels, the 16th filter being zero) hands its heat-maps over: every consumer sees the
+    1x1 head emits jp_for(J) channels - 16 or 32 - the filters beyond J being zero) hands its heat-maps over: every consumer sees the
     reference's ``list[V] of (B,J,h,w)`` and ``ProjectLayer`` recognises the views and skips its re-tiling pass -
     the kernel reads the producer's buffer directly (``SP3D_LAYOUT_NHWC`` takes per-view pointers)."""
     V, B, h, w, Jp = packed.shape
@@ -65,6 +65,17 @@ def nhwc_heatmap_views(packed: torch.Tensor, num_joints: int) -> "list[torch.Ten
         t._sp3d_packed = (packed, c)
         views.append(t)
     return views
+
+
+def nhwc_direct_ok(hms: Sequence[torch.Tensor], layer: "ProjectLayer" = None) -> bool:
+    """``layer`` (mode "auto" or "nhwc") takes these heat-maps through the NHWC kernels, so that a producer may hand it an
+    ``out`` buffer (``get_voxel(out=...)``): up to 16 joints, and 17..32 joints when no heat-map gradient is requested"""
+    if layer is not None and layer.mode == "planar":
+        return False
+    J = int(hms[0].shape[1])
+    if J <= 16:
+        return True
+    return J <= 32 and not (torch.is_grad_enabled() and any(h.requires_grad for h in hms))
 
 
 def _packed_source(hms: Sequence[torch.Tensor], jp: int, dtype: torch.dtype):
@@ -106,7 +117,7 @@ class _UnprojectFn(torch.autograd.Function):
             views = [packed[c] for c in range(len(hms))]
             # when a gradient will be asked for, let the kernel also emit the clamp pass mask: the backward
             # then runs the line-coalesced scatter without re-reading any heat-map
-            need_grad = io == torch.float32 and any(ctx.needs_input_grad[12:]) and w >= 2 and h >= 2
+            need_grad = io == torch.float32 and any(ctx.needs_input_grad[12:]) and w >= 2 and h >= 2 and jp <= 16
             X, Y, Z = cube_size
             mask = torch.empty((B, X * Y * Z), dtype=torch.int16, device=cam.device) if need_grad else None
             # pad_channels: run the kernel over all jp channels - the padded ones are zero in `packed`,
@@ -159,8 +170,8 @@ class _UnprojectFn(torch.autograd.Function):
 
 
 class ProjectLayer(nn.Module):
-    """See module docstring.  ``mode``: "nhwc" (re-tile + fast kernel, J <= 16), "planar"
-    (direct kernel on the reference layout) or "auto"."""
+    """See module docstring.  ``mode``: "nhwc" (re-tile + fast kernel: J <= 16, and J <= 32 without a heat-map
+    gradient), "planar" (direct kernel on the reference layout) or "auto" (nhwc wherever it applies)."""
 
     def __init__(self, cfg, mode: str = "auto", io_dtype: torch.dtype = torch.float32):
         super().__init__()
@@ -192,7 +203,8 @@ class ProjectLayer(nn.Module):
 
     @staticmethod
     def jp_for(J: int) -> int:
-        return 4 if J <= 4 else (8 if J <= 8 else (12 if J <= 12 else 16))
+        """channel stride of the packed heat-maps: ceil4(J) up to 16, then one 32-float (128-byte) pixel for 17..32"""
+        return 4 if J <= 4 else (8 if J <= 8 else (12 if J <= 12 else (16 if J <= 16 else 32)))
 
     # -- host side -----------------------------------------------------------------------
     def camera_table(self, meta: Sequence[dict], batch: int, flip_xcoords, device) -> torch.Tensor:
@@ -290,11 +302,18 @@ class ProjectLayer(nn.Module):
         if isinstance(grid_size, (int, float)):
             grid_size = [grid_size] * 3
         mode = self.mode
+        # 17..32 joints (Jp = 32): forward only - the pass mask of the packed backward holds 16 bits per voxel, so a
+        # heat-map gradient keeps the planar kernels there
+        wide = 16 < J <= 32
+        grad_hm = torch.is_grad_enabled() and any(x.requires_grad for x in heatmaps)
         if mode == "auto":
-            mode = "nhwc" if (J <= 16 and w >= 2 and h >= 2) else "planar"
-        if self.io_dtype != torch.float32 and (mode != "nhwc" or self.jp_for(J) != 16):
-            raise _lib.Sp3dError("bf16 storage needs the NHWC path with 13..16 joints")
-        if mode != "nhwc":
+            mode = "nhwc" if ((J <= 16 or (wide and not grad_hm)) and w >= 2 and h >= 2) else "planar"
+        elif mode == "nhwc" and J > 16 and grad_hm:
+            raise _lib.Sp3dError(f"ProjectLayer(mode='nhwc'): {J} joints with a heat-map gradient - the NHWC path "
+                                 "differentiates at most 16 joints (use mode='planar' or 'auto')")
+        if self.io_dtype != torch.float32 and (mode != "nhwc" or self.jp_for(J) not in (16, 32) or J > 32):
+            raise _lib.Sp3dError("bf16 storage needs the NHWC path with 13..32 joints")
+        if mode != "nhwc" or J > 16:
             pad_channels = channels_last = False
         if channels_last and not pad_channels and (J & 3):
             channels_last = False

@@ -68,18 +68,49 @@ def ring_cameras(num_views: int, radius: float = 3000.0, height: float = 2000.0,
     return cams
 
 
+# Rigs of the reference's Shelf / Campus synthetic datasets, chosen by DATASET.TRAIN_DATASET / TEST_DATASET: camera count
+# and image size as there (lib/dataset/campus_synthetic.py:80,212-213: 3 cameras of 360x288; shelf_synthetic.py:82,214-215:
+# 5 cameras of 1032x776).  Their calibrations are data files that are not in the image, so the cameras here are distortion-
+# free pin-holes on a ring around SPACE_CENTER, principal point at the image centre, aimed at SPACE_CENTER:
+#   name -> (cameras, (width, height), focal length px, ring radius mm, camera height mm)
+RIGS = {
+    "campus_synthetic": (3, (360, 288), 320.0, 6000.0, 2600.0),
+    "shelf_synthetic": (5, (1032, 776), 760.0, 4500.0, 2600.0),
+}
+
+
+def rig_cameras(name: str, target: Sequence[float]):
+    """(cameras, (width, height)) of the Shelf / Campus rig ``name`` aimed at ``target``; None for any other dataset name"""
+    if name not in RIGS:
+        return None
+    V, (W, H), f, radius, height = RIGS[name]
+    cams = ring_cameras(V, radius=radius, height=height, target=tuple(float(t) for t in target))
+    for c in cams:
+        c.update({"fx": np.float64(f), "fy": np.float64(f), "cx": np.float64(W / 2.0), "cy": np.float64(H / 2.0),
+                  "k": np.zeros((3, 1), np.float64), "p": np.zeros((2, 1), np.float64)})
+    return cams, (W, H)
+
+
 def make_meta(batch: int, num_views: int, image_size: Sequence[int],
               rotations: Optional[Sequence[float]] = None,
               scale_mults: Optional[Sequence[float]] = None,
-              ssv_style: bool = False) -> List[dict]:
+              ssv_style: bool = False, rig: Optional[str] = None,
+              target: Sequence[float] = SPACE_CENTER) -> List[dict]:
     """Per-view meta dicts with a leading batch dim (what default collate emits).
+
+    ``rig``: a name of ``RIGS`` (the Shelf / Campus camera rigs, aimed at ``target``) instead of the Panoptic ring.
 
     ``rotations`` / ``scale_mults`` are per-sample augmentation (degrees, multiplier);
     None = the un-augmented validation path (rotation 0, int64 like the reference).
     ``ssv_style`` emits fp32 camera tensors (JointsDatasetSSV.py:230-237).
     """
-    cams = ring_cameras(num_views)
-    base_scale = get_scale(ORIG_IMAGE, image_size)
+    if rig is None:
+        cams, orig = ring_cameras(num_views), ORIG_IMAGE
+    else:
+        cams, orig = rig_cameras(rig, target)
+        if len(cams) != num_views:
+            raise ValueError(f"the {rig} rig has {len(cams)} cameras, not {num_views}")
+    base_scale = get_scale(orig, image_size)
     metas = []
     for v in range(num_views):
         cam = cams[v]
@@ -97,7 +128,7 @@ def make_meta(batch: int, num_views: int, image_size: Sequence[int],
         if ssv_style:                                          # JointsDatasetSSV.py:230-237 also stores the pairs
             camera["f"] = torch.stack([camera["fx"], camera["fy"]], -1).reshape(batch, 2, 1)
             camera["c"] = torch.stack([camera["cx"], camera["cy"]], -1).reshape(batch, 2, 1)
-        center = torch.tensor([[ORIG_IMAGE[0] / 2.0, ORIG_IMAGE[1] / 2.0]] * batch, dtype=torch.float64)
+        center = torch.tensor([[orig[0] / 2.0, orig[1] / 2.0]] * batch, dtype=torch.float64)
         scale = np.repeat(base_scale[None], batch, 0).copy()
         if scale_mults is not None:
             scale = scale * np.asarray(scale_mults, dtype=np.float32)[:, None]

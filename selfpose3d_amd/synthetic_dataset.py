@@ -2,6 +2,11 @@
 emit (/root/reference/lib/dataset/JointsDataset.py:102-225, panoptic.py:221-233) without any real data
 (the CMU Panoptic files and OpenCV are not in the image).  Deterministic per (seed, index).
 
+The camera rig follows the dataset name (``DATASET.TEST_DATASET``, or the ``dataset`` argument): ``campus_synthetic`` and
+``shelf_synthetic`` get the reference's Campus / Shelf camera count and image size (``synthetic.RIGS``), with the people
+moved to SPACE_CENTER; any other name keeps the Panoptic ring of 1920x1080 cameras.  A list ``DATASET.ROOTIDX`` means the
+mean of the listed joints (lib/dataset/JointsDataset.py:207-210).
+
 item = (inputs[V] (3,H,W), target_heatmaps[V] (J,h,w), target_weights[V] (J,1), targets_3d[V] (X,Y,Z),
         meta[V] dict, input_heatmaps[V] (J,h,w))  - default_collate adds the batch dim.
 """
@@ -15,7 +20,8 @@ from . import synthetic as syn
 
 
 class SyntheticPanoptic(Dataset):
-    def __init__(self, cfg, num_frames: int = 32, seed: int = 0, max_people: int = 4, images: bool = True):
+    def __init__(self, cfg, num_frames: int = 32, seed: int = 0, max_people: int = 4, images: bool = True,
+                 dataset: str = None):
         self.cfg = cfg
         self.n = int(num_frames)
         self.seed = int(seed)
@@ -28,13 +34,33 @@ class SyntheticPanoptic(Dataset):
         self.cube = [int(v) for v in cfg.MULTI_PERSON.INITIAL_CUBE_SIZE]
         self.maxp = int(cfg.MULTI_PERSON.MAX_PEOPLE_NUM)
         self.max_people = min(max_people, self.maxp)
-        self.root_id = int(cfg.DATASET.ROOTIDX) if not isinstance(cfg.DATASET.ROOTIDX, (list, tuple)) else 2
+        rid = cfg.DATASET.ROOTIDX
+        self.root_id = [int(r) for r in rid] if isinstance(rid, (list, tuple)) else int(rid)
         self.images = images
-        self.cams = syn.ring_cameras(self.V)
-        self.scale = syn.get_scale(syn.ORIG_IMAGE, self.img)
+        self.dataset = str(dataset if dataset is not None else cfg.DATASET.TEST_DATASET)
+        rig = syn.rig_cameras(self.dataset, self.space_center)
+        if rig is None:
+            self.cams, self.orig = syn.ring_cameras(self.V), tuple(syn.ORIG_IMAGE)
+            self.offset = np.zeros(3)
+        else:
+            self.cams, self.orig = rig
+            if len(self.cams) != self.V:
+                raise ValueError(f"DATASET.CAMERA_NUM = {self.V} but the {self.dataset} rig has {len(self.cams)} cameras")
+            # people_points scatters roots around the Panoptic centre (0, -500): move them to this space's centre
+            self.offset = np.array([self.space_center[0], self.space_center[1] + 500.0, 0.0])
+        self.scale = syn.get_scale(self.orig, self.img)
 
     def __len__(self):
         return self.n
+
+    def _roots(self, j3d):
+        """(maxp, 3) root of every person slot: joint ROOTIDX, or the mean of the listed joints"""
+        if isinstance(self.root_id, list):
+            return j3d[:, self.root_id].mean(axis=1)
+        return j3d[:, self.root_id]
+
+    def _people(self, idx):
+        return syn.people_points(1, self.J, self.seed * 100003 + idx)[0][:self.max_people] + self.offset
 
     def _image(self, idx, v):
         """N(0,1) camera image from a small pool (content is irrelevant to the geometry; avoids 7 M normal
@@ -65,7 +91,7 @@ class SyntheticPanoptic(Dataset):
         sigma = float(self.cfg.NETWORK.SIGMA)
         s = self.scale.astype(np.float64) * 200.0
         a = self.img[0] / s[0] if s[0] >= s[1] else self.img[1] / s[1]
-        t = np.array([self.img[0] / 2.0, self.img[1] / 2.0]) - a * np.array(syn.ORIG_IMAGE) / 2.0
+        t = np.array([self.img[0] / 2.0, self.img[1] / 2.0]) - a * np.array(self.orig) / 2.0
         xs, ys = np.arange(w, dtype=np.float64), np.arange(h, dtype=np.float64)
         P = joints.shape[0]
         out = []
@@ -80,13 +106,12 @@ class SyntheticPanoptic(Dataset):
 
     def __getitem__(self, idx):
         w, h = self.hm
-        pts = syn.people_points(1, self.J, self.seed * 100003 + idx)
-        joints = pts[0][:self.max_people]                              # (P,J,3)
+        joints = self._people(idx)                                     # (P,J,3)
         hms = [x[None] for x in self._render(joints)]
         P = joints.shape[0]
         j3d = np.zeros((self.maxp, self.J, 3)); j3d[:P] = joints
         vis = np.zeros((self.maxp, self.J, 3)); vis[:P] = 1.0
-        roots = j3d[:, self.root_id]
+        roots = self._roots(j3d)
         t3d = torch.from_numpy(self._target_3d(roots[:P]))
         inputs, targets, weights, t3ds, metas, ihm = [], [], [], [], [], []
         for v in range(self.V):
@@ -99,7 +124,7 @@ class SyntheticPanoptic(Dataset):
             ihm.append(hms[v][0])
             metas.append({
                 "image": f"synthetic/{idx:06d}_{v}", "num_person": P, "joints_3d": j3d, "joints_3d_vis": vis,
-                "roots_3d": roots, "center": np.array([syn.ORIG_IMAGE[0] / 2.0, syn.ORIG_IMAGE[1] / 2.0]),
+                "roots_3d": roots, "center": np.array([self.orig[0] / 2.0, self.orig[1] / 2.0]),
                 "scale": self.scale.copy(), "rotation": 0,
                 "camera": {k: (np.asarray(val)) for k, val in cam.items()},
             })
@@ -121,12 +146,12 @@ class SyntheticPanopticSSV(SyntheticPanoptic):
         w, h = self.hm
         sigma = float(self.cfg.NETWORK.SIGMA)
         P = joints.shape[0]
-        center = np.array([syn.ORIG_IMAGE[0] / 2.0, syn.ORIG_IMAGE[1] / 2.0])
+        center = np.array([self.orig[0] / 2.0, self.orig[1] / 2.0])
         scale = (self.scale * np.float32(mult)).astype(np.float32)
         trans = get_affine_transform_batch(center[None], scale[None], np.array([rot], np.float64), self.img)[0]
         j3d = np.zeros((self.maxp, self.J, 3)); j3d[:P] = joints
         vis3 = np.zeros((self.maxp, self.J, 3)); vis3[:P] = 1.0
-        roots = j3d[:, self.root_id]
+        roots = self._roots(j3d)
         t3d = torch.from_numpy(self._target_3d(roots[:P]))
         xs, ys = np.arange(w, dtype=np.float64), np.arange(h, dtype=np.float64)
         stride = np.array([self.img[0] / w, self.img[1] / h])
@@ -154,8 +179,7 @@ class SyntheticPanopticSSV(SyntheticPanoptic):
     def __getitem__(self, idx):
         ds = self.cfg.DATASET
         rng = np.random.default_rng(self.seed * 7919 + idx)
-        pts = syn.people_points(1, self.J, self.seed * 100003 + idx)
-        joints = pts[0][:self.max_people]
+        joints = self._people(idx)
         out = ()
         for k in (1, 2):
             rf, sf = float(ds.get(f"ROT_FACTOR{k}", 45)), float(ds.get(f"SCALE_FACTOR{k}", 0.35))
