@@ -28,12 +28,71 @@ MAX_VIEWS = 16
 MAX_TOPK = 32
 ABI_VERSION = 3
 
-EXPORTS = [
-    "sp3d_abi_version", "sp3d_error_string", "sp3d_pack_heatmaps", "sp3d_unproject_fwd", "sp3d_unproject_bwd",
-    "sp3d_nms_topk_workspace_bytes", "sp3d_nms_topk", "sp3d_nms_proposals", "sp3d_soft_argmax", "sp3d_unproject_fwd_indexed",
-    "sp3d_unproject_bwd_indexed", "sp3d_unproject_fwd_strided", "sp3d_fetch_ring", "sp3d_maxpool2x_cl", "sp3d_crop_shift_act_cl", "sp3d_rfft3d", "sp3d_irfft3d", "sp3d_cfft2d", "sp3d_cfft2d_ex", "sp3d_zdft_fwd_cl", "sp3d_zdft_inv_cl", "sp3d_unproject_fwd_zdft", "sp3d_cfft2d_88_tiled", "sp3d_freq_contract_ty", "sp3d_soft_argmax_grid", "sp3d_soft_argmax_grid_train", "sp3d_soft_argmax_grid_bwd", "sp3d_channel_shift_act", "sp3d_pack_heatmaps_ex",
-    "sp3d_unproject_fwd_train", "sp3d_unproject_bwd_packed", "sp3d_unproject_bwd_packed_det", "sp3d_fixed_to_float", "sp3d_gaussian_target_3d", "sp3d_render_root_heatmaps", "sp3d_freq_contract", "sp3d_freq_contract_ex", "sp3d_wino_input", "sp3d_wino_output", "sp3d_wino_fused", "sp3d_wino_fused_split", "sp3d_wino_fused_split64", "sp3d_conv3_split", "sp3d_camera_finish", "sp3d_upsample2x_scatter", "sp3d_upsample2x_scatter_head", "sp3d_render_joints_fwd", "sp3d_render_joints_bwd", "sp3d_gbn_workspace_bytes", "sp3d_gbn_forward", "sp3d_gbn_backward",
-]
+# The C ABI, one line per entry point: "<return>: <arguments>", one letter per type (blanks only group runs for the eye).
+#   p  pointer - any parameter declared with * or [] (device pointers, host arrays, the stream): c_void_p
+#   i  int / int32_t      l  int64_t      f  float      d  double      s  const char * (return only)
+# tests/test_host_cabi.py parses the prototypes of the header and holds every line against it, both ways.
+_CTYPES = {"p": C.c_void_p, "i": C.c_int, "l": C.c_int64, "f": C.c_float, "d": C.c_double, "s": C.c_char_p}
+
+SIGNATURES = {                                  # include/sp3d.h, in the header's order
+    "sp3d_abi_version": "i:",
+    "sp3d_camera_finish": "i: p i",
+    "sp3d_error_string": "s: i",
+    "sp3d_pack_heatmaps": "i: pp iiiiii p",
+    "sp3d_pack_heatmaps_ex": "i: pp iiiiiiii p",
+    "sp3d_unproject_fwd": "i: p ii ppppp iiiiiiii p ii p",
+    "sp3d_unproject_fwd_indexed": "i: p ii pppppp iiiiiiii p ii p",
+    "sp3d_unproject_fwd_strided": "i: p ii pppppp iiiiiiii p ii p",
+    "sp3d_unproject_bwd": "i: pppppp iiiiiiii p ii p",
+    "sp3d_unproject_bwd_indexed": "i: ppppppp iiiiiiii p ii p",
+    "sp3d_unproject_fwd_train": "i: p ii ppppppp iiiiiiii p ii p",
+    "sp3d_unproject_bwd_packed": "i: ppppppp iiiiiiiiii p iii p",
+    "sp3d_unproject_bwd_packed_det": "i: pppppppp iiiiiiiiii p iii p",
+    "sp3d_fixed_to_float": "i: ppp l p",
+    "sp3d_nms_topk_workspace_bytes": "l: iiiii",
+    "sp3d_nms_topk": "i: p iiiii ppppppp",
+    "sp3d_nms_proposals": "i: p iiiii pp f pppppp",
+    "sp3d_soft_argmax": "i: ppp ii l f p",
+    "sp3d_soft_argmax_grid": "i: ppp iii p ii f p",
+    "sp3d_soft_argmax_grid_train": "i: ppp iii pp ii f p",
+    "sp3d_soft_argmax_grid_bwd": "i: ppp iii pppp ii f p",
+    "sp3d_channel_shift_act": "i: ppp i l i l i p",
+    "sp3d_fetch_ring": "i: ppp ii p",
+    "sp3d_maxpool2x_cl": "i: pp iiiii p",
+    "sp3d_crop_shift_act_cl": "i: ppp iiiiiiiii p",
+    "sp3d_rfft3d": "i: pp iiii p",
+    "sp3d_irfft3d": "i: pp iiii p",
+    "sp3d_cfft2d": "i: p iiii p",
+    "sp3d_cfft2d_ex": "i: p iiiiii p",
+    "sp3d_zdft_fwd_cl": "i: pp iiiiiiiii p",
+    "sp3d_zdft_inv_cl": "i: ppp iiiiiiiii p",
+    "sp3d_unproject_fwd_zdft": "i: p i pppp iiiiiiii p iii p",
+    "sp3d_cfft2d_88_tiled": "i: pp iii p",
+    "sp3d_freq_contract_ty": "i: pppp iiiii p",
+    "sp3d_gaussian_target_3d": "i: p ii ppp iii f pp",
+    "sp3d_render_root_heatmaps": "i: p ii p iii f pp",
+    "sp3d_render_joints_fwd": "i: pp iiiii f pp",
+    "sp3d_render_joints_bwd": "i: ppp iiiii f pp",
+    "sp3d_freq_contract": "i: ppp iii l p",
+    "sp3d_freq_contract_ex": "i: ppp iii lllll ii p",
+    "sp3d_wino_input": "i: pp iiiii p",
+    "sp3d_wino_output": "i: pppp iiiiii p",
+    "sp3d_wino_fused": "i: ppppp iiiiiii p",
+    "sp3d_wino_fused_split": "i: ppppp iiiiiii p",
+    "sp3d_wino_fused_split64": "i: ppppp iiiiiii p",
+    "sp3d_conv3_split": "i: ppppp iiiiiii p",
+    "sp3d_upsample2x_scatter": "i: pppp l iiii p",
+    "sp3d_upsample2x_scatter_head": "i: pppppp l iiiii p",
+    "sp3d_gbn_workspace_bytes": "l: ii",
+    "sp3d_gbn_forward": "i: pp i pp i l iii pppp dd i ppppppp",
+    "sp3d_gbn_backward": "i: ppp i pp i l ii ppppp i ppppppp",
+}
+TUNING_SIGNATURES = {                           # selfpose3d_amd/csrc/sp3d_tuning.h: measurement builds only, declared when present
+    "sp3d_unproject_fwd_variant": "i: p i ppppp iiiiiiii p iii p",
+    "sp3d_debug_set_timeline": "i: p",
+    "sp3d_debug_stamp": "i: pp",
+}
+EXPORTS = list(SIGNATURES)
 
 _lib = None
 
@@ -82,61 +141,13 @@ def load():
             f"{LIB_PATH} not found - the HIP extension is not built. Run `python -m selfpose3d_amd.build` "
             "(hipcc, gfx950). There is no CPU fallback for the unprojection path.")
     lib = C.CDLL(LIB_PATH)
-    P, I, F, V = C.c_void_p, C.c_int, C.c_float, C.c_void_p
-    lib.sp3d_abi_version.restype = I
-    lib.sp3d_error_string.restype = C.c_char_p
-    lib.sp3d_error_string.argtypes = [I]
-    lib.sp3d_pack_heatmaps.restype = I
-    lib.sp3d_pack_heatmaps.argtypes = [P, P, I, I, I, I, I, I, V]
-    lib.sp3d_pack_heatmaps_ex.restype = I
-    lib.sp3d_pack_heatmaps_ex.argtypes = [P, P, I, I, I, I, I, I, I, I, V]
-    lib.sp3d_unproject_fwd.restype = I
-    lib.sp3d_unproject_fwd.argtypes = [P, I, I, P, P, P, P, P, I, I, I, I, I, I, I, I, P, I, I, V]
-    lib.sp3d_unproject_bwd.restype = I
-    lib.sp3d_unproject_bwd.argtypes = [P, P, P, P, P, P, I, I, I, I, I, I, I, I, P, I, I, V]
-    lib.sp3d_nms_topk_workspace_bytes.restype = C.c_int64
-    lib.sp3d_nms_topk_workspace_bytes.argtypes = [I, I, I, I, I]
-    lib.sp3d_nms_topk.restype = I
-    lib.sp3d_nms_topk.argtypes = [P, I, I, I, I, I, P, P, P, P, P, P, V]
-    lib.sp3d_soft_argmax.restype = I
-    lib.sp3d_soft_argmax.argtypes = [P, P, P, I, I, C.c_int64, F, V]
-    lib.sp3d_unproject_fwd_indexed.restype = I
-    lib.sp3d_unproject_fwd_indexed.argtypes = [P, I, I, P, P, P, P, P, P, I, I, I, I, I, I, I, I, P, I, I, V]
-    lib.sp3d_unproject_bwd_indexed.restype = I
-    lib.sp3d_unproject_bwd_indexed.argtypes = [P, P, P, P, P, P, P, I, I, I, I, I, I, I, I, P, I, I, V]
-    lib.sp3d_unproject_fwd_train.restype = I
-    lib.sp3d_unproject_fwd_train.argtypes = [P, I, I, P, P, P, P, P, P, P, I, I, I, I, I, I, I, I, P, I, I, V]
-    lib.sp3d_unproject_bwd_packed.restype = I
-    lib.sp3d_unproject_bwd_packed.argtypes = [P, P, P, P, P, P, P, I, I, I, I, I, I, I, I, I, I, P, I, I, I, V]
-    lib.sp3d_upsample2x_scatter.restype = I
-    lib.sp3d_upsample2x_scatter.argtypes = [P, P, P, P, C.c_int64, I, I, I, I, V]
-    lib.sp3d_render_joints_fwd.restype = I
-    lib.sp3d_render_joints_fwd.argtypes = [P, P, I, I, I, I, I, F, P, V]
-    lib.sp3d_render_joints_bwd.restype = I
-    lib.sp3d_render_joints_bwd.argtypes = [P, P, P, I, I, I, I, I, F, P, V]
-    lib.sp3d_wino_fused.restype = I
-    lib.sp3d_wino_fused.argtypes = [P, P, P, P, P, I, I, I, I, I, I, I, V]
-    lib.sp3d_wino_input.restype = I
-    lib.sp3d_wino_input.argtypes = [P, P, I, I, I, I, I, V]
-    lib.sp3d_wino_output.restype = I
-    lib.sp3d_wino_output.argtypes = [P, P, P, P, I, I, I, I, I, I, V]
-    lib.sp3d_freq_contract_ex.restype = I
-    lib.sp3d_freq_contract_ex.argtypes = [P, P, P, I, I, I] + [C.c_int64] * 5 + [I, I, V]
-    lib.sp3d_freq_contract.restype = I
-    lib.sp3d_freq_contract.argtypes = [P, P, P, I, I, I, C.c_int64, V]
-    lib.sp3d_gaussian_target_3d.restype = I
-    lib.sp3d_gaussian_target_3d.argtypes = [P, I, I, P, P, P, I, I, I, F, P, V]
-    lib.sp3d_render_root_heatmaps.restype = I
-    lib.sp3d_render_root_heatmaps.argtypes = [P, I, I, P, I, I, I, F, P, V]
-    lib.sp3d_soft_argmax_grid.restype = I
-    lib.sp3d_soft_argmax_grid.argtypes = [P, P, P, I, I, I, P, I, I, F, V]
-    lib.sp3d_channel_shift_act.restype = I
-    lib.sp3d_channel_shift_act.argtypes = [P, P, P, I, C.c_int64, I, C.c_int64, I, V]
-    lib.sp3d_unproject_fwd_strided.restype = I
-    lib.sp3d_unproject_fwd_strided.argtypes = [P, I, I, P, P, P, P, P, P, I, I, I, I, I, I, I, I, P, I, I, V]
-    if hasattr(lib, "sp3d_unproject_fwd_variant"):
-        lib.sp3d_unproject_fwd_variant.restype = I
-        lib.sp3d_unproject_fwd_variant.argtypes = [P, I, P, P, P, P, P, I, I, I, I, I, I, I, I, P, I, I, I, V]
+    for table, required in ((SIGNATURES, True), (TUNING_SIGNATURES, False)):
+        for name, sig in table.items():
+            if required or hasattr(lib, name):
+                ret, args = sig.split(":")
+                fn = getattr(lib, name)
+                fn.restype = _CTYPES[ret]
+                fn.argtypes = [_CTYPES[a] for a in args.replace(" ", "")]
     if lib.sp3d_abi_version() != ABI_VERSION:
         raise Sp3dError(f"libsp3d.so ABI {lib.sp3d_abi_version()} != binding ABI {ABI_VERSION}; rebuild")
     _lib = lib
@@ -183,6 +194,27 @@ def _f3(vals):
     return (C.c_float * 3)(float(vals[0]), float(vals[1]), float(vals[2]))
 
 
+def _opt(t: Optional[torch.Tensor]):
+    """device pointer of an optional tensor (None -> NULL)"""
+    return None if t is None else t.data_ptr()
+
+
+def _empty_cl3d(B: int, Cc: int, X: int, Y: int, Z: int, device, dtype=torch.float32) -> torch.Tensor:
+    """uninitialised (B,C,X,Y,Z) result with torch.channels_last_3d strides (memory (B,X,Y,Z,C))"""
+    return torch.empty((B, X, Y, Z, Cc), dtype=dtype, device=device).permute(0, 4, 1, 2, 3)
+
+
+def _require_cl3d_f32(x: torch.Tensor, who: str):
+    if not x.is_contiguous(memory_format=torch.channels_last_3d) or x.dtype != torch.float32:
+        raise Sp3dError(f"{who}: float32 channels_last_3d activations expected")
+
+
+def _as_cl3d(t: torch.Tensor) -> torch.Tensor:
+    """a residual / skip operand as the kernels read it, dense channels_last_3d like the result it is added to; copies
+    only when it is not that already (.contiguous returns its argument otherwise, so one condition covers every case)"""
+    return t if t.is_contiguous(memory_format=torch.channels_last_3d) else t.contiguous(memory_format=torch.channels_last_3d)
+
+
 def pack_heatmaps(hms: Sequence[torch.Tensor], jp: int = 16, out: Optional[torch.Tensor] = None,
                   out_dtype: Optional[torch.dtype] = None) -> torch.Tensor:
     """list[V] of (B,J,h,w) fp32|bf16 contiguous -> (V,B,h,w,jp) channels-last (fp32|bf16), padded channels zero."""
@@ -222,14 +254,13 @@ def unproject_fwd(views: Sequence[torch.Tensor], layout: int, jp: int, cam: torc
         assert tuple(out.shape) == (B, J, X, Y, Z) and out.stride(4) == 1 and out.dtype == out_dtype
         flags = (HM_BF16 if views[0].dtype == torch.bfloat16 else 0) | (OUT_BF16 if out_dtype == torch.bfloat16 else 0)
         st = (C.c_int64 * 4)(*[int(v) for v in out.stride()[:4]])
-        rc = lib.sp3d_unproject_fwd_strided(_ptr_array(views), layout | flags, jp, cam.data_ptr(),
-                                            sample_of.data_ptr() if sample_of is not None else None, centers.data_ptr(),
-                                            valid.data_ptr(), out.data_ptr(), st, B, V, J, h, w, X, Y, Z, _f3(grid_size),
-                                            int(img_size[0]), int(img_size[1]), _stream(dev))
+        rc = lib.sp3d_unproject_fwd_strided(_ptr_array(views), layout | flags, jp, cam.data_ptr(), _opt(sample_of),
+                                            centers.data_ptr(), valid.data_ptr(), out.data_ptr(), st, B, V, J, h, w, X, Y, Z,
+                                            _f3(grid_size), int(img_size[0]), int(img_size[1]), _stream(dev))
         check(rc, "sp3d_unproject_fwd_strided")
         return out, None
     if channels_last:
-        cubes = torch.empty((B, X, Y, Z, J), dtype=out_dtype, device=dev).permute(0, 4, 1, 2, 3)
+        cubes = _empty_cl3d(B, J, X, Y, Z, dev, out_dtype)
     else:
         cubes = torch.empty((B, J, X, Y, Z), dtype=out_dtype, device=dev)
     flags = (OUT_CHANNELS_LAST if channels_last else 0) | (HM_BF16 if views[0].dtype == torch.bfloat16 else 0) | \
@@ -237,24 +268,19 @@ def unproject_fwd(views: Sequence[torch.Tensor], layout: int, jp: int, cam: torc
     grids = torch.empty((B, X * Y * Z, 3), dtype=torch.float32, device=dev) if want_grids else None
     gs = _f3(grid_size)
     if pass_mask is not None:
-        rc = lib.sp3d_unproject_fwd_train(_ptr_array(views), layout | flags, jp, cam.data_ptr(),
-                                          sample_of.data_ptr() if sample_of is not None else None, centers.data_ptr(),
-                                          valid.data_ptr(), cubes.data_ptr(), grids.data_ptr() if want_grids else None,
+        rc = lib.sp3d_unproject_fwd_train(_ptr_array(views), layout | flags, jp, cam.data_ptr(), _opt(sample_of),
+                                          centers.data_ptr(), valid.data_ptr(), cubes.data_ptr(), _opt(grids),
                                           pass_mask.data_ptr(), B, V, J, h, w, X, Y, Z, gs, int(img_size[0]),
                                           int(img_size[1]), _stream(dev))
     elif variant is None:
-        rc = lib.sp3d_unproject_fwd_indexed(_ptr_array(views), layout | flags,
-                                            jp, cam.data_ptr(), sample_of.data_ptr() if sample_of is not None else None,
-                                            centers.data_ptr(), valid.data_ptr(), cubes.data_ptr(),
-                                            grids.data_ptr() if want_grids else None, B, V, J, h, w, X, Y, Z, gs,
-                                            int(img_size[0]), int(img_size[1]), _stream(dev))
+        rc = lib.sp3d_unproject_fwd_indexed(_ptr_array(views), layout | flags, jp, cam.data_ptr(), _opt(sample_of),
+                                            centers.data_ptr(), valid.data_ptr(), cubes.data_ptr(), _opt(grids),
+                                            B, V, J, h, w, X, Y, Z, gs, int(img_size[0]), int(img_size[1]), _stream(dev))
     else:
         assert layout == LAYOUT_NHWC
-        rc = lib.sp3d_unproject_fwd_variant(_ptr_array(views), jp, cam.data_ptr(), centers.data_ptr(),
-                                            valid.data_ptr(), cubes.data_ptr(),
-                                            grids.data_ptr() if want_grids else None, B, V, J, h, w, X, Y, Z, gs,
-                                            int(img_size[0]), int(img_size[1]),
-                                            int(variant) | (0x1000000 if channels_last else 0), _stream(dev))
+        rc = lib.sp3d_unproject_fwd_variant(_ptr_array(views), jp, cam.data_ptr(), centers.data_ptr(), valid.data_ptr(),
+                                            cubes.data_ptr(), _opt(grids), B, V, J, h, w, X, Y, Z, gs, int(img_size[0]),
+                                            int(img_size[1]), int(variant) | (0x1000000 if channels_last else 0), _stream(dev))
     check(rc, "sp3d_unproject_fwd")
     return cubes, grids
 
@@ -272,8 +298,7 @@ def unproject_bwd(hms: Sequence[torch.Tensor], cam, centers, valid, grad_cubes: 
     grad_cubes = grad_cubes[:, :J].float().contiguous()
     grads = torch.zeros((V, B, J, h, w), dtype=torch.float32, device=dev)
     gviews = [grads[c] for c in range(V)]
-    rc = lib.sp3d_unproject_bwd_indexed(_ptr_array(hms), cam.data_ptr(),
-                                        sample_of.data_ptr() if sample_of is not None else None, centers.data_ptr(),
+    rc = lib.sp3d_unproject_bwd_indexed(_ptr_array(hms), cam.data_ptr(), _opt(sample_of), centers.data_ptr(),
                                         valid.data_ptr(), grad_cubes.data_ptr(), _ptr_array(gviews), P, V, J, h, w, X,
                                         Y, Z, _f3(grid_size), int(img_size[0]), int(img_size[1]), _stream(dev))
     check(rc, "sp3d_unproject_bwd")
@@ -284,8 +309,6 @@ def nms_proposals(root_cubes: torch.Tensor, k: int, grid_size, grid_center, thre
     """(B,X,Y,Z) -> grid_centers (B,k,5) = [x,y,z mm, (score > threshold) - 1, score]: NMS, top-k, index -> mm and the
     eval-mode proposal flags in the same two launches (no torch glue kernels)."""
     lib = load()
-    lib.sp3d_nms_proposals.restype = C.c_int
-    lib.sp3d_nms_proposals.argtypes = [C.c_void_p] + [C.c_int] * 5 + [C.c_void_p, C.c_void_p, C.c_float] + [C.c_void_p] * 6
     _require_cuda(root_cubes, "root_cubes")
     rc_ = root_cubes.contiguous().float()
     B, X, Y, Z = rc_.shape
@@ -317,7 +340,7 @@ def nms_topk(root_cubes: torch.Tensor, k: int, grid_size=None, grid_center=None)
     ws = torch.empty((max(int(nbytes), 8),), dtype=torch.uint8, device=dev)
     rc = lib.sp3d_nms_topk(rc_.data_ptr(), B, X, Y, Z, k, _f3(grid_size) if grid_size is not None else None,
                            _f3(grid_center) if grid_center is not None else None, vals.data_ptr(), idx.data_ptr(),
-                           locs.data_ptr() if locs is not None else None, ws.data_ptr(), _stream(dev))
+                           _opt(locs), ws.data_ptr(), _stream(dev))
     check(rc, "sp3d_nms_topk")
     return vals, idx, locs
 
@@ -369,9 +392,6 @@ class _SoftArgmaxGridFn(torch.autograd.Function):
         cc = centers.detach().contiguous().float()
         out = torch.empty((P, J, 3), dtype=torch.float32, device=x.device)
         stats = torch.empty((P, J, 2), dtype=torch.float32, device=x.device)
-        lib.sp3d_soft_argmax_grid_train.restype = C.c_int
-        lib.sp3d_soft_argmax_grid_train.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
-                                                    C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_void_p]
         check(lib.sp3d_soft_argmax_grid_train(xc.data_ptr(), cc.data_ptr(), _f3(grid_size), X, Y, Z, out.data_ptr(),
                                               stats.data_ptr(), P, J, float(beta), _stream(x.device)), "sp3d_soft_argmax_grid_train")
         ctx.save_for_backward(xc, cc, out, stats)
@@ -387,9 +407,6 @@ class _SoftArgmaxGridFn(torch.autograd.Function):
         P, J = int(xc.shape[0]), int(xc.shape[1])
         dx = torch.empty_like(xc)
         gc = g.contiguous().float()
-        lib.sp3d_soft_argmax_grid_bwd.restype = C.c_int
-        lib.sp3d_soft_argmax_grid_bwd.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
-                                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_void_p]
         check(lib.sp3d_soft_argmax_grid_bwd(xc.data_ptr(), cc.data_ptr(), _f3(grid_size), X, Y, Z, out.data_ptr(), stats.data_ptr(),
                                             gc.data_ptr(), dx.data_ptr(), P, J, beta, _stream(xc.device)), "sp3d_soft_argmax_grid_bwd")
         if cl:
@@ -407,8 +424,6 @@ def soft_argmax_grid_autograd(x: torch.Tensor, centers: torch.Tensor, grid_size,
 def fetch_ring(ring: torch.Tensor, dst: torch.Tensor, counter: torch.Tensor):
     """graph-capturable: dst <- ring[counter % R] (ring: PINNED host tensor (R, ...)), counter += 1 (device int32)"""
     lib = load()
-    lib.sp3d_fetch_ring.restype = C.c_int
-    lib.sp3d_fetch_ring.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
     assert ring.is_pinned() and ring.dtype == torch.float32 and dst.is_cuda and counter.is_cuda
     R = int(ring.shape[0])
     n = ring[0].numel()
@@ -420,10 +435,8 @@ def fetch_ring(ring: torch.Tensor, dst: torch.Tensor, counter: torch.Tensor):
 def maxpool2x(x: torch.Tensor) -> torch.Tensor:
     """MaxPool3d(2,2) of a channels_last_3d tensor (B,C,X,Y,Z) -> channels_last_3d (B,C,X/2,Y/2,Z/2)"""
     lib = load()
-    lib.sp3d_maxpool2x_cl.restype = C.c_int
-    lib.sp3d_maxpool2x_cl.argtypes = [C.c_void_p, C.c_void_p] + [C.c_int] * 5 + [C.c_void_p]
     B, Cc, X, Y, Z = (int(v) for v in x.shape)
-    y = torch.empty((B, X // 2, Y // 2, Z // 2, Cc), dtype=torch.float32, device=x.device).permute(0, 4, 1, 2, 3)
+    y = _empty_cl3d(B, Cc, X // 2, Y // 2, Z // 2, x.device)
     check(lib.sp3d_maxpool2x_cl(x.data_ptr(), y.data_ptr(), B, X, Y, Z, Cc, _stream(x.device)), "sp3d_maxpool2x_cl")
     return y
 
@@ -435,8 +448,6 @@ def rfft3d(x: torch.Tensor) -> torch.Tensor:
     _require_cuda(x, "x")
     if not x.is_contiguous() or x.dtype != torch.float32 or x.dim() < 3:
         raise Sp3dError("rfft3d: x must be a dense fp32 tensor with >= 3 dims")
-    lib.sp3d_rfft3d.restype = C.c_int
-    lib.sp3d_rfft3d.argtypes = [C.c_void_p, C.c_void_p] + [C.c_int] * 4 + [C.c_void_p]
     SX, SY, SZ = (int(v) for v in x.shape[-3:])
     batch = int(x.numel() // (SX * SY * SZ))
     out = torch.empty(tuple(x.shape[:-1]) + (SZ // 2 + 1,), dtype=torch.complex64, device=x.device)
@@ -451,8 +462,6 @@ def irfft3d_(spec: torch.Tensor, SZ: int) -> torch.Tensor:
     _require_cuda(spec, "spec")
     if not spec.is_contiguous() or spec.dtype != torch.complex64 or spec.dim() < 3 or spec.shape[-1] != SZ // 2 + 1:
         raise Sp3dError("irfft3d_: spec must be a dense complex64 (..., SX,SY,SZ//2+1) tensor")
-    lib.sp3d_irfft3d.restype = C.c_int
-    lib.sp3d_irfft3d.argtypes = [C.c_void_p, C.c_void_p] + [C.c_int] * 4 + [C.c_void_p]
     SX, SY = (int(v) for v in spec.shape[-3:-1])
     batch = int(spec.numel() // (SX * SY * (SZ // 2 + 1)))
     out = torch.empty(tuple(spec.shape[:-1]) + (int(SZ),), dtype=torch.float32, device=spec.device)
@@ -472,10 +481,6 @@ def cfft2d_(spec: torch.Tensor, inverse: bool, rows_in: Optional[int] = None, ro
     _require_cuda(spec, "spec")
     if not spec.is_contiguous() or spec.dtype != torch.complex64 or spec.dim() < 2:
         raise Sp3dError("cfft2d_: dense complex64 tensor with >= 2 dims expected")
-    lib.sp3d_cfft2d.restype = C.c_int
-    lib.sp3d_cfft2d.argtypes = [C.c_void_p] + [C.c_int] * 4 + [C.c_void_p]
-    lib.sp3d_cfft2d_ex.restype = C.c_int
-    lib.sp3d_cfft2d_ex.argtypes = [C.c_void_p] + [C.c_int] * 6 + [C.c_void_p]
     SX, SY = int(spec.shape[-2]), int(spec.shape[-1])
     batch = int(spec.numel() // (SX * SY))
     if library:
@@ -493,8 +498,6 @@ def zdft_fwd_cl(x: torch.Tensor, cout: int, S) -> torch.Tensor:
     B, Cc, X, Y, Z = (int(v) for v in x.shape)
     if x.dtype != torch.float32 or not x.permute(0, 2, 3, 4, 1).is_contiguous():
         raise Sp3dError("zdft_fwd_cl: dense fp32 channels_last_3d cubes expected")
-    lib.sp3d_zdft_fwd_cl.restype = C.c_int
-    lib.sp3d_zdft_fwd_cl.argtypes = [C.c_void_p] * 2 + [C.c_int] * 9 + [C.c_void_p]
     SX, SY, SZ = (int(v) for v in S)
     spec = torch.empty((B, int(cout), SZ // 2 + 1, SX, SY), dtype=torch.complex64, device=x.device)
     check(lib.sp3d_zdft_fwd_cl(x.data_ptr(), spec.data_ptr(), B, Cc, int(cout), X, Y, Z, SX, SY, SZ, _stream(x.device)),
@@ -516,9 +519,6 @@ def unproject_fwd_zdft(views: Sequence[torch.Tensor], jp: int, cam: torch.Tensor
     if (Z, int(SZ), jp) not in ZDFT_SHAPES or X % 4 or Y % 4:
         raise Sp3dError(f"unproject_fwd_zdft: built for (Z, SZ, channels) in {sorted(ZDFT_SHAPES)} and X, Y multiples of 4")
     spec = torch.empty((batch, J, int(SZ) // 2 + 1, X // 4, Y // 4, 16), dtype=torch.complex64, device=cam.device)
-    lib.sp3d_unproject_fwd_zdft.restype = C.c_int
-    lib.sp3d_unproject_fwd_zdft.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 4 + [C.c_int] * 8 + [C.c_void_p, C.c_int, C.c_int,
-                                                                                                   C.c_int, C.c_void_p]
     check(lib.sp3d_unproject_fwd_zdft(_ptr_array(views), jp, cam.data_ptr(), centers.data_ptr(), valid.data_ptr(),
                                       spec.data_ptr(), batch, len(views), J, h, w, X, Y, Z, _f3(grid_size), int(img_size[0]),
                                       int(img_size[1]), int(SZ), _stream(cam.device)), "sp3d_unproject_fwd_zdft")
@@ -533,8 +533,6 @@ def cfft2d_88_tiled(spec: torch.Tensor, X: int, Y: int) -> torch.Tensor:
         raise Sp3dError("cfft2d_88_tiled: dense complex64 (..., X/4, Y/4, 16) expected")
     out = torch.empty(tuple(spec.shape[:-3]) + (88, 88), dtype=torch.complex64, device=spec.device)
     batch = out.numel() // (88 * 88)
-    lib.sp3d_cfft2d_88_tiled.restype = C.c_int
-    lib.sp3d_cfft2d_88_tiled.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
     check(lib.sp3d_cfft2d_88_tiled(spec.data_ptr(), out.data_ptr(), batch, int(X), int(Y), _stream(spec.device)),
           "sp3d_cfft2d_88_tiled")
     return out
@@ -546,10 +544,8 @@ def zdft_inv_cl(spec: torch.Tensor, X: int, Y: int, Z: int, SZ: int, shift: torc
     _require_cuda(spec, "spec")
     if not spec.is_contiguous() or spec.dtype != torch.complex64 or spec.dim() != 5 or spec.shape[2] != SZ // 2 + 1:
         raise Sp3dError("zdft_inv_cl: dense complex64 (B,O,SZ//2+1,SX,SY) spectrum expected")
-    lib.sp3d_zdft_inv_cl.restype = C.c_int
-    lib.sp3d_zdft_inv_cl.argtypes = [C.c_void_p] * 3 + [C.c_int] * 9 + [C.c_void_p]
     B, O, _, SX, SY = (int(v) for v in spec.shape)
-    y = torch.empty((B, X, Y, Z, O), dtype=torch.float32, device=spec.device).permute(0, 4, 1, 2, 3)
+    y = _empty_cl3d(B, O, X, Y, Z, spec.device)
     check(lib.sp3d_zdft_inv_cl(spec.data_ptr(), y.data_ptr(), shift.data_ptr(), B, O, X, Y, Z, SX, SY, int(SZ),
                                1 if relu else 0, _stream(spec.device)), "sp3d_zdft_inv_cl")
     return y
@@ -559,12 +555,10 @@ def crop_shift_act_cl(src: torch.Tensor, X: int, Y: int, Z: int, shift: torch.Te
     """planar (B,C,SX,SY,SZ) -> channels_last_3d (B,C,X,Y,Z) = act(src[:, :, :X, :Y, :Z] + shift[c]) in one pass"""
     lib = load()
     _require_cuda(src, "src")
-    lib.sp3d_crop_shift_act_cl.restype = C.c_int
-    lib.sp3d_crop_shift_act_cl.argtypes = [C.c_void_p] * 3 + [C.c_int] * 9 + [C.c_void_p]
     if not src.is_contiguous() or src.dtype != torch.float32:
         raise Sp3dError("crop_shift_act_cl: src must be a dense fp32 (B,C,SX,SY,SZ) tensor")
     B, Cc, SX, SY, SZ = (int(v) for v in src.shape)
-    y = torch.empty((B, X, Y, Z, Cc), dtype=torch.float32, device=src.device).permute(0, 4, 1, 2, 3)
+    y = _empty_cl3d(B, Cc, X, Y, Z, src.device)
     check(lib.sp3d_crop_shift_act_cl(src.data_ptr(), y.data_ptr(), shift.data_ptr(), B, Cc, X, Y, Z, SX, SY, SZ,
                                      1 if relu else 0, _stream(src.device)), "sp3d_crop_shift_act_cl")
     return y
@@ -586,8 +580,8 @@ def channel_shift_act_(y: torch.Tensor, shift: torch.Tensor, mode: int, residual
     if residual is not None:
         if residual.shape != y.shape or residual.stride() != y.stride():
             residual = residual.contiguous(memory_format=torch.channels_last_3d if cl else torch.contiguous_format)
-    check(lib.sp3d_channel_shift_act(y.data_ptr(), shift.data_ptr(), residual.data_ptr() if residual is not None else None,
-                                     int(mode), B, Cc, inner, cl, _stream(y.device)), "sp3d_channel_shift_act")
+    check(lib.sp3d_channel_shift_act(y.data_ptr(), shift.data_ptr(), _opt(residual), int(mode), B, Cc, inner, cl,
+                                     _stream(y.device)), "sp3d_channel_shift_act")
     return y
 
 
@@ -606,31 +600,25 @@ def unproject_bwd_packed(cam, centers, valid, grad_cubes: torch.Tensor, pass_mas
     X, Y, Z = (int(c) for c in cube_size)
     gc = grad_cubes[:, :J].float().contiguous()
     if deterministic:
-        I, Pp, V_ = C.c_int, C.c_void_p, C.c_void_p
-        lib.sp3d_unproject_bwd_packed_det.restype = I
-        lib.sp3d_unproject_bwd_packed_det.argtypes = [Pp] * 8 + [I] * 10 + [Pp, I, I, I, V_]
-        lib.sp3d_fixed_to_float.restype = I
-        lib.sp3d_fixed_to_float.argtypes = [Pp, Pp, Pp, C.c_int64, V_]
         # scale = 2^(40 - ceil(log2 max|g|)): computed on the device, no host synchronisation
         gmax = gc.abs().amax().clamp_min(1e-30)
         scale = torch.exp2(40.0 - torch.ceil(torch.log2(gmax))).to(torch.float32).reshape(1)
         fixed = torch.zeros((num_views, batch, h, w, jp), dtype=torch.int64, device=dev)
-        rc = lib.sp3d_unproject_bwd_packed_det(cam.data_ptr(), sample_of.data_ptr() if sample_of is not None else None,
-                                               centers.data_ptr(), valid.data_ptr(), gc.data_ptr(), pass_mask.data_ptr(),
-                                               fixed.data_ptr(), scale.data_ptr(), int(batch), P, num_views, J, jp, h, w,
-                                               X, Y, Z, _f3(grid_size), int(img_size[0]), int(img_size[1]), int(scatter),
-                                               _stream(dev))
+        rc = lib.sp3d_unproject_bwd_packed_det(cam.data_ptr(), _opt(sample_of), centers.data_ptr(), valid.data_ptr(),
+                                               gc.data_ptr(), pass_mask.data_ptr(), fixed.data_ptr(), scale.data_ptr(),
+                                               int(batch), P, num_views, J, jp, h, w, X, Y, Z, _f3(grid_size),
+                                               int(img_size[0]), int(img_size[1]), int(scatter), _stream(dev))
         check(rc, "sp3d_unproject_bwd_packed_det")
         packed = torch.empty((num_views, batch, h, w, jp), dtype=torch.float32, device=dev)
         check(lib.sp3d_fixed_to_float(fixed.data_ptr(), packed.data_ptr(), scale.data_ptr(), fixed.numel(), _stream(dev)),
               "sp3d_fixed_to_float")
-        return packed if return_packed else [packed[c].permute(0, 3, 1, 2)[:, :J] for c in range(num_views)]
-    packed = torch.zeros((num_views, batch, h, w, jp), dtype=torch.float32, device=dev)
-    rc = lib.sp3d_unproject_bwd_packed(cam.data_ptr(), sample_of.data_ptr() if sample_of is not None else None,
-                                       centers.data_ptr(), valid.data_ptr(), gc.data_ptr(), pass_mask.data_ptr(),
-                                       packed.data_ptr(), int(batch), P, num_views, J, jp, h, w, X, Y, Z,
-                                       _f3(grid_size), int(img_size[0]), int(img_size[1]), int(scatter), _stream(dev))
-    check(rc, "sp3d_unproject_bwd_packed")
+    else:
+        packed = torch.zeros((num_views, batch, h, w, jp), dtype=torch.float32, device=dev)
+        rc = lib.sp3d_unproject_bwd_packed(cam.data_ptr(), _opt(sample_of), centers.data_ptr(), valid.data_ptr(),
+                                           gc.data_ptr(), pass_mask.data_ptr(), packed.data_ptr(), int(batch), P, num_views,
+                                           J, jp, h, w, X, Y, Z, _f3(grid_size), int(img_size[0]), int(img_size[1]),
+                                           int(scatter), _stream(dev))
+        check(rc, "sp3d_unproject_bwd_packed")
     return packed if return_packed else [packed[c].permute(0, 3, 1, 2)[:, :J] for c in range(num_views)]
 
 
@@ -690,8 +678,6 @@ def freq_contract_ty(Xf: torch.Tensor, T: torch.Tensor, tw: torch.Tensor) -> tor
             tuple(T.shape) != (KZ * SX, O, Cc, 14) or tuple(tw.shape) != (SY, 3, 2) or not tw.is_contiguous():
         raise Sp3dError("freq_contract_ty: (B,C,KZ,SX,SY) complex64 x (KZ*SX,O,C,14) fp32 table expected")
     Yf = torch.empty((B, O, KZ, SX, SY), dtype=torch.complex64, device=Xf.device)
-    lib.sp3d_freq_contract_ty.restype = C.c_int
-    lib.sp3d_freq_contract_ty.argtypes = [C.c_void_p] * 4 + [C.c_int] * 5 + [C.c_void_p]
     check(lib.sp3d_freq_contract_ty(Xf.data_ptr(), T.data_ptr(), tw.data_ptr(), Yf.data_ptr(), B, Cc, O, rows, SY,
                                     _stream(Xf.device)), "sp3d_freq_contract_ty")
     return Yf
@@ -774,19 +760,14 @@ def conv3_split_(x: torch.Tensor, W3: torch.Tensor, shift: torch.Tensor, mode: i
     lib = load()
     _require_cuda(x, "x")
     B, Cc, X, Y, Z = (int(v) for v in x.shape)
-    if not x.is_contiguous(memory_format=torch.channels_last_3d) or x.dtype != torch.float32:
-        raise Sp3dError("conv3_split_: float32 channels_last_3d activations expected")
+    _require_cl3d_f32(x, "conv3_split_")
     O = int(W3.shape[3])
     dev = x.device
-    y = torch.empty((B, X, Y, Z, O), dtype=torch.float32, device=dev).permute(0, 4, 1, 2, 3)
-    if residual is not None and (tuple(residual.shape) != (B, O, X, Y, Z) or
-                                 not residual.is_contiguous(memory_format=torch.channels_last_3d)):
-        residual = residual.contiguous(memory_format=torch.channels_last_3d)
-    lib.sp3d_conv3_split.restype = C.c_int
-    lib.sp3d_conv3_split.argtypes = [C.c_void_p] * 5 + [C.c_int] * 7 + [C.c_void_p]
-    check(lib.sp3d_conv3_split(x.data_ptr(), W3.data_ptr(), y.data_ptr(), shift.data_ptr(),
-                               residual.data_ptr() if residual is not None else None, int(mode), B, X, Y, Z, Cc, O,
-                               _stream(dev)), "sp3d_conv3_split")
+    y = _empty_cl3d(B, O, X, Y, Z, dev)
+    if residual is not None:
+        residual = _as_cl3d(residual)
+    check(lib.sp3d_conv3_split(x.data_ptr(), W3.data_ptr(), y.data_ptr(), shift.data_ptr(), _opt(residual), int(mode),
+                               B, X, Y, Z, Cc, O, _stream(dev)), "sp3d_conv3_split")
     return y
 
 
@@ -797,18 +778,16 @@ def wino_conv3d_(x: torch.Tensor, U: torch.Tensor, shift: torch.Tensor, mode: in
     lib = load()
     _require_cuda(x, "x")
     B, Cc, X, Y, Z = (int(v) for v in x.shape)
-    if not x.is_contiguous(memory_format=torch.channels_last_3d) or x.dtype != torch.float32:
-        raise Sp3dError("wino_conv3d_: float32 channels_last_3d activations expected")
+    _require_cl3d_f32(x, "wino_conv3d_")
     O = int(U.shape[2])
     T = B * ((X + 1) // 2) * ((Y + 1) // 2) * ((Z + 1) // 2)
     V = torch.empty((64, T, Cc), dtype=torch.float32, device=x.device)
     check(lib.sp3d_wino_input(x.data_ptr(), V.data_ptr(), B, X, Y, Z, Cc, _stream(x.device)), "sp3d_wino_input")
     M = torch.bmm(V, U)         # the 64 products: the library's fp32 batched GEMM (an own split-bf16 GEMM was not faster: round 3)
-    y = torch.empty((B, X, Y, Z, O), dtype=torch.float32, device=x.device).permute(0, 4, 1, 2, 3)
-    if residual is not None and (residual.shape != y.shape or residual.stride() != y.stride()):
-        residual = residual.contiguous(memory_format=torch.channels_last_3d)
-    check(lib.sp3d_wino_output(M.data_ptr(), y.data_ptr(), shift.data_ptr(),
-                               residual.data_ptr() if residual is not None else None, int(mode), B, X, Y, Z, O,
+    y = _empty_cl3d(B, O, X, Y, Z, x.device)
+    if residual is not None:
+        residual = _as_cl3d(residual)
+    check(lib.sp3d_wino_output(M.data_ptr(), y.data_ptr(), shift.data_ptr(), _opt(residual), int(mode), B, X, Y, Z, O,
                                _stream(x.device)), "sp3d_wino_output")
     return y
 
@@ -821,29 +800,17 @@ def wino_fused_conv3d_(x: torch.Tensor, U: torch.Tensor, shift: torch.Tensor, mo
     lib = load()
     _require_cuda(x, "x")
     B, Cc, X, Y, Z = (int(v) for v in x.shape)
-    if not x.is_contiguous(memory_format=torch.channels_last_3d) or x.dtype != torch.float32:
-        raise Sp3dError("wino_fused_conv3d_: float32 channels_last_3d activations expected")
+    _require_cl3d_f32(x, "wino_fused_conv3d_")
     O = int(U.shape[2])
-    y = torch.empty((B, X, Y, Z, O), dtype=torch.float32, device=x.device).permute(0, 4, 1, 2, 3)
-    if residual is not None and (residual.shape != y.shape or residual.stride() != y.stride()):
-        residual = residual.contiguous(memory_format=torch.channels_last_3d)
-    if U3 is not None and O == 64:
-        lib.sp3d_wino_fused_split64.restype = C.c_int
-        lib.sp3d_wino_fused_split64.argtypes = [C.c_void_p] * 5 + [C.c_int] * 7 + [C.c_void_p]
-        check(lib.sp3d_wino_fused_split64(x.data_ptr(), U3.data_ptr(), y.data_ptr(), shift.data_ptr(),
-                                          residual.data_ptr() if residual is not None else None, int(mode), B, X, Y, Z, Cc, O,
-                                          _stream(x.device)), "sp3d_wino_fused_split64")
-        return y
-    if U3 is not None:
-        lib.sp3d_wino_fused_split.restype = C.c_int
-        lib.sp3d_wino_fused_split.argtypes = [C.c_void_p] * 5 + [C.c_int] * 7 + [C.c_void_p]
-        check(lib.sp3d_wino_fused_split(x.data_ptr(), U3.data_ptr(), y.data_ptr(), shift.data_ptr(),
-                                        residual.data_ptr() if residual is not None else None, int(mode), B, X, Y, Z, Cc, O,
-                                        _stream(x.device)), "sp3d_wino_fused_split")
-        return y
-    check(lib.sp3d_wino_fused(x.data_ptr(), U.data_ptr(), y.data_ptr(), shift.data_ptr(),
-                              residual.data_ptr() if residual is not None else None, int(mode), B, X, Y, Z, Cc, O,
-                              _stream(x.device)), "sp3d_wino_fused")
+    y = _empty_cl3d(B, O, X, Y, Z, x.device)
+    if residual is not None:
+        residual = _as_cl3d(residual)
+    if U3 is None:
+        name, weights = "sp3d_wino_fused", U
+    else:
+        name, weights = ("sp3d_wino_fused_split64" if O == 64 else "sp3d_wino_fused_split"), U3
+    check(getattr(lib, name)(x.data_ptr(), weights.data_ptr(), y.data_ptr(), shift.data_ptr(), _opt(residual), int(mode),
+                             B, X, Y, Z, Cc, O, _stream(x.device)), name)
     return y
 
 
@@ -853,13 +820,11 @@ def upsample2x_(x: torch.Tensor, w_gemm: torch.Tensor, shift: torch.Tensor, skip
     lib = load()
     _require_cuda(x, "x")
     B, Cc, X, Y, Z = (int(v) for v in x.shape)
-    if not x.is_contiguous(memory_format=torch.channels_last_3d) or x.dtype != torch.float32:
-        raise Sp3dError("upsample2x_: float32 channels_last_3d activations expected")
+    _require_cl3d_f32(x, "upsample2x_")
     O = int(w_gemm.shape[1]) // 8
     G = torch.matmul(x.permute(0, 2, 3, 4, 1).reshape(-1, Cc), w_gemm)
-    out = torch.empty((B, 2 * X, 2 * Y, 2 * Z, O), dtype=torch.float32, device=x.device).permute(0, 4, 1, 2, 3)
-    if skip.shape != out.shape or skip.stride() != out.stride():
-        skip = skip.contiguous(memory_format=torch.channels_last_3d)
+    out = _empty_cl3d(B, O, 2 * X, 2 * Y, 2 * Z, x.device)
+    skip = _as_cl3d(skip)
     check(lib.sp3d_upsample2x_scatter(G.data_ptr(), out.data_ptr(), shift.data_ptr(), skip.data_ptr(), B, X, Y, Z, O,
                                       _stream(x.device)), "sp3d_upsample2x_scatter")
     return out
@@ -871,22 +836,18 @@ def upsample2x_head_(x: torch.Tensor, w_gemm: torch.Tensor, shift: torch.Tensor,
     of a (B,2X,2Y,2Z,J) tensor (for J = 1 that is also the dense NCDHW tensor)"""
     lib = load()
     _require_cuda(x, "x")
-    lib.sp3d_upsample2x_scatter_head.restype = C.c_int
-    lib.sp3d_upsample2x_scatter_head.argtypes = [C.c_void_p] * 6 + [C.c_int64] + [C.c_int] * 5 + [C.c_void_p]
     B, Cc, X, Y, Z = (int(v) for v in x.shape)
-    if not x.is_contiguous(memory_format=torch.channels_last_3d) or x.dtype != torch.float32:
-        raise Sp3dError("upsample2x_head_: float32 channels_last_3d activations expected")
+    _require_cl3d_f32(x, "upsample2x_head_")
     O = int(w_gemm.shape[1]) // 8
     J = int(w_out.shape[0])
     G = torch.matmul(x.permute(0, 2, 3, 4, 1).reshape(-1, Cc), w_gemm)
-    if tuple(skip.shape) != (B, O, 2 * X, 2 * Y, 2 * Z) or not skip.is_contiguous(memory_format=torch.channels_last_3d):
-        skip = skip.contiguous(memory_format=torch.channels_last_3d)
+    skip = _as_cl3d(skip)
     wo = w_out.reshape(J, O).contiguous().float()
     bo = (b_out if b_out is not None else torch.zeros(J, device=x.device)).contiguous().float()
-    head = torch.empty((B, 2 * X, 2 * Y, 2 * Z, J), dtype=torch.float32, device=x.device)
+    head = _empty_cl3d(B, J, 2 * X, 2 * Y, 2 * Z, x.device)
     check(lib.sp3d_upsample2x_scatter_head(G.data_ptr(), head.data_ptr(), shift.data_ptr(), skip.data_ptr(), wo.data_ptr(),
                                            bo.data_ptr(), B, X, Y, Z, O, J, _stream(x.device)), "sp3d_upsample2x_scatter_head")
-    return head.permute(0, 4, 1, 2, 3)
+    return head
 
 
 class _RenderJoints(torch.autograd.Function):
@@ -898,8 +859,8 @@ class _RenderJoints(torch.autograd.Function):
         k = kps.contiguous().float()
         cnt = None if count is None else count.to(device=kps.device, dtype=torch.int32).contiguous()
         out = torch.empty((N, J, h, w), dtype=torch.float32, device=kps.device)
-        check(lib.sp3d_render_joints_fwd(k.data_ptr(), cnt.data_ptr() if cnt is not None else None, N, Pn, J, h, w,
-                                         float(sigma), out.data_ptr(), _stream(kps.device)), "sp3d_render_joints_fwd")
+        check(lib.sp3d_render_joints_fwd(k.data_ptr(), _opt(cnt), N, Pn, J, h, w, float(sigma), out.data_ptr(),
+                                         _stream(kps.device)), "sp3d_render_joints_fwd")
         ctx.save_for_backward(k, cnt if cnt is not None else torch.empty(0, device=kps.device))
         ctx.geom = (h, w, float(sigma), cnt is not None, kps.dtype)
         return out if kps.dtype == torch.float32 else out.to(kps.dtype)      # float64 callers: fp32 kernel, caller's type

@@ -57,10 +57,7 @@ class GraphedRootNet:
             if time_unprojection:
                 # three one-thread kernels that write the chip-wide 100 MHz clock: before and after get_voxel, and a third
                 # right behind the second (stamp-to-stamp distance with nothing in between = what the marker nodes cost)
-                import ctypes as C
                 lib = _lib.load()
-                lib.sp3d_debug_stamp.restype = C.c_int
-                lib.sp3d_debug_stamp.argtypes = [C.c_void_p, C.c_void_p]
                 self._stamps = torch.zeros(3, dtype=torch.int64, device=dev)
                 def stamp(i):
                     _lib.check(lib.sp3d_debug_stamp(self._stamps[i:].data_ptr(), _lib._stream(dev)), "sp3d_debug_stamp")

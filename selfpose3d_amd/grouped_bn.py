@@ -14,7 +14,6 @@ There is no CPU path: tensors must be on the GPU and libsp3d.so built, otherwise
 from __future__ import annotations
 
 import contextlib
-import ctypes as C
 from typing import Optional, Sequence
 
 import torch
@@ -116,11 +115,11 @@ class _GroupedBNFn(torch.autograd.Function):
         if (running_mean is not None) != (rm is not None):
             raise _lib.Sp3dError("grouped BatchNorm: running statistics must have the input's dtype")
         ws = spec.workspace(C_, dev)
-        p = lambda t: None if t is None else C.c_void_p(t.data_ptr())
-        rc = lib.sp3d_gbn_forward(p(x), p(y), _DT[x.dtype], p(spec.group_of), p(spec.group_samples), N, C.c_int64(S), C_,
-                                  spec.G, spec.n_update, p(w), p(b), p(rm), p(rv), C.c_double(eps), C.c_double(momentum),
+        p = _lib._opt
+        rc = lib.sp3d_gbn_forward(p(x), p(y), _DT[x.dtype], p(spec.group_of), p(spec.group_samples), N, S, C_,
+                                  spec.G, spec.n_update, p(w), p(b), p(rm), p(rv), eps, momentum,
                                   mode, p(residual), p(stats[0]), p(stats[1]), p(stats[2]), p(stats[3]), p(ws),
-                                  C.c_void_p(_lib._stream(dev)))
+                                  _lib._stream(dev))
         _lib.check(rc, "sp3d_gbn_forward")
         if mode == 2:
             ctx.save_for_backward(x, w, stats, y)                 # the block's output is what the next layer keeps anyway
@@ -145,26 +144,13 @@ class _GroupedBNFn(torch.autograd.Function):
         gb = torch.empty(C_, dtype=x.dtype, device=dev)
         k123 = torch.empty((3, spec.G, C_), dtype=x.dtype, device=dev)
         ws = spec.workspace(C_, dev)
-        p = lambda t: None if t is None else C.c_void_p(t.data_ptr())
-        rc = lib.sp3d_gbn_backward(p(x), p(dy), p(dx), _DT[x.dtype], p(spec.group_of), p(spec.group_samples), N, C.c_int64(S),
+        p = _lib._opt
+        rc = lib.sp3d_gbn_backward(p(x), p(dy), p(dx), _DT[x.dtype], p(spec.group_of), p(spec.group_samples), N, S,
                                    C_, spec.G, p(w), p(stats[0]), p(stats[1]), p(stats[2]), p(stats[3]), ctx.mode, p(yout),
-                                   p(dres), p(gw), p(gb), p(k123), p(ws), C.c_void_p(_lib._stream(dev)))
+                                   p(dres), p(gw), p(gb), p(k123), p(ws), _lib._stream(dev))
         _lib.check(rc, "sp3d_gbn_backward")
         return (dx, (gw if ctx.has_affine[0] else None), (gb if ctx.has_affine[1] else None), None, None, None, None, None, None,
                 dres)
-
-
-def _declare(lib):
-    if getattr(lib, "_gbn_declared", False):
-        return
-    I, P, L, D = C.c_int, C.c_void_p, C.c_int64, C.c_double
-    lib.sp3d_gbn_workspace_bytes.restype = L
-    lib.sp3d_gbn_workspace_bytes.argtypes = [I, I]
-    lib.sp3d_gbn_forward.restype = I
-    lib.sp3d_gbn_forward.argtypes = [P, P, I, P, P, I, L, I, I, I, P, P, P, P, D, D, I, P, P, P, P, P, P, P]
-    lib.sp3d_gbn_backward.restype = I
-    lib.sp3d_gbn_backward.argtypes = [P, P, P, I, P, P, I, L, I, I, P, P, P, P, P, I, P, P, P, P, P, P, P]
-    lib._gbn_declared = True
 
 
 class _GroupedMixin:
@@ -183,7 +169,6 @@ class _GroupedMixin:
             return torch.relu_(y) if relu else y
         if self.momentum is None or not self.track_running_stats:
             raise ValueError("grouped BatchNorm needs a numeric momentum and running statistics (as the reference's layers)")
-        _declare(_lib.load())
         y = _GroupedBNFn.apply(x, self.weight, self.bias, self.running_mean, self.running_var, spec, float(self.eps),
                                float(self.momentum), bool(relu), residual)
         with torch.no_grad():

@@ -97,20 +97,14 @@ def test_cabi_jp32_limits_validated_before_any_launch(lib):
     assert f(views, 1, 32, d, d, d, d, None, 1, 2, 17, 1, 8, 4, 4, 4, gs, 96, 72, None) == -4
     # the fused z-spectrum entry: Jp = 16 only
     z = lib.sp3d_unproject_fwd_zdft
-    z.restype = C.c_int
-    z.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 4 + [C.c_int] * 8 + [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
     spec = C.c_void_p(0x10000)
     assert z(views, 32, d, d, d, spec, 1, 2, 17, 8, 8, 4, 4, 20, gs, 96, 72, 28, None) == -4
     # the pass-mask (training) forward and both packed backward entries: at most 16 channels
     t = lib.sp3d_unproject_fwd_train
-    t.restype = C.c_int
-    t.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 7 + [C.c_int] * 8 + [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
     assert t(views, 1, 32, d, None, d, d, d, None, d, 1, 2, 17, 8, 8, 4, 4, 4, gs, 96, 72, None) == -4
     for name in ("sp3d_unproject_bwd_packed", "sp3d_unproject_bwd_packed_det"):
         b = getattr(lib, name)
-        b.restype = C.c_int
         det = name.endswith("_det")
-        b.argtypes = [C.c_void_p] * (8 if det else 7) + [C.c_int] * 10 + [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
         args = [d, None, d, d, d, d, d] + ([d] if det else []) + [1, 1, 2, 17, 32, 8, 8, 4, 4, 4, gs, 96, 72, 0, None]
         assert b(*args) == -4, name
     # the re-tiling pass: Jp in 4/8/12/16/32, J <= Jp

@@ -24,6 +24,89 @@ def lib():
     return _lib.load()
 
 
+_C_SCALARS = {"int": C.c_int, "int32_t": C.c_int, "int64_t": C.c_int64, "float": C.c_float, "double": C.c_double}
+
+
+def _header_signatures(path):
+    """{name: (restype, [argtypes])} of every `<ret> sp3d_name(<args>);` prototype of a header, by the binding's type rule: a
+    parameter declared with * or [] is c_void_p, int / int32_t c_int, int64_t c_int64, float c_float, double c_double;
+    return type `const char *` is c_char_p; (void) is no arguments.  Any other type is an error (KeyError), not a guess."""
+    src = re.sub(r"//[^\n]*", "", re.sub(r"/\*.*?\*/", "", open(path).read(), flags=re.S))
+
+    def scalar(decl, is_return=False):
+        words = [w for w in decl.split() if w != "const"]
+        assert len(words) == (1 if is_return else 2), decl              # <type> [<name>]
+        return _C_SCALARS[words[0]]
+
+    sigs = {}
+    for ret, name, args in re.findall(r"([A-Za-z_][\w \t]*?[\s*]+)(sp3d_\w+)\s*\(([^()]*)\)\s*;", src):
+        assert name not in sigs, name
+        restype = C.c_char_p if ret.split() == ["const", "char", "*"] else scalar(ret, True)
+        params = [] if args.strip() == "void" else [a.strip() for a in args.split(",")]
+        sigs[name] = (restype, [C.c_void_p if ("*" in a or "[" in a) else scalar(a) for a in params])
+    # the pattern saw every function the header names (a prototype it cannot read must not drop out silently)
+    assert sorted(sigs) == sorted(set(re.findall(r"\b(sp3d_[a-z0-9_]+)\s*\(", src))), path
+    return sigs
+
+
+def _table_signatures(table):
+    """the same form from one of the binding's tables, decoded the way _lib.load() does"""
+    out = {}
+    for name, sig in table.items():
+        ret, args = sig.split(":")
+        out[name] = (_lib._CTYPES[ret], [_lib._CTYPES[a] for a in args.replace(" ", "")])
+    return out
+
+
+def test_signature_tables_match_the_headers():
+    """every prototype of include/sp3d.h (and of csrc/sp3d_tuning.h for the measurement entries) against the binding's table,
+    both directions, argument by argument: no library and no GPU needed.  One argument added, dropped or of another width
+    on either side fails here - before a pointer can land in the wrong slot of a launch."""
+    for header, table in ((os.path.join(ROOT, "include", "sp3d.h"), _lib.SIGNATURES),
+                          (os.path.join(ROOT, "selfpose3d_amd", "csrc", "sp3d_tuning.h"), _lib.TUNING_SIGNATURES)):
+        declared, bound = _header_signatures(header), _table_signatures(table)
+        assert sorted(bound) == sorted(declared), sorted(set(bound) ^ set(declared))
+        for name in declared:
+            assert bound[name] == declared[name], (name, table[name])
+    assert len(_lib.SIGNATURES) == 51 and _lib.EXPORTS == list(_lib.SIGNATURES)
+    assert not set(_lib.SIGNATURES) & set(_lib.TUNING_SIGNATURES)
+    # the rule itself, on prototypes written here (a parser that returned nothing would pass the loop above vacuously)
+    assert _lib.SIGNATURES["sp3d_abi_version"] == "i:" and _table_signatures({"f": "l: p i l f d"})["f"] == \
+        (C.c_int64, [C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_double])
+    assert _table_signatures(_lib.SIGNATURES)["sp3d_error_string"] == (C.c_char_p, [C.c_int])
+    assert _table_signatures(_lib.SIGNATURES)["sp3d_gbn_workspace_bytes"] == (C.c_int64, [C.c_int, C.c_int])
+
+
+def test_declarations_live_in_load_only():
+    """no module of the package assigns .argtypes / .restype (or setattr()s them) outside _lib.load(): a wrapper that
+    declares its own signature is a second copy that the header check above cannot see"""
+    import ast
+    import glob
+    stray, in_load = [], 0
+    for path in sorted(glob.glob(os.path.join(ROOT, "selfpose3d_amd", "*.py"))):
+        tree = ast.parse(open(path).read())
+        allowed = set()
+        if os.path.basename(path) == "_lib.py":
+            load = [n for n in tree.body if isinstance(n, ast.FunctionDef) and n.name == "load"]
+            assert len(load) == 1
+            allowed = {id(n) for n in ast.walk(load[0])}
+        for node in ast.walk(tree):
+            if isinstance(node, (ast.Assign, ast.AugAssign, ast.AnnAssign)):
+                targets = node.targets if isinstance(node, ast.Assign) else [node.target]
+                hit = any(isinstance(t, ast.Attribute) and t.attr in ("argtypes", "restype")
+                          for tt in targets for t in ast.walk(tt))
+            elif isinstance(node, ast.Call) and isinstance(node.func, ast.Name) and node.func.id == "setattr":
+                hit = any(isinstance(a, ast.Constant) and a.value in ("argtypes", "restype") for a in node.args)
+            else:
+                hit = False
+            if hit and id(node) in allowed:
+                in_load += 1
+            elif hit:
+                stray.append("%s:%d" % (os.path.relpath(path, ROOT), node.lineno))
+    assert not stray, stray
+    assert in_load == 2              # the walk does see such assignments: the two of load()'s loop
+
+
 def test_every_declared_symbol_is_exported(lib):
     hdr = open(os.path.join(ROOT, "include", "sp3d.h")).read()
     hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
@@ -32,6 +115,11 @@ def test_every_declared_symbol_is_exported(lib):
     assert sorted(_lib.EXPORTS) == declared
     for name in declared:
         assert hasattr(lib, name), name
+    # ... and load() declared each of them as the table says (a (void) entry: an empty argument list, never None)
+    for name, (restype, argtypes) in _table_signatures(_lib.SIGNATURES).items():
+        fn = getattr(lib, name)
+        assert fn.restype is restype, name
+        assert fn.argtypes is not None and len(fn.argtypes) == len(argtypes) and list(fn.argtypes) == argtypes, name
     assert lib.sp3d_abi_version() == 3               # 2: camera records of 64 floats (derived second half); 3: per-call `scatter` argument of the packed backward
     # header constants match the python binding
     for macro, val in (("SP3D_CAM_STRIDE", CAM_STRIDE), ("SP3D_CAM_A", CAM_A), ("SP3D_CAM_W0", CAM_W0),
@@ -63,8 +151,6 @@ def test_library_keeps_no_selector_state(lib):
     gs = (C.c_float * 3)(2000, 2000, 2000)
     d = C.c_void_p(0x1000)
     f = lib.sp3d_unproject_bwd_packed
-    f.restype = C.c_int
-    f.argtypes = [C.c_void_p] * 7 + [C.c_int] * 10 + [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
     assert f(d, None, d, d, d, d, d, 1, 1, 2, 15, 16, 8, 8, 4, 4, 4, gs, 96, 72, 1, None) == -1        # scatter = 1: EINVAL
     assert f(d, None, d, d, d, d, None, 1, 1, 2, 15, 16, 8, 8, 4, 4, 4, gs, 96, 72, _lib.SCATTER_MERGE, None) == -2
 

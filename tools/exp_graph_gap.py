@@ -2,7 +2,7 @@
 """How much of the headline step is NOT inside its graph?  The step's graph with a clock-stamp kernel as its first and its
 last node (chip-wide 100 MHz counter): (last - first) of a replay vs the distance of consecutive replays' first stamps.
     python tools/exp_graph_gap.py > gpurun_out/r06_graph_gap.json"""
-import ctypes as C, json, os, sys, time
+import json, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__))); sys.path.insert(0, ROOT)
 import numpy as np, torch
 import bench
@@ -12,8 +12,6 @@ from selfpose3d_amd.camera_pack import pack_cameras
 dev = torch.device("cuda:0")
 cfg, meta, hms, model, golden = bench.build_workload(4, 0, dev)
 lib = _lib.load()
-lib.sp3d_debug_stamp.restype = C.c_int
-lib.sp3d_debug_stamp.argtypes = [C.c_void_p, C.c_void_p]
 with torch.no_grad():
     for _ in range(3):
         model(hms, meta)

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Per-wave s_memtime timeline of the pipelined unprojection kernel (measurement only)."""
-import ctypes, os, sys, json
+import os, sys, json
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__))); sys.path.insert(0, ROOT)
 import numpy as np, torch
 from selfpose3d_amd import _lib, synthetic as syn
@@ -30,7 +30,6 @@ for _ in range(5): run()
 nblk = 8 * 4096
 S = 32
 buf = torch.zeros(nblk * S, dtype=torch.int64, device=dev)
-lib.sp3d_debug_set_timeline.argtypes = [ctypes.c_void_p]
 assert lib.sp3d_debug_set_timeline(buf.data_ptr()) == 0
 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
 e0.record(); run(); e1.record(); torch.cuda.synchronize()
