@@ -183,9 +183,11 @@ int sp3d_unproject_bwd_indexed(const float *const *hm_views, const float *cam, c
 
 /*
  * Training pair with a line-coalesced scatter.  sp3d_unproject_fwd_train = sp3d_unproject_fwd_indexed
- * (NHWC fp32 input) that also writes pass_mask (P, X*Y*Z) uint16: bit j set where channel j's pre-clamp
+ * (NHWC fp32 input) that also writes pass_mask (P, X*Y*Z) uint16: bit j < J set where channel j's pre-clamp
  * value is inside [0,1] and the voxel is not NaN-zeroed - exactly where torch's clamp / index_put_
- * backward let the gradient through (project_layer.py:97-99).  sp3d_unproject_bwd_packed then needs no
+ * backward let the gradient through (project_layer.py:97-99).  A voxel that no view sees has a pre-clamp value
+ * of 0: its bits are set (and reach no gradient).  Bits J..15 (the pad channels of Jp > J) are zero, and so
+ * are the words of a cube that `valid` skips.  sp3d_unproject_bwd_packed then needs no
  * heat-maps: it accumulates into grad_packed (V,B,h,w,Jp) fp32 channels-last, ZERO-FILLED by the caller,
  * so that one atomic instruction covers whole 64-byte pixels (15x the L2 atomic rate of planar scatter).
  */

@@ -40,8 +40,9 @@ struct Geom {
     int sJ, sX, sY;
     int dense;                    // 1: the strides are the dense ones (flat voxel index == offset)
     int vec4;                     // 1: rows are 4-element aligned, 16-byte result pieces are allowed
-    uint16_t *pass_mask;          // optional (P,N): bit j set iff 0 <= pre-clamp value of channel j <= 1 and the
-                                  // voxel is not NaN-zeroed (where torch's clamp / index_put_ let gradient through)
+    uint16_t *pass_mask;          // optional (P,N): bit j < J set iff 0 <= pre-clamp value of channel j <= 1 and the
+                                  // voxel is not NaN-zeroed (where torch's clamp / index_put_ let gradient through);
+                                  // bits J..15 zero
     // blockIdx -> (sample, tile) without run-time integer divisions (set_xcd_fields; round 3: the ~10 division sequences
     // of the old prologue were ~250 of a brick wave's ~1 350 instructions, and these kernels are instruction-issue bound)
     int xm_mode;                  // 0: B <= 8 and 8 % B == 0 (XCD groups per sample), 1: B % 8 == 0, 2: plain interleave

@@ -585,6 +585,7 @@ __device__ __forceinline__ void pipe_tile(const Views &hm, const float *__restri
     // per voxel (P1 mapping, once): den = #views seeing it + 1e-6, rden = RN(1/den), 0 for a NaN sample position
     const float den_l = (float)(mymask & 0x7fffffffu) + 1e-6f;
     const float rden_l = (mymask & 0x80000000u) ? 0.0f : 1.0f / den_l;
+    const uint32_t jbits = (1u << g.J) - 1u;    // pass-mask bits of the J real channels (the zero pad channels have pre = 0)
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         const float den = __shfl(den_l, 16 * i + g16);
@@ -602,7 +603,7 @@ __device__ __forceinline__ void pipe_tile(const Views &hm, const float *__restri
             bits |= (uint32_t)__shfl_xor((int)bits, 1);
             bits |= (uint32_t)__shfl_xor((int)bits, 2);
             const int nn = 16 * i + g16;
-            if (q == 0 && nn < nvox) g.pass_mask[(size_t)b * g.N + n0 + nn] = (uint16_t)bits;
+            if (q == 0 && nn < nvox) g.pass_mask[(size_t)b * g.N + n0 + nn] = (uint16_t)(bits & jbits);
         }
         if (OUTCL) {
             // channels-last result (B, N, J): this lane's 4 channels are 16 contiguous bytes, the
@@ -804,6 +805,7 @@ __global__ __launch_bounds__(512, ZD ? SP3D_ZD_MINW : SP3D_BRICK_MINW) void unpr
 #endif
         const float den_l = (float)(mymask & 0x7fffffffu) + 1e-6f;
         const float rden_l = (mymask & 0x80000000u) ? 0.0f : 1.0f / den_l;
+        const uint32_t jbits = (1u << g.J) - 1u;    // pass-mask bits of the J real channels
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const float den = __shfl(den_l, 16 * i + g16);
@@ -821,7 +823,7 @@ __global__ __launch_bounds__(512, ZD ? SP3D_ZD_MINW : SP3D_BRICK_MINW) void unpr
                 if (!qact) bits = 0;
                 bits |= (uint32_t)__shfl_xor((int)bits, 1);
                 bits |= (uint32_t)__shfl_xor((int)bits, 2);
-                if (q == 0 && vin) g.pass_mask[(size_t)b * g.N + gn] = (uint16_t)bits;
+                if (q == 0 && vin) g.pass_mask[(size_t)b * g.N + gn] = (uint16_t)(bits & jbits);
             }
             if (OUTCL) {
                 if (qact && 4 * q < g.J && vin) {
@@ -1043,6 +1045,7 @@ __global__ __launch_bounds__(512, SP3D_BRICK_MINW) void unproject_brick_h_kernel
         __builtin_amdgcn_wave_barrier();
         const float den_l = (float)(mymask & 0x7fffffffu) + 1e-6f;
         const float rden_l = (mymask & 0x80000000u) ? 0.0f : 1.0f / den_l;
+        const uint32_t jbits = (1u << g.J) - 1u;    // pass-mask bits of the J real channels
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
             const int v = 32 * i + g32;                             // this slot's voxel inside the brick
@@ -1063,7 +1066,7 @@ __global__ __launch_bounds__(512, SP3D_BRICK_MINW) void unproject_brick_h_kernel
                     if (!bad && pre >= 0.0f && pre <= 1.0f) bits |= 1u << (8 * q + k);
                 }
                 bits |= (uint32_t)__shfl_xor((int)bits, 1);
-                if (q == 0 && vin) g.pass_mask[(size_t)b * g.N + gn] = (uint16_t)bits;
+                if (q == 0 && vin) g.pass_mask[(size_t)b * g.N + gn] = (uint16_t)(bits & jbits);
             }
             if (OUTCL) {
                 if (vin) {
