@@ -10,6 +10,8 @@ hand-written HIP work of this repo is the unprojection feeding it.
 """
 from __future__ import annotations
 
+from typing import NamedTuple, Optional
+
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
@@ -43,6 +45,62 @@ def fft_len(n: int) -> int:
         m += 2
 
 
+def is_cl(t) -> bool:
+    """channels-last (and not also plain-contiguous, as a 1x1x1 weight or a one-channel tensor is in both formats)"""
+    return t.is_contiguous(memory_format=torch.channels_last_3d) and not t.is_contiguous()
+
+
+def pad_cin(x, w):
+    """(x, w) of a conv with the input-channel count rounded up to a multiple of 4, or to what x already carries (zero
+    input channels x zero weight slices: same math); see PadCinConv3d"""
+    cin, have = w.shape[1], x.shape[1]
+    target = have if have > cin else ((cin + 3) // 4 * 4 if cin >= 3 else cin)
+    if target != cin:
+        w = F.pad(w, (0, 0, 0, 0, 0, 0, 0, target - cin))
+    if have < target:
+        x = F.pad(x, (0, 0, 0, 0, 0, 0, 0, target - have))
+    return x, w
+
+
+def conv3_route(cin, cout, shape, winograd=True, wino_split=True, direct_conv=True) -> str:
+    """Which kernel a 3x3x3 layer (cin -> cout) of the plan takes on a channels-last input of ``shape`` = (B, X, Y, Z)
+    with its weights on the GPU: the name of the _lib entry point, or "library" (the library's conv + channel_shift_act_).
+    Wide layers on small grids (the 1/4- and 1/2-resolution blocks: a GEMM with few rows, where MIOpen's implicit-GEMM
+    kernels drop to ~60 TFLOP/s) go through Winograd F(2x2x2,3x3x3): HIP input/output transforms around one batched
+    rocBLAS GEMM, 2.1x faster at (4,128,20,20,5) and 1.2x at (4,64,40,40,10) (tools/exp_wino.py); the rule keeps the
+    transformed tensor (64*T*C floats) within reach of the Infinity Cache, beyond which the transforms eat the gain."""
+    B, X, Y, Z = shape
+    full = cout == 32 and cin in (16, 32)                  # the full-resolution layers
+    if not winograd or not (cin >= 64 or full or (cout == 64 and cin == 32)):
+        return "library"
+    if wino_split and cout == 64 and cin in (32, 64):
+        # half-resolution layers in one launch (16-column split): 80 us instead of 115 at (4,64,40,40,10), 44 instead of
+        # 78 (MIOpen) at (4,32->64,40,40,10)
+        return "wino_fused_conv3d_"
+    T = B * ((X + 1) // 2) * ((Y + 1) // 2) * ((Z + 1) // 2)
+    if cin >= 128 or (cin >= 64 and 64 * T * cin * 4 <= 160e6):
+        return "wino_conv3d_"
+    if full and wino_split and direct_conv:
+        # implicit GEMM with exact three-piece bf16 splits: no Winograd transforms (which made the fused kernel
+        # VALU-bound); 155 vs 163 us (ReLU), 159 vs 182 us (residual) at (4,32,80,80,20)
+        return "conv3_split_"
+    if full:
+        # the transformed tensor would be hundreds of MB, so everything (transforms, v_mfma_f32_32x32x2_f32 products - or
+        # their bf16 splits under wino_split -, epilogue) happens in one kernel: 225 us instead of 345 us at
+        # (4,32,80,80,20), 0.99 instead of 1.34 ms for eight 64^3 pose cubes
+        return "wino_fused_conv3d_"
+    return "library"
+
+
+def _zdft_front_ok(w0, w1, Z, SZ, channels=16) -> bool:
+    """the static conditions of the direct z-DFT form of the opening conv (weight w0): cubes of ``channels`` channels and
+    a (Z, SZ) the kernels are built for, 16 output channels, and a channels-last conv stack behind it (w1: a 3x3x3
+    weight tells the layout the stack runs in)"""
+    from . import _lib
+    return bool((int(Z), int(SZ), int(channels)) in _lib.ZDFT_SHAPES and int(w0.shape[0]) == 16 and int(w0.shape[1]) <= 16
+                and is_cl(w1))
+
+
 class _FreqConv3d(torch.autograd.Function):
     """Stride-1 'same' Conv3d (odd cubic kernel) in the frequency domain, forward AND backward, for the 7x7x7 opening
     conv of the V2V nets (v2v_net.py:113-117) on the GPU: zero-padded rFFT (rocFFT through torch.fft) -> channel
@@ -66,7 +124,7 @@ class _FreqConv3d(torch.autograd.Function):
         y = torch.fft.irfftn(Yf, s=S, dim=(2, 3, 4))[:, :, :X, :Y, :Z]
         if bias is not None:
             y = y + bias.view(1, O, 1, 1, 1)
-        cl = x.is_contiguous(memory_format=torch.channels_last_3d) and not x.is_contiguous()
+        cl = is_cl(x)
         ctx.save_for_backward(x, w)
         ctx.geom = (S, p, bias is not None, cl)
         return y.contiguous(memory_format=torch.channels_last_3d if cl else torch.contiguous_format)
@@ -118,13 +176,10 @@ class PadCinConv3d(nn.Conv3d):
                 self.groups == 1 and have >= cin and \
                 (not torch.is_grad_enabled() or x.shape[0] >= self.freq_domain_min_batch):
             return _FreqConv3d.apply(x[:, :cin] if have > cin else x, self.weight, self.bias)
-        target = have if have > cin else ((cin + 3) // 4 * 4 if cin >= 3 else cin)
-        if target == cin:
+        xp, w = pad_cin(x, self.weight)
+        if w is self.weight:
             return super().forward(x)
-        w = F.pad(self.weight, (0, 0, 0, 0, 0, 0, 0, target - cin))
-        if have < target:
-            x = F.pad(x, (0, 0, 0, 0, 0, 0, 0, target - have))
-        return F.conv3d(x, w, self.bias, self.stride, self.padding, self.dilation, self.groups)
+        return F.conv3d(xp, w, self.bias, self.stride, self.padding, self.dilation, self.groups)
 
 
 class ConvBnRelu3d(nn.Module):
@@ -208,6 +263,29 @@ class TiledZSpectrum:
         self.device, self.is_cuda, self.dtype = spec.device, spec.is_cuda, torch.float32
 
 
+class _Conv(NamedTuple):
+    """one BatchNorm-folded conv of the plan (the opening conv or a 3x3x3 layer) with every form of its weights it can run with"""
+    w: torch.Tensor                            # folded weight (O, C, k, k, k)
+    shift: torch.Tensor                        # what is left of bias and BatchNorm, per output channel
+    u: Optional[torch.Tensor] = None           # Winograd-domain weights (_lib.wino_weights)
+    split: Optional[torch.Tensor] = None       # ... in three bf16 pieces (_lib.wino_weights_split): the fused kernels
+    direct: Optional[torch.Tensor] = None      # w in three bf16 pieces (_lib.conv_weights_split): conv3_split_
+
+
+class _Res(NamedTuple):
+    """a residual block: conv-ReLU-conv, + the input (or its folded 1x1x1 projection ``skip``), ReLU"""
+    c1: _Conv
+    c2: _Conv
+    skip: Optional[torch.Tensor]
+
+
+class _Up(NamedTuple):
+    """a folded ConvTranspose3d(2, stride 2): weight (Cin, Cout, 2, 2, 2), shift, and the weight in GEMM form (Cin, 8*Cout)"""
+    wT: torch.Tensor
+    shift: torch.Tensor
+    wg: torch.Tensor
+
+
 class _FoldedV2V:
     """Inference execution plan of a V2VNet: every BatchNorm3d (running statistics) is folded into the
     preceding (transposed) conv's weights, so a layer is one MIOpen conv (no bias) + ONE fused
@@ -221,100 +299,95 @@ class _FoldedV2V:
     def __init__(self, net: "V2VNet"):
         self.net = net
         self.key = None
-        self.t = {}
+        self.layers = {}           # layer name -> _Conv ("front") | _Res | _Up
+        self.spectra = {}          # ("Wf" | "Wz" | "Wty", FFT shape) -> the opening conv's weight spectrum in that form
+        self.xpad = {}             # (cin, FFT shape, device) -> zero-padded input buffer of the frequency-domain front
+
+    def graph_tensors(self):
+        """everything a captured graph of this plan's forward may hold an address of (the layers' weights in all their
+        forms, the weight spectra, the padded FFT buffers), as they are now: whoever replays the graph keeps this"""
+        return dict(self.layers), dict(self.spectra), dict(self.xpad)
 
     @staticmethod
     def _key(net):
         ps = list(net.parameters()) + list(net.buffers())
         w3 = net.front_layers[1].res_branch[0].weight          # a 3x3x3 weight: its strides tell the memory format
-        # (a 1x1x1 weight is "contiguous" in both formats)
-        return (tuple((p.data_ptr(), p._version) for p in ps), str(w3.device),
-                bool(w3.is_contiguous(memory_format=torch.channels_last_3d) and not w3.is_contiguous()))
+        return (tuple((p.data_ptr(), p._version) for p in ps), str(w3.device), bool(is_cl(w3)))
+
+    def _ensure_built(self):
+        key = self._key(self.net)
+        if key != self.key:
+            self._build()
+            self.key = key
 
     @staticmethod
     def _fold(conv, bn, transposed=False):
         s = bn.weight / torch.sqrt(bn.running_var + bn.eps)
         shape = (1, -1, 1, 1, 1) if transposed else (-1, 1, 1, 1, 1)
         w = conv.weight * s.view(shape)
-        fmt = torch.channels_last_3d if conv.weight.is_contiguous(memory_format=torch.channels_last_3d) and \
-            not conv.weight.is_contiguous() else torch.contiguous_format
+        fmt = torch.channels_last_3d if is_cl(conv.weight) else torch.contiguous_format
         b = conv.bias if conv.bias is not None else torch.zeros_like(bn.running_mean)
         return w.contiguous(memory_format=fmt), ((b - bn.running_mean) * s + bn.bias).contiguous()
 
+    @staticmethod
+    def _conv3_record(w, shift):
+        """a folded 3x3x3 conv with the weight forms of every route conv3_route can give it (weights on the GPU), over all
+        input sizes (either side of the Infinity-Cache bound) and settings of wino_split / direct_conv"""
+        from . import _lib
+        cout, cin = int(w.shape[0]), int(w.shape[1])
+        routes = {conv3_route(cin, cout, (b, 2, 2, 2), True, ws, dc) for b in (1, 1 << 20) for ws in (True, False) for dc in (True, False)}
+        if not w.is_cuda or routes == {"library"}:
+            return _Conv(w, shift)
+        u = _lib.wino_weights(w)
+        # layers of the fused kernels: weights split for the bf16 matrix pipe (lane quarters for 64 output channels)
+        split = _lib.wino_weights_split(u, 16 if cout == 64 else 8) if "wino_fused_conv3d_" in routes else None
+        # full-resolution layers (16 | 32 -> 32): direct convolution on the bf16 matrix pipe (three exact pieces)
+        direct = _lib.conv_weights_split(w) if "conv3_split_" in routes else None
+        return _Conv(w, shift, u, split, direct)
+
     def _build(self):
-        n, t = self.net, {}
-        t["front"] = self._fold(n.front_layers[0].block[0], n.front_layers[0].block[1])
-        def res(name, blk):
-            from . import _lib
+        n, layers = self.net, {}
+        layers["front"] = _Conv(*self._fold(n.front_layers[0].block[0], n.front_layers[0].block[1]))
+        ed = n.encoder_decoder
+        for name in ("front_res", "encoder_res1", "encoder_res2", "mid_res", "decoder_res2", "decoder_res1", "skip_res1",
+                     "skip_res2"):
+            blk = n.front_layers[1] if name == "front_res" else getattr(ed, name)
             w1, s1 = self._fold(blk.res_branch[0], blk.res_branch[1])
             w2, s2 = self._fold(blk.res_branch[3], blk.res_branch[4])
-            # Winograd-domain weights for the wide (low-resolution) layers, see _conv3
-            wino = lambda w: w.is_cuda and (w.shape[1] >= 64 or (w.shape[0] == 32 and w.shape[1] in (16, 32)) or
-                                            (w.shape[0] == 64 and w.shape[1] == 32))
-            u1 = _lib.wino_weights(w1) if wino(w1) else None
-            u2 = _lib.wino_weights(w2) if wino(w2) else None
-            # full-resolution layers (16 | 32 -> 32): direct convolution on the bf16 matrix pipe (three exact pieces)
-            for wc, u in ((w1, u1), (w2, u2)):
-                if u is not None and wc.shape[0] == 32 and wc.shape[1] in (16, 32):
-                    u._sp3d_direct = _lib.conv_weights_split(wc)
-            for u in (u1, u2):                 # layers of the fused kernels: weights split for the bf16 matrix pipe
-                if u is not None and u.shape[2] == 32 and u.shape[1] in (16, 32):
-                    u._sp3d_split = _lib.wino_weights_split(u)
-                elif u is not None and u.shape[2] == 64 and u.shape[1] in (32, 64):
-                    u._sp3d_split = _lib.wino_weights_split(u, 16)
-            if len(blk.skip_con) > 0:
+            ws = None
+            if len(blk.skip_con) > 0:              # the skip's shift rides on the second conv's epilogue
                 ws, ss = self._fold(blk.skip_con[0], blk.skip_con[1])
-                t[name] = (w1, s1, w2, (s2 + ss).contiguous(), ws, u1, u2)
-            else:
-                t[name] = (w1, s1, w2, s2, None, u1, u2)
-        res("front_res", n.front_layers[1])
-        ed = n.encoder_decoder
-        for name in ("encoder_res1", "encoder_res2", "mid_res", "decoder_res2", "decoder_res1", "skip_res1", "skip_res2"):
-            res(name, getattr(ed, name))
+                s2 = (s2 + ss).contiguous()
+            layers[name] = _Res(self._conv3_record(w1, s1), self._conv3_record(w2, s2), ws)
         for name in ("decoder_upsample2", "decoder_upsample1"):
             blk = getattr(ed, name).block
             wT, sT = self._fold(blk[0], blk[1], transposed=True)
             # (Cin, Cout, 2,2,2) -> GEMM form (Cin, 8*Cout), columns ordered (i,j,k,o): see _up2x
             wg = wT.permute(0, 2, 3, 4, 1).reshape(wT.shape[0], 8 * wT.shape[1]).contiguous()
-            t[name] = (wT, sT, wg)
-        self.t = t
+            layers[name] = _Up(wT, sT, wg)
+        # the spectra belong to the old weights; the padded buffers go with them, a caller's view of one is then copied
+        self.layers, self.spectra, self.xpad = layers, {}, {}
 
-    def _conv3(self, x, w, u, shift, mode, residual=None):
-        """3x3x3 conv + fused epilogue.  Wide layers on small grids (the 1/4- and 1/2-resolution blocks: a GEMM with
-        few rows, where MIOpen's implicit-GEMM kernels drop to ~60 TFLOP/s) go through Winograd F(2x2x2,3x3x3):
-        HIP input/output transforms around one batched rocBLAS GEMM, 2.1x faster at (4,128,20,20,5) and 1.2x at
-        (4,64,40,40,10) (tools/exp_wino.py); the rule below keeps the transformed tensor (64*T*C floats) within
-        reach of the Infinity Cache, beyond which the transforms eat the gain."""
+    def _conv3(self, x, c: "_Conv", mode, residual=None):
+        """3x3x3 conv + fused epilogue on the route conv3_route names (weights on the GPU and channels-last x)"""
         from . import _lib
-        if u is not None and self.net.winograd and x.is_contiguous(memory_format=torch.channels_last_3d) \
-                and not x.is_contiguous():
-            B, C, X, Y, Z = x.shape
-            T = B * ((X + 1) // 2) * ((Y + 1) // 2) * ((Z + 1) // 2)
-            u3 = getattr(u, "_sp3d_split", None) if getattr(self.net, "wino_split", True) else None
-            if u3 is not None and u.shape[2] == 64:
-                # half-resolution layers in one launch: 80 us instead of 115 at (4,64,40,40,10), 44 instead of 78
-                # (MIOpen) at (4,32->64,40,40,10)
-                return _lib.wino_fused_conv3d_(x, u, shift, mode, residual, u3)
-            if C >= 128 or (C >= 64 and 64 * T * C * 4 <= 160e6):
-                return _lib.wino_conv3d_(x, u, shift, mode, residual)
-            w3 = getattr(u, "_sp3d_direct", None) if getattr(self.net, "wino_split", True) and getattr(self.net, "direct_conv", True) else None
-            if w3 is not None and C in (16, 32) and u.shape[2] == 32:
-                # implicit GEMM with exact three-piece bf16 splits: no Winograd transforms (which made the fused kernel
-                # VALU-bound); 155 vs 163 us (ReLU), 159 vs 182 us (residual) at (4,32,80,80,20)
-                return _lib.conv3_split_(x, w3, shift, mode, residual)
-            if C in (16, 32) and u.shape[2] == 32:
-                # full-resolution layers: the transformed tensor would be hundreds of MB, so everything (transforms,
-                # v_mfma_f32_32x32x2_f32 products, epilogue) happens in one kernel: 225 us instead of 345 us at
-                # (4,32,80,80,20), 0.99 instead of 1.34 ms for eight 64^3 pose cubes
-                u3 = getattr(u, "_sp3d_split", None) if getattr(self.net, "wino_split", True) else None
-                return _lib.wino_fused_conv3d_(x, u, shift, mode, residual, u3)
-        return _lib.channel_shift_act_(F.conv3d(x, w, None, 1, 1), shift, mode, residual)
+        n, route = self.net, "library"
+        split = getattr(n, "wino_split", True)
+        if c.u is not None and is_cl(x):
+            route = conv3_route(int(c.w.shape[1]), int(c.w.shape[0]), (x.shape[0],) + tuple(x.shape[2:]), n.winograd, split,
+                                getattr(n, "direct_conv", True))
+        if route == "conv3_split_":
+            return _lib.conv3_split_(x, c.direct, c.shift, mode, residual)
+        if route == "wino_fused_conv3d_":
+            return _lib.wino_fused_conv3d_(x, c.u, c.shift, mode, residual, c.split if split else None)
+        if route == "wino_conv3d_":
+            return _lib.wino_conv3d_(x, c.u, c.shift, mode, residual)
+        return _lib.channel_shift_act_(F.conv3d(x, c.w, None, 1, 1), c.shift, mode, residual)
 
     def _res(self, x, name):
-        w1, s1, w2, s2, ws, u1, u2 = self.t[name]
-        h = self._conv3(x, w1, u1, s1, 1)
-        r = x if ws is None else self._conv1(x, ws)
-        return self._conv3(h, w2, u2, s2, 2, r)
+        r = self.layers[name]
+        h = self._conv3(x, r.c1, 1)
+        return self._conv3(h, r.c2, 2, x if r.skip is None else self._conv1(x, r.skip))
 
     # -- library GEMM selection (OPT-IN) ---------------------------------------------------------------------------
     # The plan's GEMMs (batched Winograd products, transposed-conv and 1x1x1 GEMMs) are plain library calls; which
@@ -366,80 +439,53 @@ class _FoldedV2V:
 
     def _run(self, x):
         from . import _lib
-        key = self._key(self.net)
-        if key != self.key:
-            self._build()
-            self.key = key
-        w0, s0 = self.t["front"]
-        cin = w0.shape[1]
-        have = x.shape[1]
+        self._ensure_built()
+        w0, s0 = self.layers["front"][:2]
         if isinstance(x, TiledZSpectrum):
             return self._tail(self._front_zspectrum(x, w0, s0))
-        if self.net.fft_front and w0.shape[2] == 7 and have >= cin:
-            x = self._front_fft(x, w0, s0)
-            return self._tail(x)
-        target = have if have > cin else ((cin + 3) // 4 * 4 if cin >= 3 else cin)
-        if target != cin:
-            w0 = F.pad(w0, (0, 0, 0, 0, 0, 0, 0, target - cin))
-        if have < target:
-            x = F.pad(x, (0, 0, 0, 0, 0, 0, 0, target - have))
-        x = _lib.channel_shift_act_(F.conv3d(x, w0, None, 1, 3), s0, 1)
-        return self._tail(x)
+        if self.net.fft_front and w0.shape[2] == 7 and x.shape[1] >= w0.shape[1]:
+            return self._tail(self._front_fft(x, w0, s0))
+        x, w0 = pad_cin(x, w0)
+        return self._tail(_lib.channel_shift_act_(F.conv3d(x, w0, None, 1, 3), s0, 1))
 
     def _zdft_ok(self, x, w0, S):
-        """the direct z-DFT form of the opening conv applies: channels-last 16-channel cubes of a (Z, SZ) the kernels are
-        built for, 16 output channels, channels-last conv stack behind it"""
-        from . import _lib
+        """the direct z-DFT form of the opening conv applies: _zdft_front_ok, and x is channels-last 16-channel fp32 cubes"""
         if not (getattr(self.net, "zdft", True) and x.dim() == 5 and x.is_cuda and x.dtype == torch.float32):
             return False
-        w1 = self.t["front_res"][0]
-        return bool((int(x.shape[4]), int(S[2]), int(x.shape[1])) in _lib.ZDFT_SHAPES and int(w0.shape[0]) == 16
-                    and int(w0.shape[1]) <= 16 and self._is_cl(w1) and x.permute(0, 2, 3, 4, 1).is_contiguous())
+        return bool(_zdft_front_ok(w0, self.layers["front_res"].c1.w, x.shape[4], S[2], x.shape[1])
+                    and x.permute(0, 2, 3, 4, 1).is_contiguous())
 
-    _fft_len = staticmethod(fft_len)
-
-    @classmethod
-    def _fft_shape(cls, X, Y, Z, k):
+    @staticmethod
+    def _fft_shape(X, Y, Z, k):
         """padded transform lengths: >= n + k//2 zeros behind the signal, rocFFT-friendly factors, and a z length that
         is a multiple of 4 so that every row of the buffer starts 16-byte aligned"""
-        sz = cls._fft_len(Z + k - 1)
+        sz = fft_len(Z + k - 1)
         while sz % 4:
-            sz = cls._fft_len(sz + 2)
-        return (cls._fft_len(X + k - 1), cls._fft_len(Y + k - 1), sz)
+            sz = fft_len(sz + 2)
+        return (fft_len(X + k - 1), fft_len(Y + k - 1), sz)
 
     def _fft_buffer(self, B, cin, S, device):
         """zero-padded input buffer for B volumes: ONE buffer per (cin, S, device), grown when a larger batch shows
         up and sliced otherwise (the padding is never written, so any prefix of it is a valid padded buffer)"""
-        bkey = ("xpad", cin, S, str(device))
-        buf = self.t.get(bkey)
+        bkey = (cin, S, str(device))
+        buf = self.xpad.get(bkey)
         if buf is None or buf.shape[0] < B:
-            buf = self.t[bkey] = torch.zeros((B, cin) + S, dtype=torch.float32, device=device)
+            buf = self.xpad[bkey] = torch.zeros((B, cin) + S, dtype=torch.float32, device=device)
         return buf[:B]
 
     def fft_input_view(self, B, X, Y, Z, device):
         """(B,cin,X,Y,Z) view of the zero-padded input buffer of the frequency-domain opening conv: a producer
         (ProjectLayer.get_voxel(out=...)) that fills it saves the pad/copy pass; `run` recognises the view."""
-        key = self._key(self.net)
-        if key != self.key:
-            self._build()
-            self.key = key
-        w0 = self.t["front"][0]
+        self._ensure_built()
+        w0 = self.layers["front"].w
         cin, k = int(w0.shape[1]), int(w0.shape[2])
         if not (self.net.fft_front and k == 7):
             return None
-        S = self._fft_shape(X, Y, Z, k)
-        view = self._fft_buffer(B, cin, S, device)[:, :, :X, :Y, :Z]
-        view._sp3d_fft_shape = S
-        return view
-
-    @staticmethod
-    def tag_fft_view(view, S):
-        view._sp3d_fft_shape = S
-        return view
+        return self._fft_buffer(B, cin, self._fft_shape(X, Y, Z, k), device)[:, :, :X, :Y, :Z]
 
     def _is_padded_view(self, x, cin, S):
         """is x the [:X,:Y,:Z] corner of whole samples of the zero-padded buffer this plan owns for (cin, S)?"""
-        buf = self.t.get(("xpad", cin, S, str(x.device)))
+        buf = self.xpad.get((cin, S, str(x.device)))
         vol = S[0] * S[1] * S[2]
         if buf is None or x.dim() != 5 or x.shape[1] != cin or x.dtype != buf.dtype or \
                 tuple(x.stride()) != (cin * vol, vol, S[1] * S[2], S[2], 1):
@@ -448,21 +494,27 @@ class _FoldedV2V:
         per = cin * vol * buf.element_size()
         return off >= 0 and off % per == 0 and off // per + x.shape[0] <= buf.shape[0]
 
+    def _weights_f(self, w0, S):
+        """the opening conv's weight spectrum conj(rfftn(taps)) / N, (O, C, SX, SY, SZ/2+1)"""
+        if ("Wf", S) not in self.spectra:
+            # the signal sits at the ORIGIN of the padded buffer (so a producer can write 16-byte aligned rows into it,
+            # fft_input_view), hence the kernel is centred on the origin: taps -p..p wrap around to S-p..S-1
+            k = int(w0.shape[2])
+            wp = torch.zeros(tuple(w0.shape[:2]) + S, dtype=torch.float32, device=w0.device)
+            wp[:, :, :k, :k, :k] = w0.float()
+            wp = torch.roll(wp, shifts=(-(k // 2),) * 3, dims=(2, 3, 4))
+            # correlation (conj); the inverse transform's 1/N is folded in here, so irfftn runs unnormalised
+            self.spectra["Wf", S] = (torch.conj(torch.fft.rfftn(wp, dim=(2, 3, 4))).resolve_conj() /
+                                     float(S[0] * S[1] * S[2])).contiguous()
+        return self.spectra["Wf", S]
+
     def _weights_z(self, w0, S):
         """the opening conv's weight spectrum with kz as the slowest frequency index (what the direct z-DFT form contracts with)"""
-        wkey, zkey = ("Wf", S), ("Wz", S)
-        if zkey not in self.t:
-            if wkey not in self.t:
-                k = int(w0.shape[2])
-                wp = torch.zeros(tuple(w0.shape[:2]) + S, dtype=torch.float32, device=w0.device)
-                wp[:, :, :k, :k, :k] = w0.float()
-                wp = torch.roll(wp, shifts=(-(k // 2),) * 3, dims=(2, 3, 4))
-                self.t[wkey] = (torch.conj(torch.fft.rfftn(wp, dim=(2, 3, 4))).resolve_conj() /
-                                float(S[0] * S[1] * S[2])).contiguous()
-            self.t[zkey] = self.t[wkey].permute(0, 1, 4, 2, 3).contiguous()
-            if not any(k[0] == "xpad" for k in self.t if isinstance(k, tuple)):
-                del self.t[wkey]                       # nobody asked for the planar buffer: keep one spectrum only
-        return self.t[zkey]
+        if ("Wz", S) not in self.spectra:
+            self.spectra["Wz", S] = self._weights_f(w0, S).permute(0, 1, 4, 2, 3).contiguous()
+            if not self.xpad:
+                del self.spectra["Wf", S]              # nobody asked for the planar buffer: keep one spectrum only
+        return self.spectra["Wz", S]
 
     def _weights_ty(self, w0, S):
         """(T, tw) of _lib.freq_contract_ty: the opening conv's taps transformed along z and x only (float64 on the host
@@ -470,7 +522,7 @@ class _FoldedV2V:
         (cos, sin)(2 pi ky u / SY) table.  W^[o,c,kz,kx,ky] = conj(rfftn(taps centred on the origin)) / N is what the kernel
         rebuilds from them per bin (csrc/sp3d_fftconv.hip)."""
         key = ("Wty", S)
-        if key not in self.t:
+        if key not in self.spectra:
             import math
             k = int(w0.shape[2])
             p = k // 2
@@ -487,8 +539,8 @@ class _FoldedV2V:
             T = T.reshape(G.shape[0] * G.shape[1], G.shape[2], G.shape[3], 2 * (1 + 2 * p)).float().contiguous()
             ang = 2.0 * math.pi * torch.arange(SY, dtype=torch.float64)[:, None] * torch.arange(1, p + 1, dtype=torch.float64)[None, :] / SY
             tw = torch.stack([torch.cos(ang), torch.sin(ang)], -1).float().contiguous()
-            self.t[key] = (T.to(w0.device), tw.to(w0.device))
-        return self.t[key]
+            self.spectra[key] = (T.to(w0.device), tw.to(w0.device))
+        return self.spectra[key]
 
     def _contract(self, Xs, w0, S):
         """channel contraction of the opening conv on the kz-slowest spectrum: with the weight spectrum's y transform rebuilt
@@ -524,24 +576,9 @@ class _FoldedV2V:
         B, _, X, Y, Z = x.shape
         cin, k = int(w0.shape[1]), int(w0.shape[2])
         S = self._fft_shape(X, Y, Z, k)
-        wkey = ("Wf", S)
-        if wkey not in self.t and not (("Wz", S) in self.t and self._zdft_ok(x, w0, S)):
-            # the signal sits at the ORIGIN of the padded buffer (so a producer can write 16-byte aligned rows into it,
-            # fft_input_view), hence the kernel is centred on the origin: taps -p..p wrap around to S-p..S-1
-            wp = torch.zeros(tuple(w0.shape[:2]) + S, dtype=torch.float32, device=w0.device)
-            wp[:, :, :k, :k, :k] = w0.float()
-            wp = torch.roll(wp, shifts=(-(k // 2),) * 3, dims=(2, 3, 4))
-            # correlation (conj); the inverse transform's 1/N is folded in here, so irfftn runs unnormalised
-            self.t[wkey] = (torch.conj(torch.fft.rfftn(wp, dim=(2, 3, 4))).resolve_conj() /
-                            float(S[0] * S[1] * S[2])).contiguous()
         if self._zdft_ok(x, w0, S):
             # root grid: direct z-DFTs around dense 2-D complex transforms; the spectrum's slowest frequency index is kz,
-            # the weight spectrum is stored in the same order.  x is the unprojection's channels-last result.
-            zkey = ("Wz", S)
-            if zkey not in self.t:
-                self.t[zkey] = self.t[wkey].permute(0, 1, 4, 2, 3).contiguous()
-                if not any(k[0] == "xpad" for k in self.t if isinstance(k, tuple)):
-                    del self.t[wkey]                       # nobody asked for the planar buffer: keep one spectrum only
+            # the weight spectrum is stored in the same order (_weights_z).  x is the unprojection's channels-last result.
             Xs = _lib.cfft2d_(_lib.zdft_fwd_cl(x, cin, S), False, rows_in=X)          # rows x >= X are zero padding
             Ys = _lib.cfft2d_(self._contract(Xs, w0, S), True, rows_out=X)              # ... and not read on the way back
             return _lib.zdft_inv_cl(Ys, X, Y, Z, S[2], s0, True)
@@ -555,10 +592,9 @@ class _FoldedV2V:
             buf[:, :, :X, :Y, :Z].copy_(x[:, :cin])                             # borders stay zero across calls
         # cached hipFFT plans behind the C ABI: same rocFFT kernels (bit-identical spectra) as torch.fft.rfftn / irfftn,
         # minus the defensive clones torch makes around every real transform on ROCm (3 x ~55 MB per root-net step)
-        Yf = _lib.freq_contract(_lib.rfft3d(buf), self.t[wkey])
+        Yf = _lib.freq_contract(_lib.rfft3d(buf), self._weights_f(w0, S))
         y = _lib.irfft3d_(Yf, S[2])                                  # unnormalised (1/N is in Wf); Yf is scratch
-        w1 = self.t["front_res"][0]             # a 3x3x3 weight tells the layout the conv stack runs in
-        cl = w1.is_contiguous(memory_format=torch.channels_last_3d) and not w1.is_contiguous()
+        cl = is_cl(self.layers["front_res"].c1.w)       # a 3x3x3 weight tells the layout the conv stack runs in
         if cl and y.is_contiguous() and y.shape[1] % 4 == 0 and Z % 4 == 0 and 4 * Z * (y.shape[1] + 4) * 4 <= 65536:
             return _lib.crop_shift_act_cl(y, X, Y, Z, s0, True)     # crop + layout change + epilogue in one pass
         y = y[:, :, :X, :Y, :Z]
@@ -576,8 +612,8 @@ class _FoldedV2V:
         x = self._up2x(x, "decoder_upsample2", skip2)
         x = self._res(x, "decoder_res1")
         o = self.net.output_layer
-        wT, sT, wg = self.t["decoder_upsample1"]
-        if self.net.winograd and self._is_cl(x) and wg.is_cuda and wT.shape[1] == 32 and x.dtype == torch.float32:
+        wT, sT, wg = self.layers["decoder_upsample1"]
+        if self.net.winograd and is_cl(x) and wg.is_cuda and wT.shape[1] == 32 and x.dtype == torch.float32:
             # the last up-sampling layer's only consumer is the 1x1x1 output conv: one kernel, no 32-channel tensor
             return _lib.upsample2x_head_(x, wg, sT, skip1, o.weight, o.bias)
         x = self._up2x(x, "decoder_upsample1", skip1)
@@ -586,27 +622,23 @@ class _FoldedV2V:
     def _pool(self, x):
         """MaxPool3d(2,2): own channels-last kernel (torch's also computes the arg-max indices: 2.4x the time)"""
         from . import _lib
-        if self._is_cl(x) and x.is_cuda and x.dtype == torch.float32 and x.shape[1] % 4 == 0 and \
+        if is_cl(x) and x.is_cuda and x.dtype == torch.float32 and x.shape[1] % 4 == 0 and \
                 all(int(v) % 2 == 0 for v in x.shape[2:]):
             return _lib.maxpool2x(x)
         return F.max_pool3d(x, 2, 2)
-
-    @staticmethod
-    def _is_cl(x):
-        return x.is_contiguous(memory_format=torch.channels_last_3d) and not x.is_contiguous()
 
     def _up2x(self, x, name, skip):
         """ConvTranspose3d(2, stride 2) + BN + ReLU + skip: no overlapping taps, so on channels-last activations it is
         one GEMM + a scatter with the epilogue (sp3d_upsample2x_scatter) instead of MIOpen's backward-data kernel"""
         from . import _lib
-        wT, sT, wg = self.t[name]
-        if self.net.winograd and self._is_cl(x) and wg.is_cuda and wT.shape[1] % 4 == 0:
+        wT, sT, wg = self.layers[name]
+        if self.net.winograd and is_cl(x) and wg.is_cuda and wT.shape[1] % 4 == 0:
             return _lib.upsample2x_(x, wg, sT, skip)
         return _lib.channel_shift_act_(F.conv_transpose3d(x, wT, None, 2), sT, 3, skip)
 
     def _conv1(self, x, w, bias=None):
         """1x1x1 conv: on channels-last activations a plain (voxels, Cin) x (Cin, Cout) GEMM on the same memory"""
-        if self.net.winograd and self._is_cl(x) and x.is_cuda:
+        if self.net.winograd and is_cl(x) and x.is_cuda:
             B, C, X, Y, Z = x.shape
             O = w.shape[0]
             x2 = x.permute(0, 2, 3, 4, 1).reshape(-1, C)
@@ -662,16 +694,16 @@ class V2VNet(nn.Module):
         self._plan = None
         return super()._load_from_state_dict(*args, **kwargs)
 
+    def _get_plan(self) -> _FoldedV2V:
+        if self._plan is None:
+            self._plan = _FoldedV2V(self)
+        return self._plan
+
     def forward(self, x):
-        if isinstance(x, TiledZSpectrum):
-            if self._plan is None:
-                self._plan = _FoldedV2V(self)
-            return self._plan.run(x)
-        if self.fused_inference and not self.training and not torch.is_grad_enabled() and x.is_cuda \
-                and x.dtype == torch.float32 and x.shape[2] % 4 == 0 and x.shape[3] % 4 == 0 and x.shape[4] % 4 == 0:
-            if self._plan is None:
-                self._plan = _FoldedV2V(self)
-            return self._plan.run(x)
+        if isinstance(x, TiledZSpectrum) or (
+                self.fused_inference and not self.training and not torch.is_grad_enabled() and x.is_cuda
+                and x.dtype == torch.float32 and x.shape[2] % 4 == 0 and x.shape[3] % 4 == 0 and x.shape[4] % 4 == 0):
+            return self._get_plan().run(x)
         return self.output_layer(self.encoder_decoder(self.front_layers(x)))
 
     def input_view(self, B, X, Y, Z, device):
@@ -679,9 +711,7 @@ class V2VNet(nn.Module):
         padded buffer), or None when any tensor will do"""
         if not (self.wants_planar_input() and torch.device(device).type == "cuda" and X % 4 == 0 and Y % 4 == 0 and Z % 4 == 0):
             return None
-        if self._plan is None:
-            self._plan = _FoldedV2V(self)
-        return self._plan.fft_input_view(B, X, Y, Z, device)
+        return self._get_plan().fft_input_view(B, X, Y, Z, device)
 
     def input_chunk_views(self, P, chunk, X, Y, Z, device):
         """for a caller that produces P inputs at once and feeds them in chunks of `chunk` (tail rounded up to a power
@@ -690,8 +720,8 @@ class V2VNet(nn.Module):
         first = self.input_view(1, X, Y, Z, device)
         if first is None:
             return None
-        S = first._sp3d_fft_shape
         cin = first.shape[1]
+        S = _FoldedV2V._fft_shape(X, Y, Z, 7)          # input_view answers for the 7x7x7 FFT opening conv only
         sizes = []
         s0 = 0
         while s0 < P:
@@ -701,21 +731,16 @@ class V2VNet(nn.Module):
         total = sizes[-1][0] + sizes[-1][2]
         buf = self._plan._fft_buffer(total, cin, S, device)
         whole = buf[:P, :, :X, :Y, :Z]
-        chunks = [(n, _FoldedV2V.tag_fft_view(buf[a:a + m, :, :X, :Y, :Z], S)) for a, n, m in sizes]
+        chunks = [(n, buf[a:a + m, :, :X, :Y, :Z]) for a, n, m in sizes]
         return whole, chunks
 
     def wants_channels_last_cubes(self, X, Y, Z) -> bool:
         """True when the next inference forward's opening conv reads channels-last 16-channel cubes directly (direct
         z-DFT form, root grid): the caller should ask the unprojection for its channels-last result, not fill input_view"""
-        from . import _lib
         if not (self.wants_planar_input() and getattr(self, "zdft", True) and self.front_layers[0].block[0].kernel_size == (7, 7, 7)):
             return False
         w0, w1 = self.front_layers[0].block[0].weight, self.front_layers[1].res_branch[0].weight
-        k = int(w0.shape[2])
-        S = _FoldedV2V._fft_shape(X, Y, Z, k)
-        cl = w1.is_contiguous(memory_format=torch.channels_last_3d) and not w1.is_contiguous()
-        return bool(w0.is_cuda and cl and (int(Z), int(S[2]), 16) in _lib.ZDFT_SHAPES and int(w0.shape[0]) == 16
-                    and int(w0.shape[1]) <= 16)
+        return bool(w0.is_cuda and _zdft_front_ok(w0, w1, Z, _FoldedV2V._fft_shape(X, Y, Z, 7)[2]))
 
     def wants_zspectrum(self, X, Y, Z, cin: int):
         """SZ when the next inference forward can start from the cubes' z-spectrum (``TiledZSpectrum``: the unprojection

@@ -142,9 +142,8 @@ def test_contraction_with_the_y_transform_rebuilt_per_bin(dev):
     torch.manual_seed(5)
     net = V2VNet(15, 1).to(dev).eval()
     plan = _FoldedV2V(net)
-    plan._build()
-    plan.key = plan._key(net)
-    w0, s0 = plan.t["front"]
+    plan._ensure_built()
+    w0 = plan.layers["front"].w
     S = (88, 88, 28)
     Wz = plan._weights_z(w0, S)                                           # (16,15,15,88,88)
     T, tw = plan._weights_ty(w0, S)

@@ -625,12 +625,12 @@ def test_freq_contract_and_fft_opening_conv(dev, shape):
     fp32 convolution is, plus a small margin)."""
     import torch.nn.functional as F
     from selfpose3d_amd import _lib
-    from selfpose3d_amd.v2v_net import _FoldedV2V
+    from selfpose3d_amd.v2v_net import fft_len
     B, C, O, (X, Y, Z) = shape
     g = torch.Generator(device="cpu").manual_seed(5)
     x = torch.rand((B, C, X, Y, Z), generator=g).to(dev)
     w = (torch.randn((O, C, 7, 7, 7), generator=g) * 0.05).to(dev)
-    S = tuple(_FoldedV2V._fft_len(n + 6) for n in (X, Y, Z))
+    S = tuple(fft_len(n + 6) for n in (X, Y, Z))
     Wf = torch.conj(torch.fft.rfftn(w, s=S, dim=(2, 3, 4))).resolve_conj().contiguous()
     xp = F.pad(x, (3, S[2] - Z - 3, 3, S[1] - Y - 3, 3, S[0] - X - 3))
     Xf = torch.fft.rfftn(xp, dim=(2, 3, 4))

@@ -29,11 +29,11 @@ from tests import golden_io as gio
 pytestmark = pytest.mark.gpu
 
 # ---- census: the kernel every layer takes, from the dispatch rules of v2v_net.py --------------------------------------------
-# _conv3 (v2v_net.py:282-311) on channels-last activations with the default switches: 16|32 -> 32 at full resolution have
-# _sp3d_direct -> conv3_split_; 32|64 -> 64 have a 16-column split (u.shape[2] == 64) -> wino_fused_conv3d_ (split64);
-# 64|128 -> 128 have no split, C >= 128 or 64*T*C*4 <= 160e6 at every shape below -> wino_conv3d_.  _pool (:586-592):
-# channels-last, C % 4 == 0, even sides -> maxpool2x.  _up2x (:598-605): 64 output channels -> upsample2x_.  _tail
-# (:578-582): the 32-channel up-sampling + 1^3 output conv -> upsample2x_head_.
+# v2v_net.conv3_route on channels-last activations with the default switches: 16|32 -> 32 at full resolution ->
+# conv3_split_; 32|64 -> 64 (16-column split) -> wino_fused_conv3d_ (split64); 64|128 -> 128 have no split, C >= 128 or
+# 64*T*C*4 <= 160e6 at every shape below -> wino_conv3d_.  _FoldedV2V._pool: channels-last, C % 4 == 0, even sides ->
+# maxpool2x.  _FoldedV2V._up2x: 64 output channels -> upsample2x_.  _FoldedV2V._tail: the 32-channel up-sampling + 1^3
+# output conv -> upsample2x_head_.
 # (layer, kernels in call order, input channels, resolution divisor of the input)
 TAIL = [
     ("front_res", ("conv3_split_", "conv3_split_"), 16, 1),
@@ -49,7 +49,7 @@ TAIL = [
     ("decoder_res1", ("wino_fused_conv3d_", "wino_fused_conv3d_"), 64, 2),
     ("head", ("upsample2x_head_",), 64, 2),
 ]
-# the opening 7^3 conv (_run, _front_zspectrum, _front_fft: v2v_net.py:367-387, 506-566)
+# the opening 7^3 conv (_FoldedV2V._run, _front_zspectrum, _front_fft)
 FRONTS = {
     "zspectrum": ("cfft2d_88_tiled", "freq_contract", "cfft2d_", "zdft_inv_cl"),          # TiledZSpectrum (fused unprojection)
     "zdft_cl": ("zdft_fwd_cl", "cfft2d_", "freq_contract", "cfft2d_", "zdft_inv_cl"),     # channels-last 16-channel cubes

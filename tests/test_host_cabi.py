@@ -373,9 +373,9 @@ def test_torch_op_registry_face():
 def test_fft_lengths_for_the_opening_conv():
     """FFT sizes of the frequency-domain 7x7x7 conv: even, >= n + 6, prime factors <= 13, at most one distinct odd
     prime (70 = 2*5*7 and 140 lose to 72 and 144 in rocFFT); the z length is a multiple of 4 (16-byte aligned rows)"""
-    from selfpose3d_amd.v2v_net import _FoldedV2V
+    from selfpose3d_amd.v2v_net import _FoldedV2V, fft_len
     for n, want in ((86, 88), (26, 26), (70, 72), (22, 22), (14, 14), (46, 48), (134, 144)):
-        m = _FoldedV2V._fft_len(n)
+        m = fft_len(n)
         assert m == want and m % 2 == 0 and m >= n
         r, odd = m, 0
         for q in (2, 3, 5, 7, 11, 13):
@@ -437,7 +437,7 @@ def test_v2v_inference_plan_key_sees_every_weight_change():
 
 def test_padded_fft_input_view_is_recognised_by_address_not_by_python_attribute():
     """get_voxel(out=view) returns the buffer through an autograd Function; under no_grad that re-wraps the
-    tensor into a new Python object without the old `_sp3d_fft_shape` tag, and the opening conv then copied the padded
+    tensor into a new Python object without the Python attribute that used to tag it, and the opening conv then copied the padded
     buffer's corner onto itself.  The plan now recognises its own buffer by data_ptr + strides."""
     from selfpose3d_amd.v2v_net import V2VNet, _FoldedV2V
     net = V2VNet(2, 1).eval()
@@ -459,6 +459,47 @@ def test_padded_fft_input_view_is_recognised_by_address_not_by_python_attribute(
     assert not plan._is_padded_view(view.clone(), 2, S)          # a copy is not the buffer
     assert not plan._is_padded_view(view[:, :1], 1, S)           # wrong channel count
     assert not plan._is_padded_view(view[:, :, 1:], 2, S)        # not the corner
+
+
+def test_conv3_route_reproduces_the_census_of_every_configuration():
+    """v2v_net.conv3_route, a function of channels, input shape and the three switches alone, gives every 3x3x3 layer of
+    every root and pose configuration the kernel that tests/test_gpu_v2v_plan_f64.py pins on the GPU (TAIL), and the
+    documented routes when wino_split / direct_conv are off (bench.py's fp32-matrix leg): the full-resolution layers fall
+    back to the one-launch Winograd kernel, the 32 -> 64 layer to the library, and a 64 -> 64 layer to wino_conv3d_ only
+    while its transformed tensor 64 * T * 64 * 4 bytes fits the 160e6-byte Infinity-Cache bound (T <= 9765 tiles)"""
+    from selfpose3d_amd.v2v_net import conv3_route
+    from tests.test_gpu_v2v_plan_f64 import POSE_CONFIGS, ROOT_CONFIGS, TAIL
+    cout = {"front_res": 32, "skip_res1": 32, "encoder_res1": 64, "skip_res2": 64, "encoder_res2": 128, "mid_res": 128,
+            "decoder_res2": 128, "decoder_res1": 64}
+    res = [row for row in TAIL if row[0] in cout]
+    assert len(res) == 8 and {r[0] for r in res} == set(cout)
+    cfgs = {cid: (c["B"], c["cube"]) for cid, c in ROOT_CONFIGS.items()}
+    # the pose net runs its 64^3 cubes in chunks of at most 8, each padded to a power of two
+    for cid, (B, K, _) in POSE_CONFIGS.items():
+        for m in {1 << (min(8, B * K - s) - 1).bit_length() for s in range(0, B * K, 8)}:
+            cfgs[f"{cid}_chunk{m}"] = (m, (64, 64, 64))
+    assert {b for b, cube in cfgs.values() if cube == (64, 64, 64)} == {1, 4, 8}
+
+    def routes(name, cin, d, B, cube, **switches):
+        o, shape = cout[name], (B,) + tuple(v // d for v in cube)
+        return conv3_route(cin, o, shape, **switches), conv3_route(o, o, shape, **switches)
+
+    # half-resolution tiles of the 64 -> 64 layers: T = B * (X/4) * (Y/4) * (Z/4) of the cube
+    fits = {cid: B * (X // 4) * (Y // 4) * (Z // 4) <= 9765 for cid, (B, (X, Y, Z)) in cfgs.items()}
+    assert fits["R1_b4"] and not fits["R5_b2"] and fits["P1_p1_chunk1"] and not fits["P1_p8_chunk8"]     # 8000, 32000, 4096, 32768
+    n = 0
+    for cid, (B, cube) in cfgs.items():
+        for name, kernels, cin, d in res:
+            assert routes(name, cin, d, B, cube) == kernels, (cid, name)
+            assert routes(name, cin, d, B, cube, winograd=False) == ("library", "library"), (cid, name)
+            fused = ("wino_fused_conv3d_",) * 2 if cout[name] == 32 else kernels
+            assert routes(name, cin, d, B, cube, direct_conv=False) == fused, (cid, name)
+            w64 = "wino_conv3d_" if fits[cid] else "library"
+            nosplit = {32: ("wino_fused_conv3d_",) * 2, 64: ("library" if cin == 32 else w64, w64), 128: ("wino_conv3d_",) * 2}
+            assert routes(name, cin, d, B, cube, wino_split=False) == nosplit[cout[name]], (cid, name)
+            assert routes(name, cin, d, B, cube, wino_split=False, direct_conv=False) == nosplit[cout[name]], (cid, name)
+            n += 1
+    assert n == 8 * len(cfgs) and len(cfgs) == len(ROOT_CONFIGS) + 5
 
 
 def test_three_piece_weight_splits_are_exact_and_laid_out_as_documented():

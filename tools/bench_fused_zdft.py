@@ -78,8 +78,8 @@ for cold in (False, True):
 # round 6, second step: the channel contraction with the weight spectrum's y transform rebuilt per bin
 from selfpose3d_amd.v2v_net import V2VNet, _FoldedV2V
 net = V2VNet(15, 1).to(dev).eval()
-plan = _FoldedV2V(net); plan._build(); plan.key = plan._key(net)
-w0, _s0 = plan.t["front"]
+plan = _FoldedV2V(net); plan._ensure_built()
+w0 = plan.layers["front"].w
 Wz = plan._weights_z(w0, S); Tt, tw = plan._weights_ty(w0, S)
 Xs = _lib.cfft2d_88_tiled(spec1, 80, 80)
 for cold in (False, True):
