@@ -92,7 +92,18 @@ enum {
      * (BASELINE configs[4] "mixed bf16": storage only - projection, interpolation and view fusion
      * stay fp32; cubes are rounded to nearest-even on the final store). */
     SP3D_HM_BF16 = 0x200,
-    SP3D_OUT_BF16 = 0x400
+    SP3D_OUT_BF16 = 0x400,
+    /* OR-ed into hm_layout of sp3d_unproject_fwd, _fwd_indexed and _fwd_strided: unproject ONE channel of a wider fp32
+     * heat-map tensor, read where it lies (no slice copy, no re-tiling pass, one launch; the root-joint map of the
+     * ROOTNET_ROOTHM root nets).  hm_views[c] points at the wanted channel's element (sample 0, row 0, pixel 0) of view c
+     * and needs 4-byte alignment only.  SP3D_LAYOUT_PLANAR: Jp = channel count of the (B, Jp, h, w) tensor the pointer lies
+     * in (>= 1); SP3D_LAYOUT_NHWC: Jp = pixel stride in elements of the (B, h, w, Jp) buffer (>= 1, any value).
+     * J = channels written: 1, or 4 (the value and three zero channels); with SP3D_OUT_CHANNELS_LAST J must be 4.
+     * Same bits as the other forward kernels give for that channel.  SP3D_EUNSUPPORTED, before any launch, for any
+     * other J, for either bf16 flag, for sp3d_unproject_fwd_train (no pass mask), for heat-maps narrower or lower
+     * than 2 pixels or of more than 2^24 pixels, and for a sample of more than 2^31 bytes; SP3D_EINVAL for Jp < 1 and for a
+     * layout byte that is neither SP3D_LAYOUT_PLANAR nor SP3D_LAYOUT_NHWC. */
+    SP3D_HM_ONE_CHANNEL = 0x800
 };
 
 int sp3d_abi_version(void);

@@ -23,6 +23,7 @@ LAYOUT_NHWC = 1
 OUT_CHANNELS_LAST = 0x100
 HM_BF16 = 0x200
 OUT_BF16 = 0x400
+HM_ONE_CHANNEL = 0x800      # one channel of a wider tensor, read in place (include/sp3d.h)
 SCATTER_AUTO, SCATTER_PER_TAP, SCATTER_MERGE = 0, 2, 3      # include/sp3d.h: per-call scatter choice of unproject_bwd_packed
 MAX_VIEWS = 16
 MAX_TOPK = 32
@@ -238,21 +239,29 @@ def unproject_fwd(views: Sequence[torch.Tensor], layout: int, jp: int, cam: torc
                   valid: torch.Tensor, B: int, J: int, h: int, w: int, cube_size, grid_size, img_size,
                   want_grids: bool = True, variant: Optional[int] = None, channels_last: bool = False,
                   sample_of: Optional[torch.Tensor] = None, out_dtype: torch.dtype = torch.float32,
-                  pass_mask: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None):
+                  pass_mask: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None, one_channel: bool = False):
     """-> (cubes (B,J,X,Y,Z), grids (B,N,3) | None).  With ``channels_last`` the cubes tensor has
     torch.channels_last_3d strides (memory (B,X,Y,Z,J), J % 4 == 0, NHWC input only).
     ``sample_of`` (int32, (B,)): output cube p reads heat-map/camera row sample_of[p] (B = #cubes).
     ``out``: a (B,J,X,Y,Z) VIEW of a larger buffer (z contiguous, e.g. the zero-padded FFT input of the opening
-    conv): the planar result is written straight into it (sp3d_unproject_fwd_strided)."""
+    conv): the planar result is written straight into it (sp3d_unproject_fwd_strided).
+    ``one_channel`` (SP3D_HM_ONE_CHANNEL): ``views[c]`` is any fp32 tensor whose ``data_ptr()`` is the wanted channel's first
+    element of view c - a (B,1,h,w) slice of a planar (B,jp,h,w) tensor (``LAYOUT_PLANAR``, ``jp`` = its channel count) or
+    of a channels-last (B,h,w,jp) buffer (``LAYOUT_NHWC``, ``jp`` = its pixel stride) - read in place; ``J`` = channels
+    written, 1 or 4 (value + three zero channels; channels-last results: 4)."""
     lib = load()
     dev = cam.device
     _require_cam(cam)
     X, Y, Z = (int(c) for c in cube_size)
     V = len(views)
+    one = HM_ONE_CHANNEL if one_channel else 0
+    if one_channel:
+        assert pass_mask is None and variant is None and out_dtype == torch.float32 and jp >= 1
+        assert all(v.dtype == torch.float32 for v in views)
     if out is not None:
-        assert layout == LAYOUT_NHWC and not channels_last and not want_grids and pass_mask is None and variant is None
+        assert (layout == LAYOUT_NHWC or one_channel) and not channels_last and not want_grids and pass_mask is None and variant is None
         assert tuple(out.shape) == (B, J, X, Y, Z) and out.stride(4) == 1 and out.dtype == out_dtype
-        flags = (HM_BF16 if views[0].dtype == torch.bfloat16 else 0) | (OUT_BF16 if out_dtype == torch.bfloat16 else 0)
+        flags = (HM_BF16 if views[0].dtype == torch.bfloat16 else 0) | (OUT_BF16 if out_dtype == torch.bfloat16 else 0) | one
         st = (C.c_int64 * 4)(*[int(v) for v in out.stride()[:4]])
         rc = lib.sp3d_unproject_fwd_strided(_ptr_array(views), layout | flags, jp, cam.data_ptr(), _opt(sample_of),
                                             centers.data_ptr(), valid.data_ptr(), out.data_ptr(), st, B, V, J, h, w, X, Y, Z,
@@ -264,7 +273,7 @@ def unproject_fwd(views: Sequence[torch.Tensor], layout: int, jp: int, cam: torc
     else:
         cubes = torch.empty((B, J, X, Y, Z), dtype=out_dtype, device=dev)
     flags = (OUT_CHANNELS_LAST if channels_last else 0) | (HM_BF16 if views[0].dtype == torch.bfloat16 else 0) | \
-        (OUT_BF16 if out_dtype == torch.bfloat16 else 0)
+        (OUT_BF16 if out_dtype == torch.bfloat16 else 0) | one
     grids = torch.empty((B, X * Y * Z, 3), dtype=torch.float32, device=dev) if want_grids else None
     gs = _f3(grid_size)
     if pass_mask is not None:

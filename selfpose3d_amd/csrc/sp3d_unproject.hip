@@ -670,6 +670,130 @@ __global__ __launch_bounds__(64 * NW) void unproject_pipe_kernel(Views hm, const
 }
 
 // ------------------------------------------------------------------------------------------
+// one-channel forward (SP3D_HM_ONE_CHANNEL): ONE channel of a wider heat-map tensor, read where it lies - the root
+// joint's map of the ROOTNET_ROOTHM root nets (cuboid_proposal_net.py:103-108 of the reference, V2VNet(1, 1)).
+//
+// Lane = voxel in every phase (projection, gather, view fusion, store): no LDS, no barrier.  A wave owns 64 consecutive
+// voxels.  hm.p[c] points at the wanted channel's element (sample 0, row 0, pixel 0) of view c; a tap is one
+// global_load_dword at  sample * s_sample + y * s_row + x * s_px  elements from it, so the same kernel reads a channel
+// plane of a planar (B,Jt,h,w) tensor (Jt*h*w, w, 1) and a channel of a channels-last (B,h,w,PS) buffer
+// (h*w*PS, w*PS, PS).  Projection and tap records are project_pk / make_record_pk (zero weights on clamped in-range
+// addresses: a branch-free gather); interpolation and view fusion are pipe_views' / pipe_tile's, operation for
+// operation, so the result has the bits of the packed path's channel.
+//
+// Latency (at B = 1 the root grid is 2 000 waves on 1 024 SIMDs): the views are taken in chunks of CS; a chunk's
+// records stay in registers, all of its tap loads are issued back to back, and the next chunk is projected while
+// they are in flight.  The FMAs run last, in view order.  VT >= V is the number of view slots the kernel is unrolled
+// for (launch_one: V itself up to 6, then 8, 10, 12, 16), CS = 4 up to 8 views and 8 above.
+//
+// Result: planar with g.J = 1 or 4 channels (dense or strided; channels 1-3 zeros), or channels-last (B,X,Y,Z,4) as
+// one 16-byte store {v, 0, 0, 0} per lane.
+// ------------------------------------------------------------------------------------------
+template <int VT, int CS, bool OUTCL>
+__global__ __launch_bounds__(64) void unproject_one_kernel(Views hm, const float *__restrict__ cam,
+                                                           const float *__restrict__ centers,
+                                                           const uint8_t *__restrict__ valid, float *__restrict__ cubes,
+                                                           float *__restrict__ grids, Geom g, long long s_sample,
+                                                           int s_row, int s_px)
+{
+    constexpr int NCH = (VT + CS - 1) / CS;
+    int b, tile;
+    if (!xcd_map_fast(blockIdx.x, g, b, tile)) return;
+    const int bs = g.sample_of ? g.sample_of[b] : b;
+    const int lane = threadIdx.x;
+    const int n0 = tile * 64;
+    if (n0 >= g.N) return;
+    const int nvox = min(64, g.N - n0);
+    const bool inb = lane < nvox;
+    const int n = n0 + (inb ? lane : 0);
+    int vx, rem, vy, vz;
+    udiv_magic((uint32_t)n, (uint32_t)g.YZ, g.magicYZ, vx, rem);
+    udiv_magic((uint32_t)rem, (uint32_t)g.Z, g.magicZ, vy, vz);
+    // where this lane's voxel goes: channel plane j of a planar result starts j * sJ further
+    float *dst = OUTCL ? cubes + ((size_t)b * g.N + n) * 4
+                       : cubes + (size_t)b * g.sB + (g.dense ? (size_t)n : (size_t)vx * g.sX + (size_t)vy * g.sY + vz);
+    float out = 0.0f;
+    if (valid[b]) {
+        const float x = linspace_step(g.Lx, g.stepx, g.X, vx) + centers[3 * b + 0];
+        const float y = linspace_step(g.Ly, g.stepy, g.Y, vy) + centers[3 * b + 1];
+        const float z = linspace_step(g.Lz, g.stepz, g.Z, vz) + centers[3 * b + 2];
+        if (grids && inb) {
+            float *gp = grids + ((size_t)b * g.N + n) * 3;
+            gp[0] = x; gp[1] = y; gp[2] = z;
+        }
+        const unsigned long long inbm = __builtin_amdgcn_ballot_w64(inb);
+        uint32_t mymask = 0;                        // views that see MY voxel (+ bit 31: NaN position)
+        uint32_t have = 0;                          // wave-uniform: views with a record (some voxel of the wave sees them)
+        uint32_t off[VT];                           // byte offset of the 2x2 block inside the sample's image
+        float w00[VT], w10[VT], w01[VT], w11[VT];
+        float t00[VT], t10[VT], t01[VT], t11[VT];
+        const size_t pxb = (size_t)s_px * sizeof(float), rowb = (size_t)s_row * sizeof(float);
+#pragma unroll
+        for (int ch = 0; ch < NCH; ++ch) {
+#pragma unroll
+            for (int c = ch * CS; c < (ch + 1) * CS && c < VT; ++c) {
+                off[c] = 0u;
+                w00[c] = w10[c] = w01[c] = w11[c] = 0.0f;
+                if (c < g.V) {
+                    const float *cm = cam + ((size_t)bs * g.V + c) * SP3D_CAM_STRIDE;
+                    P1State st;
+                    const bool go = project_pk(cm, g, x, y, z, inbm, st);
+                    add_mask(mymask, st.bm);
+                    if (st.nm != 0ull && lane_of(st.nm)) mymask |= 0x80000000u;
+                    const unsigned long long um = st.bm & ~st.nm;
+                    if (go && um != 0ull) {         // else: no voxel of this wave sees camera c
+                        const RecPk r = make_record_pk(lane_of(um), st.i, g.w, g.h);
+                        off[c] = (__umul24((unsigned)r.y0, (unsigned)s_row) + __umul24((unsigned)r.x0, (unsigned)s_px)) << 2;
+                        w00[c] = r.wt.x; w10[c] = r.wt.y; w01[c] = r.wb.x; w11[c] = r.wb.y;
+                        have |= 1u << c;
+                    }
+                }
+            }
+            __builtin_amdgcn_sched_barrier(0);
+            // The chunk's taps: four wave-uniform bases (scalar register pairs) + one 32-bit byte offset per lane, no
+            // branch between the loads.  A view without a record (and a slot past V, which reads view 0) loads its
+            // first 2x2 block with zero weights and is left out of the sum below.  Issued in the reverse of the order
+            // the interpolation consumes them (loads return in order).
+#pragma unroll
+            for (int c = min((ch + 1) * CS, VT) - 1; c >= ch * CS; --c) {
+                const char *vb = reinterpret_cast<const char *>((c < g.V ? hm.p[c] : hm.p[0]) + (ptrdiff_t)bs * s_sample);
+                const char *vb2 = vb + rowb;
+                t11[c] = *reinterpret_cast<const float *>(vb2 + pxb + off[c]);
+                t01[c] = *reinterpret_cast<const float *>(vb2 + off[c]);
+                t10[c] = *reinterpret_cast<const float *>(vb + pxb + off[c]);
+                t00[c] = *reinterpret_cast<const float *>(vb + off[c]);
+            }
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        float acc = 0.0f;
+#pragma unroll
+        for (int c = 0; c < VT; ++c) {
+            // ATen's bilinear chain: fma(se, wse, fma(sw, wsw, fma(ne, wne, nw * wnw)))
+            float v = t00[c] * w00[c];
+            v = fmaf(t10[c], w10[c], v);
+            v = fmaf(t01[c], w01[c], v);
+            v = fmaf(t11[c], w11[c], v);
+            const float a = acc + v;
+            acc = ((have >> c) & 1u) ? a : acc;     // wave-uniform, as the pipelined kernels skip such a view
+        }
+        // view fusion (project_layer.py:96-99): den = #views seeing the voxel + 1e-6; NaN sample position -> 0
+        const float den = (float)(mymask & 0x7fffffffu) + 1e-6f;
+        const float rden = (mymask & 0x80000000u) ? 0.0f : 1.0f / den;
+        out = fuse_rcp(acc, den, rden);
+    } else if (grids && inb) {                      // skipped sample: zeros (project_layer.py:48,51,54)
+        float *gp = grids + ((size_t)b * g.N + n) * 3;
+        gp[0] = 0.0f; gp[1] = 0.0f; gp[2] = 0.0f;
+    }
+    if (!inb) return;
+    if (OUTCL) {
+        Store4<float>::store_nt(dst, make_float4(out, 0.0f, 0.0f, 0.0f));
+    } else {
+        dst[0] = out;
+        for (int j = 1; j < g.J; ++j) dst[(size_t)j * g.sJ] = 0.0f;
+    }
+}
+
+// ------------------------------------------------------------------------------------------
 // "brick" kernel: the same per-wave pipeline, but a wave owns a 4x4x4 block of voxels instead of 64
 // consecutive ones, and a workgroup is a stack of `zw` such bricks along z.
 //
@@ -1861,26 +1985,34 @@ static int launch_nhwc_wide(const Views &v, const float *cam, const float *cente
     }
 }
 
+// Default chunk size of the XCD tile map for 64-voxel tiles (launch_nhwc, launch_one): 2-4 chunks per serving XCD -
+// compact enough that an XCD's L2 sees a fraction of each view (fabric reads 93 MB -> 81 MB on the bench workload), fine
+// enough to balance visibility
+static int default_xcd_chunk(const Geom &g)
+{
+    const int xps = (g.B <= 8 && (8 % g.B) == 0) ? 8 / g.B : 1;
+    const int t64 = (g.N + 63) / 64;
+    int k = 1;
+    while (k * 2 * xps * 2 <= t64) k *= 2;
+    return k;
+}
+
+// Default chunk order: centre of the volume first (cheap edge tiles form the tail) when a sample is spread over >= 4 XCDs
+// (-2.5 % at B = 1); with 2 XCDs per sample it buys no time and costs L2 locality (HBM-side reads 75 -> 92 MB on the bench
+// workload), so the plain sweep stays there
+static int default_xcd_order(const Geom &g) { return g.B <= 2 ? 1 : 0; }
+
 // io: bit 0 = packed heat-maps are bf16, bit 1 = cubes are bf16
 static int launch_nhwc(const Views &v, int Jp, const float *cam, const float *centers, const uint8_t *valid,
                        float *cubes, float *grids, const Geom &g_in, int variant, bool out_cl, int io, hipStream_t s)
 {
     Geom g = g_in;
-    // chunk order: centre of the volume first (cheap edge tiles form the tail) when a sample is spread over >= 4 XCDs
-    // (-2.5 % at B = 1); with 2 XCDs per sample it buys no time and costs L2 locality (HBM-side reads 75 -> 92 MB on
-    // the bench workload), so the plain sweep stays there.  Tuning bit 21 forces the sweep.
-    g.xcd_order = ((!((variant >> 21) & 1) && g.B <= 2) ? 1 : 0) | ((variant & 256) ? 2 : 0);
-    if ((variant >> 17) & 15) {
+    // chunk order and size: the defaults above; tuning bit 21 forces the plain sweep, bits 17-20 a chunk size
+    g.xcd_order = ((variant >> 21) & 1 ? 0 : default_xcd_order(g)) | ((variant & 256) ? 2 : 0);
+    if ((variant >> 17) & 15)
         g.xcd_chunk = 1 << (((variant >> 17) & 15) - 1);   // tuning bits 17-20: log2(K)+1
-    } else {
-        // default: 2-4 chunks per serving XCD - compact enough that an XCD's L2 sees a fraction of each
-        // view (fabric reads 93 MB -> 81 MB on the bench workload), fine enough to balance visibility
-        const int xps = (g.B <= 8 && (8 % g.B) == 0) ? 8 / g.B : 1;
-        const int t64 = (g.N + 63) / 64;
-        int k = 1;
-        while (k * 2 * xps * 2 <= t64) k *= 2;
-        g.xcd_chunk = k;
-    }
+    else
+        g.xcd_chunk = default_xcd_chunk(g);
     if (Jp == WIDE_PS) {
         // 17..32 channels (see launch_nhwc_wide): planar results of the default kernels; no channels-last result, no pass
         // mask, no z-spectrum, and the pipelined kernels' limits on the image (2x2 block, 24-bit pixel indices)
@@ -1908,6 +2040,48 @@ static int launch_nhwc(const Views &v, int Jp, const float *cam, const float *ce
     default: return SP3D_EUNSUPPORTED;
     }
     return rc ? rc : launch_status();
+}
+
+// SP3D_HM_ONE_CHANNEL (include/sp3d.h): every refusal before any launch.  `layout` = hm_layout without its flag bits;
+// g.J = channels written (1, or 4 = value + three zero channels), g.sB.. = planar result strides (dense or strided).
+static int launch_one(const Views &v, int layout, int Jp, const float *cam, const float *centers, const uint8_t *valid,
+                      float *cubes, float *grids, const Geom &g_in, bool out_cl, int io, hipStream_t s)
+{
+    if (layout != SP3D_LAYOUT_PLANAR && layout != SP3D_LAYOUT_NHWC) return SP3D_EINVAL;
+    if (Jp < 1) return SP3D_EINVAL;
+    if (io || g_in.pass_mask) return SP3D_EUNSUPPORTED;
+    if (!(g_in.J == 4 || (g_in.J == 1 && !out_cl))) return SP3D_EUNSUPPORTED;
+    if (g_in.w < 2 || g_in.h < 2 || (int64_t)g_in.h * g_in.w > (1 << 24)) return SP3D_EUNSUPPORTED;
+    if (out_cl && ((uintptr_t)cubes & 15)) return SP3D_EUNSUPPORTED;
+    const int64_t px = layout == SP3D_LAYOUT_NHWC ? Jp : 1, row = (int64_t)g_in.w * px;
+    const int64_t sample = layout == SP3D_LAYOUT_NHWC ? (int64_t)g_in.h * row : (int64_t)Jp * g_in.h * g_in.w;
+    // 24-bit multiplies form the tap offset, a 32-bit byte offset addresses it
+    if (row >= (1 << 24) || (int64_t)g_in.h * row * 4 > (int64_t)0x7fffffff) return SP3D_EUNSUPPORTED;
+    Geom g = g_in;
+    // the pipe kernel's tile map: 64-voxel tiles dealt to the XCDs that serve a sample in chunks
+    g.xcd_order = default_xcd_order(g);
+    g.xcd_chunk = default_xcd_chunk(g);
+    const int ptiles = (g.N + 63) / 64;
+    set_xcd_fields(g, ptiles);
+    dim3 grid(xcd_grid_blocks(g.B, ptiles, g.xcd_chunk)), block(64);
+#define SP3D_ONE(VT_, CS_) do { \
+        if (out_cl) hipLaunchKernelGGL((unproject_one_kernel<VT_, CS_, true>), grid, block, 0, s, v, cam, centers, valid, cubes, grids, g, (long long)sample, (int)row, (int)px); \
+        else hipLaunchKernelGGL((unproject_one_kernel<VT_, CS_, false>), grid, block, 0, s, v, cam, centers, valid, cubes, grids, g, (long long)sample, (int)row, (int)px); \
+    } while (0)
+    switch (g.V) {
+    case 1: SP3D_ONE(1, 4); break;
+    case 2: SP3D_ONE(2, 4); break;
+    case 3: SP3D_ONE(3, 4); break;
+    case 4: SP3D_ONE(4, 4); break;
+    case 5: SP3D_ONE(5, 4); break;
+    case 6: SP3D_ONE(6, 4); break;
+    case 7: case 8: SP3D_ONE(8, 4); break;
+    case 9: case 10: SP3D_ONE(10, 8); break;
+    case 11: case 12: SP3D_ONE(12, 8); break;
+    default: SP3D_ONE(16, 8); break;
+    }
+#undef SP3D_ONE
+    return launch_status();
 }
 
 } // namespace sp3d
@@ -2020,6 +2194,7 @@ extern "C" int sp3d_unproject_fwd_indexed(const float *const *hm_views, int hm_l
     const int tiles = (g.N + TILE - 1) / TILE;
     const bool out_cl = (hm_layout & SP3D_OUT_CHANNELS_LAST) != 0;
     const int io = ((hm_layout & SP3D_HM_BF16) ? 1 : 0) | ((hm_layout & SP3D_OUT_BF16) ? 2 : 0);
+    if (hm_layout & SP3D_HM_ONE_CHANNEL) return launch_one(v, hm_layout & 0xff, Jp, cam, centers, valid, cubes, grids, g, out_cl, io, s);
     hm_layout &= 0xff;
     if (hm_layout == SP3D_LAYOUT_PLANAR) {
         if (out_cl || io) return SP3D_EUNSUPPORTED;
@@ -2047,7 +2222,8 @@ extern "C" int sp3d_unproject_fwd_strided(const float *const *hm_views, int hm_l
     if (!cam || !centers || !valid || !cubes || !out_strides) return SP3D_ENULL;
     const bool out_cl = (hm_layout & SP3D_OUT_CHANNELS_LAST) != 0;
     const int io = ((hm_layout & SP3D_HM_BF16) ? 1 : 0) | ((hm_layout & SP3D_OUT_BF16) ? 2 : 0);
-    if ((hm_layout & 0xff) != SP3D_LAYOUT_NHWC || out_cl || w < 2 || h < 2) return SP3D_EUNSUPPORTED;
+    const bool one = (hm_layout & SP3D_HM_ONE_CHANNEL) != 0;       // reads either layout (launch_one)
+    if ((!one && (hm_layout & 0xff) != SP3D_LAYOUT_NHWC) || out_cl || w < 2 || h < 2) return SP3D_EUNSUPPORTED;
     const int64_t sB = out_strides[0], sJ = out_strides[1], sX = out_strides[2], sY = out_strides[3];
     // the planes must not overlap and must fit 32-bit in-plane offsets
     if (sY < Z || sX < (int64_t)Y * sY || sJ < (int64_t)X * sX || sB < (int64_t)J * sJ) return SP3D_EINVAL;
@@ -2061,6 +2237,7 @@ extern "C" int sp3d_unproject_fwd_strided(const float *const *hm_views, int hm_l
     rc = load_views(v, hm_views, V);
     if (rc) return rc;
     g.vec4 = ((g.dense || ((sY | sX | sJ | sB) & 3) == 0) && ((uintptr_t)cubes & 15) == 0) ? 1 : 0;
+    if (one) return launch_one(v, hm_layout & 0xff, Jp, cam, centers, valid, cubes, nullptr, g, false, io, (hipStream_t)stream);
     return launch_nhwc(v, Jp, cam, centers, valid, cubes, nullptr, g, default_variant(g, false), false, io, (hipStream_t)stream);
 }
 
@@ -2158,7 +2335,7 @@ extern "C" int sp3d_unproject_fwd_train(const float *const *hm_views, int hm_lay
     int rc = make_geom(g, P, V, J, h, w, X, Y, Z, grid_size, W_in, H_in);
     if (rc) return rc;
     if (!cam || !centers || !valid || !cubes || !pass_mask) return SP3D_ENULL;
-    if ((hm_layout & 0xff) != SP3D_LAYOUT_NHWC || (hm_layout & (SP3D_HM_BF16 | SP3D_OUT_BF16)) || w < 2 || h < 2)
+    if ((hm_layout & 0xff) != SP3D_LAYOUT_NHWC || (hm_layout & (SP3D_HM_BF16 | SP3D_OUT_BF16 | SP3D_HM_ONE_CHANNEL)) || w < 2 || h < 2)
         return SP3D_EUNSUPPORTED;
     g.sample_of = sample_of;
     g.pass_mask = pass_mask;

@@ -74,7 +74,7 @@ class CuboidProposalNet(nn.Module):
 
     def forward(self, all_heatmaps, meta, flip_xcoords=None):
         if self.rootnet_roothm:                                   # root-joint channel only (:103-108)
-            hms = [a[:, self.root_id:self.root_id + 1].contiguous() for a in all_heatmaps]
+            hms = [a[:, self.root_id:self.root_id + 1] for a in all_heatmaps]      # a view: read in place with ProjectLayer.one_channel, copied otherwise
         else:
             hms = all_heatmaps
         planar = self.v2v_net.wants_planar_input() and hms[0].is_cuda      # FFT opening conv: plain J-channel cubes

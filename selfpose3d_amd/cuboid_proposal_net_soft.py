@@ -75,7 +75,7 @@ class CuboidProposalNetSoft(nn.Module):
 
     def get_grid_centres(self, all_heatmaps, meta, flip_xcoords=None):
         if self.rootnet_roothm:
-            hms = [a[:, self.root_id:self.root_id + 1].contiguous() for a in all_heatmaps]
+            hms = [a[:, self.root_id:self.root_id + 1] for a in all_heatmaps]      # a view: read in place with ProjectLayer.one_channel, copied otherwise
         else:
             hms = all_heatmaps
         root_cubes = self._root_cubes(hms, meta, flip_xcoords)

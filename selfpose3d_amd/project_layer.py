@@ -93,6 +93,54 @@ def _packed_source(hms: Sequence[torch.Tensor], jp: int, dtype: torch.dtype):
     return base
 
 
+def one_channel_source(hms: Sequence[torch.Tensor]):
+    """``list[V] of (B,1,h,w)`` fp32 tensors that each are ONE channel of a wider tensor -> ``(layout, Jp)`` as the
+    one-channel kernel addresses it (``SP3D_HM_ONE_CHANNEL``, include/sp3d.h), else ``None``.  Decided from shapes, dtypes
+    and strides alone (no device access; CPU tensors classify the same way):
+
+      * pixel stride 1, row stride w: a channel plane of a planar (B,Jp,h,w) tensor -> ``(LAYOUT_PLANAR, Jp)``, Jp = sample
+        stride / (h*w) (a contiguous (B,1,h,w) tensor is the case Jp = 1);
+      * pixel stride PS > 1, row stride w*PS, sample stride h*w*PS: a channel of a channels-last (B,h,w,PS) buffer (a slice
+        of ``nhwc_heatmap_views``) -> ``(LAYOUT_NHWC, PS)``.
+
+    A dimension of size 1 carries an arbitrary stride, so at B = 1 the sample stride is evidence of nothing and is not
+    looked at (planar: Jp = 1, the kernel never leaves sample 0).  ``None`` for anything else: J != 1, another dtype,
+    a stride of 0 (expanded tensors) or below 0, heat-maps under 2x2 or over 2^24 pixels, a row stride that is not
+    w x pixel stride, a sample stride that fits neither form, views of different form."""
+    if len(hms) == 0:
+        return None
+    first = None
+    for t in hms:
+        if t.dim() != 4 or t.dtype != torch.float32 or t.shape != hms[0].shape:
+            return None
+        B, J, h, w = t.shape
+        if J != 1 or B < 1 or h < 2 or w < 2 or h * w > (1 << 24):
+            return None
+        sB, _, sH, sW = t.stride()
+        if sW < 1 or sH != w * sW or (B > 1 and sB < 1):
+            return None
+        if sW == 1:
+            if B == 1:
+                form = (_lib.LAYOUT_PLANAR, 1)
+            elif sB % (h * w) == 0:
+                form = (_lib.LAYOUT_PLANAR, sB // (h * w))
+            else:
+                return None
+        else:
+            if B > 1 and sB != h * w * sW:
+                return None
+            # the limits launch_one (csrc/sp3d_unproject.hip) answers SP3D_EUNSUPPORTED for - 32-bit byte offsets, 24-bit
+            # multiplies - so that such a buffer keeps the packed path instead of raising
+            if h * w * sW * 4 > 0x7fffffff or w * sW >= (1 << 24):
+                return None
+            form = (_lib.LAYOUT_NHWC, sW)
+        if first is None:
+            first = form
+        elif form != first:
+            return None
+    return first
+
+
 class _UnprojectFn(torch.autograd.Function):
     """autograd seam: gradient flows to the heat-maps only."""
 
@@ -103,6 +151,20 @@ class _UnprojectFn(torch.autograd.Function):
         B = int(centers.shape[0])                 # number of output cubes (== batch unless `sample_of` is given)
         hms = [x.detach() for x in heatmaps]
         io = layer.io_dtype
+        # one channel of a wider tensor (the root-joint map of the ROOTNET_ROOTHM root nets): read where it lies by the
+        # one-channel kernel - no slice copy, no re-tiling pass, no pack-cache entry.  A heat-map gradient keeps the packed
+        # path below (its backward needs the pass mask).
+        one = one_channel_source(hms) if (layer.one_channel and mode == "nhwc" and io == torch.float32 and J == 1
+                                          and not any(ctx.needs_input_grad[12:])) else None
+        if one is not None:
+            cubes, grids = _lib.unproject_fwd(hms, one[0], one[1], cam, centers, valid, B, 4 if pad_channels else 1, h, w,
+                                              cube_size, grid_size, layer.img_size, want_grids, channels_last=channels_last,
+                                              sample_of=sample_of, out=out, one_channel=True)
+            # nothing is saved for backward: no input of this call requires a gradient, so backward() is never entered
+            if grids is None:
+                grids = torch.empty(0, device=cubes.device)
+            ctx.mark_non_differentiable(grids)
+            return cubes, grids
         source = _packed_source(heatmaps, layer.jp_for(J), io) if mode == "nhwc" else None
         if io == torch.float32 and source is None:
             hms = [x if (x.is_contiguous() and x.dtype == torch.float32) else x.contiguous().float() for x in hms]
@@ -187,6 +249,10 @@ class ProjectLayer(nn.Module):
         self._static_cam = None       # see static_camera_table()
         # gradient scatter in 64-bit fixed point (bit-identical run to run) instead of fp32 atomics; SP3D_BWD_DETERMINISTIC=1
         self.deterministic_backward = os.environ.get("SP3D_BWD_DETERMINISTIC", "0") not in ("", "0")
+        # opt-in (SP3D_ONE_CHANNEL=1 / ``one_channel = True``): a (B,1,h,w) heat-map list that is one channel of a wider
+        # tensor goes through the one-channel kernel, read in place (one_channel_source), instead of slice copy + re-tile +
+        # packed kernel.  Same bits either way; off until tools/bench_roothm.py has recorded that it is faster
+        self.one_channel = os.environ.get("SP3D_ONE_CHANNEL", "0") not in ("", "0")
 
     @contextlib.contextmanager
     def static_camera_table(self, table: torch.Tensor):
