@@ -243,6 +243,9 @@ int sp3d_fixed_to_float(const int64_t *acc, float *out, const float *scale, int6
  * core.proposal.nms + ProposalLayer.get_real_loc (lib/core/proposal.py:28-48,
  * lib/models/cuboid_proposal_net.py:42-52): 3x3x3 local-max mask, top-k over the flat volume
  * (ties: larger value, then LOWER flat index), unravel, index -> mm.
+ * The order is total: value descending with -0 == +0, then lower flat index; vals holds the product (x == max) * x as computed
+ * (-0.0 stays -0.0).  A NaN voxel of that product is never a candidate, wherever it lies - a deviation from torch.topk, which
+ * ranks NaN first; a slot without a candidate (k > the number of non-NaN voxels) is value 0, index (0,0,0).
  *   root_cubes (B,X,Y,Z)   vals (B,k) fp32   idx (B,k,3) int64   locs (B,k,3) fp32 mm or NULL
  *   workspace  device scratch of sp3d_nms_topk_workspace_bytes(...) bytes
  */
