@@ -90,6 +90,7 @@ SIGNATURES = {                                  # include/sp3d.h, in the header'
 }
 TUNING_SIGNATURES = {                           # selfpose3d_amd/csrc/sp3d_tuning.h: measurement builds only, declared when present
     "sp3d_unproject_fwd_variant": "i: p i ppppp iiiiiiii p iii p",
+    "sp3d_unproject_fwd_plan": "i: iii p iiiiiiiii pppp",
     "sp3d_debug_set_timeline": "i: p",
     "sp3d_debug_stamp": "i: pp",
 }
@@ -292,6 +293,34 @@ def unproject_fwd(views: Sequence[torch.Tensor], layout: int, jp: int, cam: torc
                                             int(img_size[1]), int(variant) | (0x1000000 if channels_last else 0), _stream(dev))
     check(rc, "sp3d_unproject_fwd")
     return cubes, grids
+
+
+PLAN_ENTRIES = ("indexed", "strided", "train", "zdft", "variant")      # SP3D_PLAN_* (csrc/sp3d_tuning.h)
+PLAN_FIELDS = ("workgroups", "block", "lds", "nscalars", "s0", "s1", "s2", "s3", "J", "xcd_chunk", "xcd_order", "xm_mode", "xm_log2xps",
+               "xm_log2K", "xm_rows", "xm_tiles", "xm_magic_tiles", "bk_nxy", "bk_nby", "bk_magic_nxy", "bk_magic_nby", "blk_log2py",
+               "blk_w", "blk_h", "blk_nbx", "blk_nzc", "blk_magic_wh", "blk_magic_h", "view_off", "out_off", "grids")
+PLAN_TUNING = ("unroll", "no_xcd_map", "pipe", "one_wave", "brick", "brick_own_wg", "z_fastest", "view_sync", "ballast", "forced_chunk",
+               "plain_sweep", "chunk_map")
+
+
+def unproject_fwd_plan(entry: str, layout: int, jp: int, B: int, V: int, J: int, h: int, w: int, cube_size, variant: int = 0,
+                       out_strides=None):
+    """Measurement only, no GPU: what the forward unprojection would launch for a request given as shapes
+    (sp3d_unproject_fwd_plan) -> (rc, launches, tuning): per launch a dict of its kernel ``name`` and PLAN_FIELDS (magic
+    numbers as unsigned), and the decoded tuning as a dict of PLAN_TUNING; ``launches`` is empty when rc is a refusal."""
+    lib = load()
+    names = C.create_string_buffer(2 * 96)
+    fields, tuning, n = (C.c_int32 * (2 * len(PLAN_FIELDS)))(), (C.c_int32 * len(PLAN_TUNING))(), C.c_int32(0)
+    st = (C.c_int64 * 4)(*[int(v) for v in out_strides]) if out_strides is not None else None
+    X, Y, Z = (int(c) for c in cube_size)
+    rc = lib.sp3d_unproject_fwd_plan(PLAN_ENTRIES.index(entry), layout, jp, st, B, V, J, h, w, X, Y, Z, int(variant), names, fields,
+                                     tuning, C.byref(n))
+    launches = []
+    for i in range(n.value if rc == 0 else 0):
+        f = fields[i * len(PLAN_FIELDS):(i + 1) * len(PLAN_FIELDS)]
+        launches.append(dict(zip(PLAN_FIELDS, (v & 0xFFFFFFFF if "magic" in k else v for k, v in zip(PLAN_FIELDS, f))),
+                             name=names.raw[i * 96:(i + 1) * 96].split(b"\0")[0].decode()))
+    return rc, launches, dict(zip(PLAN_TUNING, tuning))
 
 
 def unproject_bwd(hms: Sequence[torch.Tensor], cam, centers, valid, grad_cubes: torch.Tensor, cube_size, grid_size,

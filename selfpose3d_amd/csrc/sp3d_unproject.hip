@@ -20,9 +20,11 @@
 //                            g * w_tap with hardware fp32 atomics.
 #include <type_traits>
 
+#include <stdio.h>
 #include <string.h>
 #include "sp3d_device.h"
 #include "sp3d_proj_pk.h"
+#include "sp3d_tuning.h"
 #include "sp3d_twiddles.h"
 
 namespace sp3d {
@@ -151,7 +153,7 @@ __global__ __launch_bounds__(256) void pack_nhwc_kernel(Views hm, float *__restr
     const int pc = p < HW ? p : HW - 1;
     float vals[JP];
     // channel index clamped too (planes j >= J re-read plane J - 1 and are zeroed below): straight-line code, no branch between
-    // the loads - behind a wave-uniform `j < J` branch the bf16 variant still waited for every load before widening it
+    // the loads - behind a wave-uniform `j < J` branch the bf16 form still waited for every load before widening it
     if constexpr (sizeof(TI) == 2) {
         uint32_t raw[JP];
 #pragma unroll
@@ -648,7 +650,7 @@ __device__ __forceinline__ void pipe_tile(const Views &hm, const float *__restri
 // NW = waves per workgroup (waves are independent; NW only sets the dispatch granularity)
 // TI / TO: storage type of the packed heat-maps / of the cubes (float or bf16_t); math is fp32.
 // PS: elements per packed pixel (the buffer's channel stride); JP channels from the pixel start are gathered.  PS > JP is one
-// channel group of a wider pixel (launch_nhwc_wide: `hm` then points at the group's first channel).
+// channel group of a wider pixel (resolve_fwd: `hm` then points at the group's first channel).
 template <int JP, bool XCD, int NW, bool OUTCL, typename TI = float, typename TO = float, int PS = JP>
 __global__ __launch_bounds__(64 * NW) void unproject_pipe_kernel(Views hm, const float *__restrict__ cam,
                                                              const float *__restrict__ centers,
@@ -684,7 +686,7 @@ __global__ __launch_bounds__(64 * NW) void unproject_pipe_kernel(Views hm, const
 // Latency (at B = 1 the root grid is 2 000 waves on 1 024 SIMDs): the views are taken in chunks of CS; a chunk's
 // records stay in registers, all of its tap loads are issued back to back, and the next chunk is projected while
 // they are in flight.  The FMAs run last, in view order.  VT >= V is the number of view slots the kernel is unrolled
-// for (launch_one: V itself up to 6, then 8, 10, 12, 16), CS = 4 up to 8 views and 8 above.
+// for (resolve_one: V itself up to 6, then 8, 10, 12, 16), CS = 4 up to 8 views and 8 above.
 //
 // Result: planar with g.J = 1 or 4 channels (dense or strided; channels 1-3 zeros), or channels-last (B,X,Y,Z,4) as
 // one 16-byte store {v, 0, 0, 0} per lane.
@@ -836,8 +838,6 @@ constexpr int BR = 4;
 // one whole 128-byte line.  `cubes` then points at that spectrum.  Deletes the cubes' write + re-read (2 x 32.8 MB at
 // B = 4) and one launch from the root-net step; cfft2d_88_kernel un-tiles while it loads a plane into LDS.
 constexpr int ZDZ = 20, ZDSZ = 28;
-constexpr int SP3D_VARIANT_ZD = 1 << 24;        // launch_nhwc `variant` bit: brick stacks emit the z-spectrum
-constexpr int SP3D_VARIANT_CHUNKS = 1 << 22;    // launch_nhwc `variant` bit: round-5 chunk map of the bricks instead of blocks / octants
 template <int JP, bool OUTCL, typename TI = float, typename TO = float, bool ZD = false, int PS = JP>
 __global__ __launch_bounds__(512, ZD ? SP3D_ZD_MINW : SP3D_BRICK_MINW) void unproject_brick_kernel(Views hm, const float *__restrict__ cam,
                                                                 const float *__restrict__ centers,
@@ -855,7 +855,7 @@ __global__ __launch_bounds__(512, ZD ? SP3D_ZD_MINW : SP3D_BRICK_MINW) void unpr
     if (!(g.xcd_order & 2)) {   // default (round 3): z slowest - consecutive workgroups sweep (y, x) inside one z-layer of bricks
         // and an XCD's chunk is a z-slab: -3 % on all three grids (profiles/r03_ab_zslab.json)
         udiv_magic((uint32_t)wg, (uint32_t)g.bk_nxy, g.bk_magic_nxy, zc, t);
-    } else {                    // bit 8 of the tuning `variant`: round 2's order, z fastest
+    } else {                    // tuning (z-fastest order): round 2's order, z fastest
         zc = wg % nzc; t = wg / nzc;
     }
     int bx, by;
@@ -1722,278 +1722,199 @@ static int launch_status()
     return e == hipSuccess ? SP3D_OK : (int)e;
 }
 
-// variant: bits[1:0] voxels in flight per lane (0:1, 1:2, 2:4); bit 2: disable the XCD-aware tile map;
-// bit 3: per-wave software-pipelined kernel (unproject_pipe_kernel); bit 4: one wave per workgroup
-// default: pipelined kernel; XCD-aware tile map only when several samples share the chip
-// Default kernel per result layout and grid (profiles/r02_ab_brick.json, same-box A/B, bit-identical results):
-//   channels-last result     4x4x4 bricks, one brick per workgroup (120): -5 % on the root grid, -20 % on 64^3 person
-//                            cubes, -30 % on the 160x160x40 grid - fewer distinct 128-B lines per wave-load
-//   planar result, Z % 32==0 brick stacks of 8 (56): the workgroup store writes whole 128-B z-runs (64^3 cubes: -20 %)
-//   planar result, other Z   64 consecutive voxels per wave (24): a 20- or 40-voxel z-run does not fill store lines from a
-//                            brick stack, and the stack's barrier costs more than the gather saves (root grid: +30 %)
-static int default_variant(const Geom &g, bool out_cl)
-{
-    if (g.w < 2 || g.h < 2) return 24;
-    if (out_cl) return 120;
-    return (g.Z % 32 == 0) ? 56 : 24;
-}
-
-// workgroup geometry of the brick kernels (4x4x4 voxels per wave, a z-stack of `zw` bricks per workgroup)
-struct BrickPlan {
-    Geom gb;
-    int wgs, nby, nzc, zw, block_grid;
-    size_t blds;
+// ------------------------------------------------------------------------------------------
+// Forward unprojection, host side: request (fwd_request) -> resolve_fwd() -> launch records -> launch_fwd().
+// ------------------------------------------------------------------------------------------
+// The tuning word of sp3d_unproject_fwd_variant, decoded: one field per bit group documented in sp3d_tuning.h (the only
+// place the word's layout is written down).  All int, no padding: tunings compare with memcmp.
+struct FwdTuning {
+    int unroll;          // tile kernel: voxels in flight per lane (1, 2, 4)
+    int no_xcd_map;      // tile / pipe kernels: plain blockIdx order instead of the XCD-aware tile map
+    int pipe;            // per-wave software-pipelined kernel (unproject_pipe_kernel)
+    int one_wave;        // pipe kernel: one wave per workgroup instead of four
+    int brick;           // 4x4x4 voxels per wave, a z-stack of bricks per workgroup
+    int brick_own_wg;    // every brick its own workgroup
+    int z_fastest;       // z-fastest chunk order (xcd_order bit 1); the bricks keep the chunk map
+    int view_sync;       // round-5 L1-residency experiment (measurement only): view-synchronous brick workgroups
+    int ballast;         // same experiment: n * 20 KB of unused LDS per brick workgroup caps the workgroups resident on a CU
+    int forced_chunk;    // log2(tiles per XCD chunk) + 1; 0: the default chunk size
+    int plain_sweep;     // chunks in sweep order instead of centre first
+    int chunk_map;       // bricks: round-5 chunk map instead of blocks / octants
 };
 
-static void plan_bricks(const Geom &g, int variant, int wlds, BrickPlan &p)
+static FwdTuning decode_tuning(int variant)
 {
-    const int nbx = (g.X + BR - 1) / BR, nby = (g.Y + BR - 1) / BR, nwz = (g.Z + BR - 1) / BR;
-    int nzc = (nwz + 7) / 8, zw = (nwz + nzc - 1) / nzc;
-    if (variant & 64) { zw = 1; nzc = nwz; }                  // tuning: every brick its own workgroup
-    const int wgs = nbx * nby * nzc;
-    Geom gb = g;
-    {   // 2-4 chunks of consecutive workgroups (x-slabs of the volume) per serving XCD
-        const int xps = (g.B <= 8 && (8 % g.B) == 0) ? 8 / g.B : 1;
-        int k = 1;
-        while (k * 2 * xps * 2 <= wgs) k *= 2;
-        if ((variant >> 17) & 15) k = 1 << (((variant >> 17) & 15) - 1);
-        gb.xcd_chunk = k;
-    }
-    set_xcd_fields(gb, wgs);
-    set_brick_fields(gb, nbx * nby, nby);
-    // default since round 6 (B in {1, 2, 4}): one block of brick columns per XCD - octants at B = 1, quadrants at B = 2,
-    // halves at B = 4 - instead of round-robin chunks; same results, L2 fills 138 -> 60 MB on the 160x160x40 grid,
-    // 75 -> 56 MB on the root grid at B = 4 (profiles/r06_pmc_blocks.json).  Tuning bit 22 restores the chunk map.
-    p.block_grid = (variant & SP3D_VARIANT_CHUNKS) || (variant & 256) ? 0 : set_block_fields(gb, nbx, nby, nzc);
-    p.blds = (size_t)zw * wlds * sizeof(float);
-    // round-5 L1-residency experiment (measurement only): tuning bit 10 = view-synchronous workgroups (only when every
-    // wave of every workgroup lies inside the volume, so that all of them reach the per-view barrier)
-    if (((variant >> 10) & 1) && nwz % zw == 0 && nzc * zw == nwz) gb.xcd_order |= 4;
-    p.gb = gb; p.wgs = wgs; p.nby = nby; p.nzc = nzc; p.zw = zw;
+    FwdTuning t;
+    t.unroll = (variant & 3) == 0 ? 1 : ((variant & 3) == 2 ? 4 : 2);
+    t.no_xcd_map = (variant >> 2) & 1;
+    t.pipe = (variant >> 3) & 1;
+    t.one_wave = (variant >> 4) & 1;
+    t.brick = (variant >> 5) & 1;
+    t.brick_own_wg = (variant >> 6) & 1;
+    t.z_fastest = (variant >> 8) & 1;
+    t.view_sync = (variant >> 10) & 1;
+    t.ballast = (variant >> 11) & 7;
+    t.forced_chunk = (variant >> 17) & 15;
+    t.plain_sweep = (variant >> 21) & 1;
+    t.chunk_map = (variant >> 22) & 1;
+    return t;
 }
 
-template <int JP>
-static int launch_nhwc_jp(const Views &v, const float *cam, const float *centers, const uint8_t *valid, float *cubes,
-                          float *grids, const Geom &g, int variant, bool out_cl, int io, hipStream_t s)
+// The three defaults.  All: pipelined, one wave per workgroup, XCD-aware tile map, centre-first chunks of the default size.
+enum FwdDefault { FWD_PIPE, FWD_BRICK_STACKS, FWD_BRICK_EACH };
+static FwdTuning default_tuning(FwdDefault d)
 {
-    const int tiles = (g.N + TILE - 1) / TILE;
-    const int total = tiles * g.B;
-    const size_t lds = (size_t)(JP * OSTR + 2 * g.V * TILE + TILE) * sizeof(float);
-    const bool xcd = !(variant & 4);
-    dim3 grid(xcd ? xcd_grid_blocks(g.B, tiles, g.xcd_chunk) : total), block(TILE);
-    if (variant & 32) {      // brick kernel: 4x4x4 voxels per wave, a z-stack of bricks per workgroup
-        constexpr int WLDS = (JP * WOSTR > WREC) ? JP * WOSTR : WREC;
-        BrickPlan bp;
-        plan_bricks(g, variant, WLDS, bp);
-        Geom &gb = bp.gb;
-        const int wgs = bp.wgs, nby = bp.nby, nzc = bp.nzc, zw = bp.zw, block_grid = bp.block_grid;
-        size_t blds = bp.blds;
-        // (round-5 L1-residency experiment, measurement only) tuning bits 11-13 = n: n * 20 KB of unused LDS per
-        // workgroup, which caps the workgroups resident on a CU
-        const int ballast = (variant >> 11) & 7;
-        if (ballast) {
-            blds += (size_t)ballast * 20480;
-            if (blds > 65536) {
-                const void *fn = out_cl ? reinterpret_cast<const void *>(unproject_brick_kernel<JP, true, float, float>)
-                                        : reinterpret_cast<const void *>(unproject_brick_kernel<JP, false, float, float>);
-                const hipError_t ea = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)blds);
-                if (ea != hipSuccess) return (int)ea;
-            }
-        }
-        dim3 bgrid(block_grid ? block_grid : xcd_grid_blocks(gb.B, wgs, gb.xcd_chunk)), bblock(64 * zw);
-        if (variant & SP3D_VARIANT_ZD) {   // the stack's cubes leave as their z-spectrum (sp3d_unproject_fwd_zdft)
-            if constexpr (JP == 16) {
-                if (io || out_cl || grids || g.Z != ZDZ || nzc != 1 || zw != ZDZ / BR || (g.X % BR) || (g.Y % BR) || g.pass_mask)
-                    return SP3D_EUNSUPPORTED;
-                hipLaunchKernelGGL((unproject_brick_kernel<16, false, float, float, true>), bgrid, bblock, blds, s, v, cam, centers,
-                                   valid, cubes, grids, gb, wgs, nby, nzc, zw);
-                return SP3D_OK;
-            } else {
-                return SP3D_EUNSUPPORTED;
-            }
-        }
-#define SP3D_BRICK(CL_, TI_, TO_) \
-    hipLaunchKernelGGL((unproject_brick_kernel<JP, CL_, TI_, TO_>), bgrid, bblock, blds, s, v, cam, centers, valid, cubes, grids, gb, wgs, nby, nzc, zw)
-        if ((io & 1) && JP == 16 && !((variant >> 9) & 1)) {
-            // bf16 heat-maps: two lanes per pixel (tuning bit 9: keep the four-lane kernel below, for A/B)
-#define SP3D_BRICK_H(CL_, TO_) \
-    hipLaunchKernelGGL((unproject_brick_h_kernel<CL_, TO_>), bgrid, bblock, blds, s, v, cam, centers, valid, cubes, grids, gb, wgs, nby, nzc, zw)
-            if (io & 2) { if (out_cl) SP3D_BRICK_H(true, bf16_t); else SP3D_BRICK_H(false, bf16_t); }
-            else { if (out_cl) SP3D_BRICK_H(true, float); else SP3D_BRICK_H(false, float); }
+    FwdTuning t = {};
+    t.unroll = t.pipe = t.one_wave = 1;
+    t.brick = d != FWD_PIPE;
+    t.brick_own_wg = d == FWD_BRICK_EACH;
+    return t;
+}
+// Default kernel per result layout and grid (profiles/r02_ab_brick.json, same-box A/B, bit-identical results):
+//   channels-last result     4x4x4 bricks, one brick per workgroup: -5 % on the root grid, -20 % on 64^3 person
+//                            cubes, -30 % on the 160x160x40 grid - fewer distinct 128-B lines per wave-load
+//   planar result, Z % 32==0 brick stacks of 8: the workgroup store writes whole 128-B z-runs (64^3 cubes: -20 %)
+//   planar result, other Z   64 consecutive voxels per wave: a 20- or 40-voxel z-run does not fill store lines from a
+//                            brick stack, and the stack's barrier costs more than the gather saves (root grid: +30 %)
+static FwdTuning default_tuning(const Geom &g, bool out_cl)
+{
+    return default_tuning(out_cl ? FWD_BRICK_EACH : (g.Z % 32 == 0 ? FWD_BRICK_STACKS : FWD_PIPE));
+}
+
+// what a forward entry point asks for; `g` carries J, the image, the grid, the result strides and the pass mask
+struct FwdRequest {
+    int layout, Jp;      // SP3D_LAYOUT_* without the flag bits; channels (pixel stride) of a packed pixel
+    int io;              // bit 0 = the heat-maps are bf16, bit 1 = the cubes are bf16
+    bool one, out_cl, zd, out_aligned;   // one-channel read; channels-last result; z-spectrum result; result 16-byte aligned
+    Geom g;
+};
+
+// one kernel launch.  scalar[0..nscalars): the kernel arguments after Geom, each in a 64-bit slot - an `int` parameter
+// reads the low half of its slot (little-endian host), the one-channel kernel's `long long` all of it
+struct Launch {
+    const void *fn;
+    const char *name;
+    unsigned grid, grid_y, block;
+    size_t lds;
+    Geom g;
+    int nscalars;
+    long long scalar[4];
+    size_t view_off, out_off;    // second channel group of Jp = 32: byte offsets of its views and its result; it writes no grids
+    bool grids;
+};
+
+// Kernel tables, one per kernel signature.  A row is a key, the kernel and its printable name (as a kernel trace shows it,
+// without namespace and parameter list), all three from the same template arguments.  A missing row is SP3D_EUNSUPPORTED.
+// The tables are written as functions, a row being one `if`: an array of kernel pointers and names in a shared object is
+// relocated, hence writable, data, and the library keeps none (tests/test_host_cabi.py).
+struct KernelKey {
+    int jp, ps;          // channels gathered; channels between pixels
+    int a, b;            // tile: XCD map, unroll; pipe: XCD map, waves; brick: z-spectrum, 0; one-channel: views, chunk; else 0, 0
+    int cl, io;          // channels-last result; FwdRequest::io
+};
+using PackFn = void (*)(Views, float *, int, int, int);
+using PlanarFn = void (*)(Views, const float *, const float *, const uint8_t *, float *, float *, Geom);
+using TileFn = void (*)(Views, const float *, const float *, const uint8_t *, float *, float *, Geom, int, int);   // tile and pipe
+using BrickFn = void (*)(Views, const float *, const float *, const uint8_t *, float *, float *, Geom, int, int, int, int);
+using OneFn = void (*)(Views, const float *, const float *, const uint8_t *, float *, float *, Geom, long long, int, int);
+
+template <typename TI, typename TO> constexpr int io_of() { return (sizeof(TI) == 2 ? 1 : 0) | (sizeof(TO) == 2 ? 2 : 0); }
+static bool same_key(const KernelKey &a, const KernelKey &b) { return !memcmp(&a, &b, sizeof(a)); }
+
+#define SP3D_ROW(FN_, KEY_, K_, ...) \
+    if (same_key(key, KEY_)) \
+        return fn = reinterpret_cast<const void *>(static_cast<FN_>(K_<__VA_ARGS__>)), name = #K_ "<" #__VA_ARGS__ ">", SP3D_OK;
+#define SP3D_TILE(JP_, XCD_, U_) SP3D_ROW(TileFn, (KernelKey{JP_, JP_, XCD_, U_, 0, 0}), unproject_nhwc_kernel, JP_, XCD_, U_)
+#define SP3D_TILES(JP_) SP3D_TILE(JP_, true, 1) SP3D_TILE(JP_, false, 1) SP3D_TILE(JP_, true, 2) SP3D_TILE(JP_, false, 2) \
+    SP3D_TILE(JP_, true, 4) SP3D_TILE(JP_, false, 4)
+static int find_tile_kernel(const KernelKey &key, const void *&fn, const char *&name)
+{
+    SP3D_TILES(4) SP3D_TILES(8) SP3D_TILES(12) SP3D_TILES(16)
+    return SP3D_EUNSUPPORTED;
+}
+
+#define SP3D_PIPE(JP_, XCD_, NW_, CL_, TI_, TO_, PS_) \
+    SP3D_ROW(TileFn, (KernelKey{JP_, PS_, XCD_, NW_, CL_, io_of<TI_, TO_>()}), unproject_pipe_kernel, JP_, XCD_, NW_, CL_, TI_, TO_, PS_)
+#define SP3D_PIPES(JP_, NW_, TI_, TO_) SP3D_PIPE(JP_, true, NW_, false, TI_, TO_, JP_) SP3D_PIPE(JP_, false, NW_, false, TI_, TO_, JP_) \
+    SP3D_PIPE(JP_, true, NW_, true, TI_, TO_, JP_) SP3D_PIPE(JP_, false, NW_, true, TI_, TO_, JP_)
+static int find_pipe_kernel(const KernelKey &key, const void *&fn, const char *&name)
+{
+    SP3D_PIPES(4, 1, float, float) SP3D_PIPES(8, 1, float, float) SP3D_PIPES(12, 1, float, float) SP3D_PIPES(16, 1, float, float)
+    SP3D_PIPES(4, 4, float, float) SP3D_PIPES(8, 4, float, float) SP3D_PIPES(12, 4, float, float) SP3D_PIPES(16, 4, float, float)
+    // bf16 storage: 16 channels, one wave per workgroup only
+    SP3D_PIPES(16, 1, bf16_t, float) SP3D_PIPES(16, 1, float, bf16_t) SP3D_PIPES(16, 1, bf16_t, bf16_t)
+    // Jp = 32 channel groups: planar result, XCD map
+    SP3D_PIPE(4, true, 1, false, float, float, 32) SP3D_PIPE(8, true, 1, false, float, float, 32)
+    SP3D_PIPE(12, true, 1, false, float, float, 32) SP3D_PIPE(16, true, 1, false, float, float, 32)
+    SP3D_PIPE(16, true, 1, false, bf16_t, float, 32) SP3D_PIPE(16, true, 1, false, float, bf16_t, 32)
+    SP3D_PIPE(16, true, 1, false, bf16_t, bf16_t, 32)
+    return SP3D_EUNSUPPORTED;
+}
+
+#define SP3D_BRICK(JP_, CL_, TI_, TO_, ZD_, PS_) \
+    SP3D_ROW(BrickFn, (KernelKey{JP_, PS_, ZD_, 0, CL_, io_of<TI_, TO_>()}), unproject_brick_kernel, JP_, CL_, TI_, TO_, ZD_, PS_)
+// bf16 heat-maps: two lanes per pixel, 16 channels
+#define SP3D_BRICK_H(CL_, TO_, PS_) \
+    SP3D_ROW(BrickFn, (KernelKey{16, PS_, false, 0, CL_, 1 | io_of<float, TO_>()}), unproject_brick_h_kernel, CL_, TO_, PS_)
+static int find_brick_kernel(const KernelKey &key, const void *&fn, const char *&name)
+{
+    SP3D_BRICK(4, false, float, float, false, 4) SP3D_BRICK(4, true, float, float, false, 4)
+    SP3D_BRICK(8, false, float, float, false, 8) SP3D_BRICK(8, true, float, float, false, 8)
+    SP3D_BRICK(12, false, float, float, false, 12) SP3D_BRICK(12, true, float, float, false, 12)
+    SP3D_BRICK(16, false, float, float, false, 16) SP3D_BRICK(16, true, float, float, false, 16)
+    SP3D_BRICK(16, false, float, float, true, 16)       // the stack's cubes leave as their z-spectrum (sp3d_unproject_fwd_zdft)
+    SP3D_BRICK(16, false, float, bf16_t, false, 16) SP3D_BRICK(16, true, float, bf16_t, false, 16)
+    SP3D_BRICK_H(false, float, 16) SP3D_BRICK_H(true, float, 16) SP3D_BRICK_H(false, bf16_t, 16) SP3D_BRICK_H(true, bf16_t, 16)
+    // Jp = 32 channel groups: planar result
+    SP3D_BRICK(4, false, float, float, false, 32) SP3D_BRICK(8, false, float, float, false, 32)
+    SP3D_BRICK(12, false, float, float, false, 32) SP3D_BRICK(16, false, float, float, false, 32)
+    SP3D_BRICK(16, false, float, bf16_t, false, 32) SP3D_BRICK_H(false, float, 32) SP3D_BRICK_H(false, bf16_t, 32)
+    return SP3D_EUNSUPPORTED;
+}
+
+// one-channel kernel: VT view slots gathered in chunks of CS
+#define SP3D_ONE(VT_, CS_) SP3D_ROW(OneFn, (KernelKey{1, 1, VT_, CS_, false, 0}), unproject_one_kernel, VT_, CS_, false) \
+    SP3D_ROW(OneFn, (KernelKey{1, 1, VT_, CS_, true, 0}), unproject_one_kernel, VT_, CS_, true)
+#define SP3D_PLANAR(JC_) SP3D_ROW(PlanarFn, (KernelKey{JC_, JC_, 0, 0, 0, 0}), unproject_planar_kernel, JC_)
+static int find_one_or_planar_kernel(const KernelKey &key, const void *&fn, const char *&name)
+{
+    SP3D_ONE(1, 4) SP3D_ONE(2, 4) SP3D_ONE(3, 4) SP3D_ONE(4, 4) SP3D_ONE(5, 4) SP3D_ONE(6, 4) SP3D_ONE(8, 4) SP3D_ONE(10, 8)
+    SP3D_ONE(12, 8) SP3D_ONE(16, 8) SP3D_PLANAR(1) SP3D_PLANAR(4) SP3D_PLANAR(16)
+    return SP3D_EUNSUPPORTED;
+}
+
+#define SP3D_PACK(JP_, TI_, TO_) SP3D_ROW(PackFn, (KernelKey{JP_, JP_, 0, 0, 0, io_of<TI_, TO_>()}), pack_nhwc_kernel, JP_, TI_, TO_)
+static int find_pack_kernel(const KernelKey &key, const void *&fn, const char *&name)
+{
+    SP3D_PACK(4, float, float) SP3D_PACK(8, float, float) SP3D_PACK(12, float, float) SP3D_PACK(16, float, float)
+    SP3D_PACK(32, float, float) SP3D_PACK(16, bf16_t, bf16_t) SP3D_PACK(16, bf16_t, float) SP3D_PACK(16, float, bf16_t)
+    SP3D_PACK(32, bf16_t, bf16_t) SP3D_PACK(32, bf16_t, float) SP3D_PACK(32, float, bf16_t)
+    return SP3D_EUNSUPPORTED;
+}
+#undef SP3D_PACK
+#undef SP3D_PLANAR
+#undef SP3D_ONE
 #undef SP3D_BRICK_H
-            return SP3D_OK;
-        }
-        if (io != 0) {
-            if constexpr (JP == 16) {
-                switch ((io & 3) * 2 + (out_cl ? 1 : 0)) {
-                case 2: SP3D_BRICK(false, bf16_t, float); break;
-                case 3: SP3D_BRICK(true, bf16_t, float); break;
-                case 4: SP3D_BRICK(false, float, bf16_t); break;
-                case 5: SP3D_BRICK(true, float, bf16_t); break;
-                case 6: SP3D_BRICK(false, bf16_t, bf16_t); break;
-                default: SP3D_BRICK(true, bf16_t, bf16_t); break;
-                }
-                return SP3D_OK;
-            } else {
-                return SP3D_EUNSUPPORTED;
-            }
-        }
-        if (out_cl) SP3D_BRICK(true, float, float); else SP3D_BRICK(false, float, float);
 #undef SP3D_BRICK
-        return SP3D_OK;
-    }
-    if (variant & 8) {
-        const int nw = (variant & 16) ? 1 : 4;
-        const int ptiles = (g.N + 64 * nw - 1) / (64 * nw);
-        const int ptotal = ptiles * g.B;
-        dim3 pgrid(xcd ? xcd_grid_blocks(g.B, ptiles, g.xcd_chunk) : ptotal), pblock(64 * nw);
-        Geom gp = g;
-        set_xcd_fields(gp, ptiles);
-#define SP3D_PIPE(XCD_, NW_, CL_) \
-    hipLaunchKernelGGL((unproject_pipe_kernel<JP, XCD_, NW_, CL_>), pgrid, pblock, 0, s, v, cam, centers, valid, cubes, grids, gp, ptiles, ptotal)
-#define SP3D_PIPE_T(XCD_, CL_, TI_, TO_) \
-    hipLaunchKernelGGL((unproject_pipe_kernel<JP, XCD_, 1, CL_, TI_, TO_>), pgrid, pblock, 0, s, v, cam, centers, valid, cubes, grids, gp, ptiles, ptotal)
-        if (io != 0) {   // bf16 storage variants: JP == 16, one wave per workgroup only
-            if constexpr (JP == 16) {
-                if (nw != 1) return SP3D_EUNSUPPORTED;
-                const int sel = (io & 3) * 4 + (out_cl ? 2 : 0) + (xcd ? 1 : 0);
-                switch (sel) {
-                case 4: SP3D_PIPE_T(false, false, bf16_t, float); break;
-                case 5: SP3D_PIPE_T(true, false, bf16_t, float); break;
-                case 6: SP3D_PIPE_T(false, true, bf16_t, float); break;
-                case 7: SP3D_PIPE_T(true, true, bf16_t, float); break;
-                case 8: SP3D_PIPE_T(false, false, float, bf16_t); break;
-                case 9: SP3D_PIPE_T(true, false, float, bf16_t); break;
-                case 10: SP3D_PIPE_T(false, true, float, bf16_t); break;
-                case 11: SP3D_PIPE_T(true, true, float, bf16_t); break;
-                case 12: SP3D_PIPE_T(false, false, bf16_t, bf16_t); break;
-                case 13: SP3D_PIPE_T(true, false, bf16_t, bf16_t); break;
-                case 14: SP3D_PIPE_T(false, true, bf16_t, bf16_t); break;
-                default: SP3D_PIPE_T(true, true, bf16_t, bf16_t); break;
-                }
-                return SP3D_OK;
-            } else {
-                return SP3D_EUNSUPPORTED;
-            }
-        }
-        if (out_cl) {
-            if (nw == 1) { if (xcd) SP3D_PIPE(true, 1, true); else SP3D_PIPE(false, 1, true); }
-            else { if (xcd) SP3D_PIPE(true, 4, true); else SP3D_PIPE(false, 4, true); }
-        } else {
-            if (nw == 1) { if (xcd) SP3D_PIPE(true, 1, false); else SP3D_PIPE(false, 1, false); }
-            else { if (xcd) SP3D_PIPE(true, 4, false); else SP3D_PIPE(false, 4, false); }
-        }
-#undef SP3D_PIPE_T
+#undef SP3D_PIPES
 #undef SP3D_PIPE
-        return SP3D_OK;
-    }
-    if (out_cl || io) return SP3D_EUNSUPPORTED;
-#define SP3D_LAUNCH(XCD_, U_) \
-    hipLaunchKernelGGL((unproject_nhwc_kernel<JP, XCD_, U_>), grid, block, lds, s, v, cam, centers, valid, cubes, grids, g, tiles, total)
-    switch (variant & 3) {
-    case 0: if (xcd) SP3D_LAUNCH(true, 1); else SP3D_LAUNCH(false, 1); break;
-    case 2: if (xcd) SP3D_LAUNCH(true, 4); else SP3D_LAUNCH(false, 4); break;
-    default: if (xcd) SP3D_LAUNCH(true, 2); else SP3D_LAUNCH(false, 2); break;
-    }
-#undef SP3D_LAUNCH
-    return SP3D_OK;
-}
+#undef SP3D_TILES
+#undef SP3D_TILE
+#undef SP3D_ROW
 
-// ------------------------------------------------------------------------------------------
-// Jp = 32 (17..32 joints: the 17 COCO joints of the Shelf / Campus configurations).  A packed fp32 pixel is exactly one
-// 128-byte line.  It is gathered as two channel groups, one launch each, both reading pixels at a stride of PS = 32:
-//   group 0   channels 0-15 through the JP = 16 kernel;
-//   group 1   channels 16..J-1 through a launch of width JPG = ceil4(J - 16) (16 with bf16 maps or cubes, whose kernels
-//             exist at JP = 16 only).  Its view pointers start 16 channels into the pixel (the wave-uniform row base moves,
-//             no VGPR does), its result pointer 16 channel planes further, and its Geom has J - 16 channels.
-// The per-channel arithmetic is the 16-channel kernels', so each group is bit-identical to the oracle by construction.  Only
-// group 0 writes grids; a sample that `valid` skips gets zeros in each group.  Planar results only (dense or strided: the
-// strided path already carries full-volume strides), default kernels only (pipe / brick stacks), no pass mask.
-// ------------------------------------------------------------------------------------------
-constexpr int WIDE_PS = 32;
-
-template <int JPG>
-static int launch_wide_group(const Views &v, const float *cam, const float *centers, const uint8_t *valid, float *cubes,
-                             float *grids, const Geom &g, int variant, int io, hipStream_t s)
+static void set_launch(Launch &L, unsigned grid, unsigned block, size_t lds, int nscalars, long long s0, int s1, int s2 = 0, int s3 = 0)
 {
-    constexpr int PS = WIDE_PS;
-    if (variant & 32) {
-        constexpr int WLDS = (JPG * WOSTR > WREC) ? JPG * WOSTR : WREC;
-        BrickPlan bp;
-        plan_bricks(g, variant, WLDS, bp);
-        dim3 bgrid(bp.block_grid ? bp.block_grid : xcd_grid_blocks(bp.gb.B, bp.wgs, bp.gb.xcd_chunk)), bblock(64 * bp.zw);
-#define SP3D_WBRICK(K_) hipLaunchKernelGGL(K_, bgrid, bblock, bp.blds, s, v, cam, centers, valid, cubes, grids, bp.gb, bp.wgs, bp.nby, bp.nzc, bp.zw)
-        if constexpr (JPG == 16) {
-            switch (io) {
-            case 0: SP3D_WBRICK((unproject_brick_kernel<16, false, float, float, false, PS>)); break;
-            case 1: SP3D_WBRICK((unproject_brick_h_kernel<false, float, PS>)); break;          // bf16 maps: two lanes per pixel
-            case 2: SP3D_WBRICK((unproject_brick_kernel<16, false, float, bf16_t, false, PS>)); break;
-            default: SP3D_WBRICK((unproject_brick_h_kernel<false, bf16_t, PS>)); break;
-            }
-        } else {
-            if (io) return SP3D_EUNSUPPORTED;
-            SP3D_WBRICK((unproject_brick_kernel<JPG, false, float, float, false, PS>));
-        }
-#undef SP3D_WBRICK
-        return SP3D_OK;
-    }
-    // pipe kernel, one wave per workgroup, XCD-aware tile map (default_variant 24)
-    const int ptiles = (g.N + 63) / 64;
-    dim3 pgrid(xcd_grid_blocks(g.B, ptiles, g.xcd_chunk)), pblock(64);
-    Geom gp = g;
-    set_xcd_fields(gp, ptiles);
-#define SP3D_WPIPE(TI_, TO_) \
-    hipLaunchKernelGGL((unproject_pipe_kernel<JPG, true, 1, false, TI_, TO_, PS>), pgrid, pblock, 0, s, v, cam, centers, valid, cubes, grids, gp, ptiles, ptiles * g.B)
-    if constexpr (JPG == 16) {
-        switch (io) {
-        case 0: SP3D_WPIPE(float, float); break;
-        case 1: SP3D_WPIPE(bf16_t, float); break;
-        case 2: SP3D_WPIPE(float, bf16_t); break;
-        default: SP3D_WPIPE(bf16_t, bf16_t); break;
-        }
-    } else {
-        if (io) return SP3D_EUNSUPPORTED;
-        SP3D_WPIPE(float, float);
-    }
-#undef SP3D_WPIPE
-    return SP3D_OK;
+    L.grid = grid; L.block = block; L.lds = lds;
+    L.nscalars = nscalars; L.scalar[0] = s0; L.scalar[1] = s1; L.scalar[2] = s2; L.scalar[3] = s3;
 }
 
-static int launch_nhwc_wide(const Views &v, const float *cam, const float *centers, const uint8_t *valid, float *cubes,
-                            float *grids, const Geom &g, int variant, int io, hipStream_t s)
-{
-    // the default planar variants only: 24 (pipe, one wave per workgroup, XCD map) and 56 (brick stacks)
-    if (variant != 24 && variant != 56) return SP3D_EUNSUPPORTED;
-    const size_t esz = (io & 1) ? 2 : 4, osz = (io & 2) ? 2 : 4;
-    const int J0 = g.J < 16 ? g.J : 16, J1 = g.J - J0;
-    Geom g0 = g;
-    g0.J = J0;
-    int rc = launch_wide_group<16>(v, cam, centers, valid, cubes, grids, g0, variant, io, s);
-    if (rc || J1 == 0) return rc;
-    Views v1;
-    for (int c = 0; c < SP3D_MAX_VIEWS; ++c)
-        v1.p[c] = v.p[c] ? reinterpret_cast<const float *>(reinterpret_cast<const char *>(v.p[c]) + 16 * esz) : nullptr;
-    float *cubes1 = reinterpret_cast<float *>(reinterpret_cast<char *>(cubes) + (size_t)16 * g.sJ * osz);
-    Geom g1 = g;
-    g1.J = J1;
-    if (io) return launch_wide_group<16>(v1, cam, centers, valid, cubes1, nullptr, g1, variant, io, s);
-    switch ((J1 + 3) / 4) {
-    case 1: return launch_wide_group<4>(v1, cam, centers, valid, cubes1, nullptr, g1, variant, io, s);
-    case 2: return launch_wide_group<8>(v1, cam, centers, valid, cubes1, nullptr, g1, variant, io, s);
-    case 3: return launch_wide_group<12>(v1, cam, centers, valid, cubes1, nullptr, g1, variant, io, s);
-    default: return launch_wide_group<16>(v1, cam, centers, valid, cubes1, nullptr, g1, variant, io, s);
-    }
-}
-
-// Default chunk size of the XCD tile map for 64-voxel tiles (launch_nhwc, launch_one): 2-4 chunks per serving XCD -
-// compact enough that an XCD's L2 sees a fraction of each view (fabric reads 93 MB -> 81 MB on the bench workload), fine
-// enough to balance visibility
-static int default_xcd_chunk(const Geom &g)
+// Default chunk size of the XCD tile map for 64-voxel tiles: 2-4 chunks per serving XCD - compact enough that an XCD's
+// L2 sees a fraction of each view (fabric reads 93 MB -> 81 MB on the bench workload), fine enough to balance visibility
+static int default_xcd_chunk(const Geom &g, int tiles)
 {
     const int xps = (g.B <= 8 && (8 % g.B) == 0) ? 8 / g.B : 1;
-    const int t64 = (g.N + 63) / 64;
     int k = 1;
-    while (k * 2 * xps * 2 <= t64) k *= 2;
+    while (k * 2 * xps * 2 <= tiles) k *= 2;
     return k;
 }
 
@@ -2002,86 +1923,188 @@ static int default_xcd_chunk(const Geom &g)
 // workload), so the plain sweep stays there
 static int default_xcd_order(const Geom &g) { return g.B <= 2 ? 1 : 0; }
 
-// io: bit 0 = packed heat-maps are bf16, bit 1 = cubes are bf16
-static int launch_nhwc(const Views &v, int Jp, const float *cam, const float *centers, const uint8_t *valid,
-                       float *cubes, float *grids, const Geom &g_in, int variant, bool out_cl, int io, hipStream_t s)
+// One NHWC launch of `jp` channels read at a pixel stride of `ps`: brick, pipe or tile kernel, its grid and its Geom.
+// `t` is final here (resolve_fwd applied the downgrades).
+static int resolve_group(const FwdRequest &rq, const FwdTuning &t, const Geom &g, int jp, int ps, Launch &L)
 {
-    Geom g = g_in;
-    // chunk order and size: the defaults above; tuning bit 21 forces the plain sweep, bits 17-20 a chunk size
-    g.xcd_order = ((variant >> 21) & 1 ? 0 : default_xcd_order(g)) | ((variant & 256) ? 2 : 0);
-    if ((variant >> 17) & 15)
-        g.xcd_chunk = 1 << (((variant >> 17) & 15) - 1);   // tuning bits 17-20: log2(K)+1
-    else
-        g.xcd_chunk = default_xcd_chunk(g);
-    if (Jp == WIDE_PS) {
-        // 17..32 channels (see launch_nhwc_wide): planar results of the default kernels; no channels-last result, no pass
-        // mask, no z-spectrum, and the pipelined kernels' limits on the image (2x2 block, 24-bit pixel indices)
-        if (g.J > WIDE_PS || out_cl || g.pass_mask || (variant & SP3D_VARIANT_ZD) || g.w < 2 || g.h < 2 ||
-            (int64_t)g.h * g.w > (1 << 24))
+    const int wlds = jp * WOSTR > WREC ? jp * WOSTR : WREC;      // per-wave LDS floats of the pipe and brick kernels
+    L.g = g;
+    if (t.brick) {   // 4x4x4 voxels per wave, a z-stack of `zw` bricks per workgroup
+        const int nbx = (g.X + BR - 1) / BR, nby = (g.Y + BR - 1) / BR, nwz = (g.Z + BR - 1) / BR;
+        int nzc = (nwz + 7) / 8, zw = (nwz + nzc - 1) / nzc;
+        if (t.brick_own_wg) { zw = 1; nzc = nwz; }
+        const int wgs = nbx * nby * nzc;
+        // 2-4 chunks of consecutive workgroups (x-slabs of the volume) per serving XCD
+        L.g.xcd_chunk = t.forced_chunk ? 1 << (t.forced_chunk - 1) : default_xcd_chunk(g, wgs);
+        set_xcd_fields(L.g, wgs);
+        set_brick_fields(L.g, nbx * nby, nby);
+        // default since round 6 (B in {1, 2, 4}): one block of brick columns per XCD - octants at B = 1, quadrants at B = 2,
+        // halves at B = 4 - instead of round-robin chunks; same results, L2 fills 138 -> 60 MB on the 160x160x40 grid,
+        // 75 -> 56 MB on the root grid at B = 4 (profiles/r06_pmc_blocks.json).  The chunk-map tuning restores the chunks.
+        const int block_grid = (t.chunk_map || t.z_fastest) ? 0 : set_block_fields(L.g, nbx, nby, nzc);
+        // view-synchronous workgroups only when every wave of every workgroup lies inside the volume, so that all of them
+        // reach the per-view barrier
+        if (t.view_sync && nwz % zw == 0 && nzc * zw == nwz) L.g.xcd_order |= 4;
+        if (rq.zd && (rq.io || rq.out_cl || g.Z != ZDZ || nzc != 1 || zw != ZDZ / BR || (g.X % BR) || (g.Y % BR) || g.pass_mask))
             return SP3D_EUNSUPPORTED;
-        if (io) variant |= 16;
-        const int rc = launch_nhwc_wide(v, cam, centers, valid, cubes, grids, g, variant, io, s);
-        return rc ? rc : launch_status();
+        set_launch(L, block_grid ? block_grid : xcd_grid_blocks(g.B, wgs, L.g.xcd_chunk), 64 * zw,
+                   (size_t)zw * wlds * sizeof(float) + (size_t)t.ballast * 20480, 4, wgs, nby, nzc, zw);
+        return find_brick_kernel(KernelKey{jp, ps, rq.zd, 0, rq.out_cl, rq.io}, L.fn, L.name);
     }
-    if (Jp < g.J || (Jp & 3) || Jp > 16) return SP3D_EUNSUPPORTED;
-    if (out_cl && (g.J & 3)) return SP3D_EUNSUPPORTED;           // channels-last rows must be 16-B multiples
-    if (g.w < 2 || g.h < 2) variant &= ~(8 | 32);                // the clamped 2x2 block needs a 2x2 image
-    if ((int64_t)g.h * g.w > (1 << 24)) variant &= ~(8 | 32);    // the pipelined kernels form pixel indices with 24-bit multiplies
-    variant &= ~128;                                             // (round-3 LDS patch kernels: measured slower, removed in round 4)
-    if (variant & 32) variant |= 8;
-    if (io && !(variant & 8)) return SP3D_EUNSUPPORTED;
-    if (io) variant |= 16;
-    int rc;
-    switch (Jp) {
-    case 4: rc = launch_nhwc_jp<4>(v, cam, centers, valid, cubes, grids, g, variant, out_cl, io, s); break;
-    case 8: rc = launch_nhwc_jp<8>(v, cam, centers, valid, cubes, grids, g, variant, out_cl, io, s); break;
-    case 12: rc = launch_nhwc_jp<12>(v, cam, centers, valid, cubes, grids, g, variant, out_cl, io, s); break;
-    case 16: rc = launch_nhwc_jp<16>(v, cam, centers, valid, cubes, grids, g, variant, out_cl, io, s); break;
-    default: return SP3D_EUNSUPPORTED;
+    if (t.pipe) {    // 64 consecutive voxels per wave
+        const int nw = t.one_wave ? 1 : 4;
+        const int ptiles = (g.N + 64 * nw - 1) / (64 * nw), ptotal = ptiles * g.B;
+        set_xcd_fields(L.g, ptiles);
+        set_launch(L, t.no_xcd_map ? ptotal : xcd_grid_blocks(g.B, ptiles, g.xcd_chunk), 64 * nw, 0, 2, ptiles, ptotal);
+        return find_pipe_kernel(KernelKey{jp, ps, !t.no_xcd_map, nw, rq.out_cl, rq.io}, L.fn, L.name);
     }
-    return rc ? rc : launch_status();
+    const int tiles = (g.N + TILE - 1) / TILE, total = tiles * g.B;
+    set_launch(L, t.no_xcd_map ? total : xcd_grid_blocks(g.B, tiles, g.xcd_chunk), TILE,
+               (size_t)(jp * OSTR + 2 * g.V * TILE + TILE) * sizeof(float), 2, tiles, total);
+    return find_tile_kernel(KernelKey{jp, ps, !t.no_xcd_map, t.unroll, rq.out_cl, rq.io}, L.fn, L.name);
 }
 
-// SP3D_HM_ONE_CHANNEL (include/sp3d.h): every refusal before any launch.  `layout` = hm_layout without its flag bits;
-// g.J = channels written (1, or 4 = value + three zero channels), g.sB.. = planar result strides (dense or strided).
-static int launch_one(const Views &v, int layout, int Jp, const float *cam, const float *centers, const uint8_t *valid,
-                      float *cubes, float *grids, const Geom &g_in, bool out_cl, int io, hipStream_t s)
+// SP3D_HM_ONE_CHANNEL (include/sp3d.h): g.J = channels written (1, or 4 = value + three zero channels), g.sB.. = planar
+// result strides (dense or strided).  The pipe kernel's tile map: 64-voxel tiles dealt to a sample's XCDs in chunks.
+static int resolve_one(const FwdRequest &rq, Launch &L)
 {
-    if (layout != SP3D_LAYOUT_PLANAR && layout != SP3D_LAYOUT_NHWC) return SP3D_EINVAL;
-    if (Jp < 1) return SP3D_EINVAL;
-    if (io || g_in.pass_mask) return SP3D_EUNSUPPORTED;
-    if (!(g_in.J == 4 || (g_in.J == 1 && !out_cl))) return SP3D_EUNSUPPORTED;
-    if (g_in.w < 2 || g_in.h < 2 || (int64_t)g_in.h * g_in.w > (1 << 24)) return SP3D_EUNSUPPORTED;
-    if (out_cl && ((uintptr_t)cubes & 15)) return SP3D_EUNSUPPORTED;
-    const int64_t px = layout == SP3D_LAYOUT_NHWC ? Jp : 1, row = (int64_t)g_in.w * px;
-    const int64_t sample = layout == SP3D_LAYOUT_NHWC ? (int64_t)g_in.h * row : (int64_t)Jp * g_in.h * g_in.w;
+    Geom &g = L.g;
+    if ((rq.layout != SP3D_LAYOUT_PLANAR && rq.layout != SP3D_LAYOUT_NHWC) || rq.Jp < 1) return SP3D_EINVAL;
+    if (rq.io || g.pass_mask) return SP3D_EUNSUPPORTED;
+    if (!(g.J == 4 || (g.J == 1 && !rq.out_cl))) return SP3D_EUNSUPPORTED;
+    if (g.w < 2 || g.h < 2 || (int64_t)g.h * g.w > (1 << 24)) return SP3D_EUNSUPPORTED;
+    if (rq.out_cl && !rq.out_aligned) return SP3D_EUNSUPPORTED;
+    const int64_t px = rq.layout == SP3D_LAYOUT_NHWC ? rq.Jp : 1, row = (int64_t)g.w * px;
     // 24-bit multiplies form the tap offset, a 32-bit byte offset addresses it
-    if (row >= (1 << 24) || (int64_t)g_in.h * row * 4 > (int64_t)0x7fffffff) return SP3D_EUNSUPPORTED;
-    Geom g = g_in;
-    // the pipe kernel's tile map: 64-voxel tiles dealt to the XCDs that serve a sample in chunks
-    g.xcd_order = default_xcd_order(g);
-    g.xcd_chunk = default_xcd_chunk(g);
+    if (row >= (1 << 24) || (int64_t)g.h * row * 4 > (int64_t)0x7fffffff) return SP3D_EUNSUPPORTED;
     const int ptiles = (g.N + 63) / 64;
+    g.xcd_order = default_xcd_order(g);
+    g.xcd_chunk = default_xcd_chunk(g, ptiles);
     set_xcd_fields(g, ptiles);
-    dim3 grid(xcd_grid_blocks(g.B, ptiles, g.xcd_chunk)), block(64);
-#define SP3D_ONE(VT_, CS_) do { \
-        if (out_cl) hipLaunchKernelGGL((unproject_one_kernel<VT_, CS_, true>), grid, block, 0, s, v, cam, centers, valid, cubes, grids, g, (long long)sample, (int)row, (int)px); \
-        else hipLaunchKernelGGL((unproject_one_kernel<VT_, CS_, false>), grid, block, 0, s, v, cam, centers, valid, cubes, grids, g, (long long)sample, (int)row, (int)px); \
-    } while (0)
-    switch (g.V) {
-    case 1: SP3D_ONE(1, 4); break;
-    case 2: SP3D_ONE(2, 4); break;
-    case 3: SP3D_ONE(3, 4); break;
-    case 4: SP3D_ONE(4, 4); break;
-    case 5: SP3D_ONE(5, 4); break;
-    case 6: SP3D_ONE(6, 4); break;
-    case 7: case 8: SP3D_ONE(8, 4); break;
-    case 9: case 10: SP3D_ONE(10, 8); break;
-    case 11: case 12: SP3D_ONE(12, 8); break;
-    default: SP3D_ONE(16, 8); break;
+    const int64_t sample = rq.layout == SP3D_LAYOUT_NHWC ? (int64_t)g.h * row : (int64_t)rq.Jp * g.h * g.w;
+    set_launch(L, xcd_grid_blocks(g.B, ptiles, g.xcd_chunk), 64, 0, 3, sample, (int)row, (int)px);
+    const int vt = g.V <= 6 ? g.V : (g.V <= 8 ? 8 : (g.V <= 10 ? 10 : (g.V <= 12 ? 12 : 16)));
+    return find_one_or_planar_kernel(KernelKey{1, 1, vt, vt > 8 ? 8 : 4, rq.out_cl, 0}, L.fn, L.name);
+}
+
+// Jp = 32 (17..32 joints: the 17 COCO joints of the Shelf / Campus configurations).  A packed fp32 pixel is exactly one
+// 128-byte line.  It is gathered as two channel groups, one launch each, both reading pixels at a stride of PS = 32:
+//   group 0   channels 0-15 through the JP = 16 kernel;
+//   group 1   channels 16..J-1 through a launch of width ceil4(J - 16) (16 with bf16 maps or cubes, whose kernels
+//             exist at JP = 16 only).  Its view pointers start 16 channels into the pixel (the wave-uniform row base moves,
+//             no VGPR does), its result pointer 16 channel planes further, and its Geom has J - 16 channels.
+// The per-channel arithmetic is the 16-channel kernels', so each group is bit-identical to the oracle by construction.  Only
+// group 0 writes grids; a sample that `valid` skips gets zeros in each group.  Planar results only (dense or strided: the
+// strided path already carries full-volume strides), the two planar defaults only (pipe / brick stacks), no pass mask.
+constexpr int WIDE_PS = 32;
+
+// The one place a forward request becomes launches: every downgrade and refusal, in this order.  Pure host arithmetic.
+static int resolve_fwd(const FwdRequest &rq, FwdTuning t, Launch (&plan)[SP3D_PLAN_RECORDS], int &n)
+{
+    n = 1;
+    Launch &L = plan[0];
+    L = Launch{};
+    L.g = rq.g; L.grid_y = 1; L.grids = true;
+    if (rq.one) return resolve_one(rq, L);
+    if (rq.layout == SP3D_LAYOUT_PLANAR) {
+        if (rq.out_cl || rq.io) return SP3D_EUNSUPPORTED;
+        set_launch(L, (rq.g.N + TILE - 1) / TILE, TILE, 0, 0, 0, 0);
+        L.grid_y = rq.g.B;
+        const int jc = rq.g.J == 1 ? 1 : (rq.g.J <= 4 ? 4 : 16);
+        return find_one_or_planar_kernel(KernelKey{jc, jc, 0, 0, 0, 0}, L.fn, L.name);
     }
-#undef SP3D_ONE
+    if (rq.layout != SP3D_LAYOUT_NHWC) return SP3D_EINVAL;
+    Geom g = rq.g;
+    g.xcd_order = (t.plain_sweep ? 0 : default_xcd_order(g)) | (t.z_fastest ? 2 : 0);
+    g.xcd_chunk = t.forced_chunk ? 1 << (t.forced_chunk - 1) : default_xcd_chunk(g, (g.N + 63) / 64);
+    const FwdTuning asked = t, pipe = default_tuning(FWD_PIPE), stacks = default_tuning(FWD_BRICK_STACKS);
+    // the pipelined kernels clamp a 2x2 block (needs a 2x2 image) and form pixel indices with 24-bit multiplies
+    const bool tile_only = g.w < 2 || g.h < 2 || (int64_t)g.h * g.w > (1 << 24);
+    if (tile_only) t.pipe = t.brick = 0;
+    if (t.brick) t.pipe = 1;
+    if (rq.io) t.one_wave = 1;                 // bf16 storage: one wave per workgroup only
+    if (rq.Jp == WIDE_PS) {
+        if (g.J > WIDE_PS || rq.out_cl || g.pass_mask || rq.zd || tile_only) return SP3D_EUNSUPPORTED;
+        if (memcmp(&asked, &pipe, sizeof(t)) && memcmp(&asked, &stacks, sizeof(t))) return SP3D_EUNSUPPORTED;
+        Geom gg = g;
+        gg.J = g.J < 16 ? g.J : 16;
+        int rc = resolve_group(rq, t, gg, 16, WIDE_PS, L);
+        if (rc || g.J <= 16) return rc;
+        Launch &L1 = plan[n++];
+        L1 = L;
+        gg.J = g.J - 16;
+        L1.view_off = 16 * ((rq.io & 1) ? 2 : 4);
+        L1.out_off = (size_t)16 * g.sJ * ((rq.io & 2) ? 2 : 4);
+        L1.grids = false;
+        return resolve_group(rq, t, gg, rq.io ? 16 : (gg.J + 3) / 4 * 4, WIDE_PS, L1);
+    }
+    if (rq.Jp < g.J || (rq.Jp & 3) || rq.Jp > 16) return SP3D_EUNSUPPORTED;
+    if (rq.out_cl && (g.J & 3)) return SP3D_EUNSUPPORTED;        // channels-last rows must be 16-B multiples
+    if (rq.io && !t.pipe) return SP3D_EUNSUPPORTED;
+    return resolve_group(rq, t, g, rq.Jp, rq.Jp, L);
+}
+
+// the one place a forward kernel is launched
+static int launch_fwd(Launch L, Views v, const float *cam, const float *centers, const uint8_t *valid, float *cubes,
+                      float *grids, hipStream_t s)
+{
+    for (int c = 0; c < SP3D_MAX_VIEWS; ++c)
+        if (v.p[c]) v.p[c] = reinterpret_cast<const float *>(reinterpret_cast<const char *>(v.p[c]) + L.view_off);
+    cubes = reinterpret_cast<float *>(reinterpret_cast<char *>(cubes) + L.out_off);
+    if (!L.grids) grids = nullptr;
+    if (L.lds > 65536) {     // only the LDS ballast gets there
+        const hipError_t ea = hipFuncSetAttribute(L.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)L.lds);
+        if (ea != hipSuccess) return (int)ea;
+    }
+    void *args[12] = {&v, &cam, &centers, &valid, &cubes, &grids, &L.g};
+    for (int i = 0; i < L.nscalars; ++i) args[7 + i] = &L.scalar[i];
+    (void)hipLaunchKernel(L.fn, dim3(L.grid, L.grid_y), dim3(L.block), args, L.lds, s);
     return launch_status();
+}
+
+// The steps every forward entry point starts with: the Geom, the null check (`ptrs`: all its required pointers are there)
+// and the flag bits of hm_layout.
+static int fwd_request(FwdRequest &rq, int hm_layout, int Jp, bool ptrs, int B, int V, int J, int h, int w, int X,
+                       int Y, int Z, const float *grid_size, int W_in, int H_in)
+{
+    const int rc = make_geom(rq.g, B, V, J, h, w, X, Y, Z, grid_size, W_in, H_in);
+    if (rc) return rc;
+    if (!ptrs) return SP3D_ENULL;
+    rq.layout = hm_layout & 0xff; rq.Jp = Jp;
+    rq.io = ((hm_layout & SP3D_HM_BF16) ? 1 : 0) | ((hm_layout & SP3D_OUT_BF16) ? 2 : 0);
+    rq.one = (hm_layout & SP3D_HM_ONE_CHANNEL) != 0;
+    rq.out_cl = (hm_layout & SP3D_OUT_CHANNELS_LAST) != 0;
+    rq.zd = false; rq.out_aligned = true;
+    return SP3D_OK;
+}
+
+// ... and end with: the views, the plan, its launches
+static int run_fwd(const FwdRequest &rq, const FwdTuning &t, const float *const *hm_views, const float *cam, const float *centers,
+                   const uint8_t *valid, float *cubes, float *grids, void *stream)
+{
+    Views v;
+    int rc = load_views(v, hm_views, rq.g.V);
+    if (rc) return rc;
+    Launch plan[SP3D_PLAN_RECORDS];
+    int n;
+    rc = resolve_fwd(rq, t, plan, n);
+    for (int i = 0; !rc && i < n; ++i) rc = launch_fwd(plan[i], v, cam, centers, valid, cubes, grids, (hipStream_t)stream);
+    return rc;
+}
+
+// result strides of sp3d_unproject_fwd_strided into the Geom; `cubes` decides whether 16-byte pieces are allowed
+static int set_result_strides(Geom &g, const int64_t *out_strides, const void *cubes)
+{
+    const int64_t sB = out_strides[0], sJ = out_strides[1], sX = out_strides[2], sY = out_strides[3];
+    // the planes must not overlap and must fit 32-bit in-plane offsets
+    if (sY < g.Z || sX < (int64_t)g.Y * sY || sJ < (int64_t)g.X * sX || sB < (int64_t)g.J * sJ) return SP3D_EINVAL;
+    if (sJ > 0x7fffffff) return SP3D_ERANGE;
+    g.sB = sB; g.sJ = (int)sJ; g.sX = (int)sX; g.sY = (int)sY;
+    g.dense = (sY == g.Z && sX == (int64_t)g.Y * g.Z && sJ == (int64_t)g.N && sB == (int64_t)g.J * g.N) ? 1 : 0;
+    // 16-byte pieces need 4-element aligned rows (and a 16-byte aligned base pointer); otherwise the kernels take their
+    // scalar store path, which is correct for any stride but slow
+    g.vec4 = ((g.dense || ((sY | sX | sJ | sB) & 3) == 0) && ((uintptr_t)cubes & 15) == 0) ? 1 : 0;
+    return SP3D_OK;
 }
 
 } // namespace sp3d
@@ -2142,32 +2165,15 @@ extern "C" int sp3d_pack_heatmaps_ex(const void *const *hm_views, void *packed, 
     Views v;
     int rc = load_views(v, reinterpret_cast<const float *const *>(hm_views), V);
     if (rc) return rc;
-    const int HW = h * w;
+    int HW = h * w;
     dim3 grid((HW + 255) / 256, B, V), block(256);
     hipStream_t s = (hipStream_t)stream;
     float *pk = reinterpret_cast<float *>(packed);
-    if (!in_bf16 && !out_bf16) {
-        switch (Jp) {
-        case 4: hipLaunchKernelGGL(pack_nhwc_kernel<4>, grid, block, 0, s, v, pk, B, J, HW); break;
-        case 8: hipLaunchKernelGGL(pack_nhwc_kernel<8>, grid, block, 0, s, v, pk, B, J, HW); break;
-        case 12: hipLaunchKernelGGL(pack_nhwc_kernel<12>, grid, block, 0, s, v, pk, B, J, HW); break;
-        case 16: hipLaunchKernelGGL(pack_nhwc_kernel<16>, grid, block, 0, s, v, pk, B, J, HW); break;
-        case 32: hipLaunchKernelGGL(pack_nhwc_kernel<32>, grid, block, 0, s, v, pk, B, J, HW); break;
-        default: return SP3D_EUNSUPPORTED;
-        }
-    } else {
-        if (Jp == 16) {
-            if (in_bf16 && out_bf16) hipLaunchKernelGGL((pack_nhwc_kernel<16, bf16_t, bf16_t>), grid, block, 0, s, v, pk, B, J, HW);
-            else if (in_bf16) hipLaunchKernelGGL((pack_nhwc_kernel<16, bf16_t, float>), grid, block, 0, s, v, pk, B, J, HW);
-            else hipLaunchKernelGGL((pack_nhwc_kernel<16, float, bf16_t>), grid, block, 0, s, v, pk, B, J, HW);
-        } else if (Jp == 32) {
-            if (in_bf16 && out_bf16) hipLaunchKernelGGL((pack_nhwc_kernel<32, bf16_t, bf16_t>), grid, block, 0, s, v, pk, B, J, HW);
-            else if (in_bf16) hipLaunchKernelGGL((pack_nhwc_kernel<32, bf16_t, float>), grid, block, 0, s, v, pk, B, J, HW);
-            else hipLaunchKernelGGL((pack_nhwc_kernel<32, float, bf16_t>), grid, block, 0, s, v, pk, B, J, HW);
-        } else {
-            return SP3D_EUNSUPPORTED;
-        }
-    }
+    const void *fn;
+    const char *name;
+    if (find_pack_kernel(KernelKey{Jp, Jp, 0, 0, 0, (in_bf16 ? 1 : 0) | (out_bf16 ? 2 : 0)}, fn, name)) return SP3D_EUNSUPPORTED;
+    void *args[] = {&v, &pk, &B, &J, &HW};
+    (void)hipLaunchKernel(fn, grid, block, args, 0, s);
     return launch_status();
 }
 
@@ -2182,33 +2188,13 @@ extern "C" int sp3d_unproject_fwd_indexed(const float *const *hm_views, int hm_l
                                           float *cubes, float *grids, int P, int V, int J, int h, int w, int X, int Y,
                                           int Z, const float *grid_size, int W_in, int H_in, void *stream)
 {
-    Geom g;
-    int rc = make_geom(g, P, V, J, h, w, X, Y, Z, grid_size, W_in, H_in);
+    FwdRequest rq;
+    const int rc = fwd_request(rq, hm_layout, Jp, cam && centers && valid && cubes, P, V, J, h, w, X, Y, Z,
+                               grid_size, W_in, H_in);
     if (rc) return rc;
-    if (!cam || !centers || !valid || !cubes) return SP3D_ENULL;
-    g.sample_of = sample_of;
-    Views v;
-    rc = load_views(v, hm_views, V);
-    if (rc) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    const int tiles = (g.N + TILE - 1) / TILE;
-    const bool out_cl = (hm_layout & SP3D_OUT_CHANNELS_LAST) != 0;
-    const int io = ((hm_layout & SP3D_HM_BF16) ? 1 : 0) | ((hm_layout & SP3D_OUT_BF16) ? 2 : 0);
-    if (hm_layout & SP3D_HM_ONE_CHANNEL) return launch_one(v, hm_layout & 0xff, Jp, cam, centers, valid, cubes, grids, g, out_cl, io, s);
-    hm_layout &= 0xff;
-    if (hm_layout == SP3D_LAYOUT_PLANAR) {
-        if (out_cl || io) return SP3D_EUNSUPPORTED;
-        dim3 grid(tiles, P), block(TILE);
-        if (J == 1)
-            hipLaunchKernelGGL(unproject_planar_kernel<1>, grid, block, 0, s, v, cam, centers, valid, cubes, grids, g);
-        else if (J <= 4)
-            hipLaunchKernelGGL(unproject_planar_kernel<4>, grid, block, 0, s, v, cam, centers, valid, cubes, grids, g);
-        else
-            hipLaunchKernelGGL(unproject_planar_kernel<16>, grid, block, 0, s, v, cam, centers, valid, cubes, grids, g);
-        return launch_status();
-    }
-    if (hm_layout == SP3D_LAYOUT_NHWC) return launch_nhwc(v, Jp, cam, centers, valid, cubes, grids, g, default_variant(g, out_cl), out_cl, io, s);
-    return SP3D_EINVAL;
+    rq.g.sample_of = sample_of;
+    rq.out_aligned = ((uintptr_t)cubes & 15) == 0;
+    return run_fwd(rq, default_tuning(rq.g, rq.out_cl), hm_views, cam, centers, valid, cubes, grids, stream);
 }
 
 extern "C" int sp3d_unproject_fwd_strided(const float *const *hm_views, int hm_layout, int Jp, const float *cam,
@@ -2216,46 +2202,31 @@ extern "C" int sp3d_unproject_fwd_strided(const float *const *hm_views, int hm_l
                                           float *cubes, const int64_t *out_strides, int P, int V, int J, int h, int w,
                                           int X, int Y, int Z, const float *grid_size, int W_in, int H_in, void *stream)
 {
-    Geom g;
-    int rc = make_geom(g, P, V, J, h, w, X, Y, Z, grid_size, W_in, H_in);
+    FwdRequest rq;
+    int rc = fwd_request(rq, hm_layout, Jp, cam && centers && valid && cubes && out_strides, P, V, J, h, w,
+                         X, Y, Z, grid_size, W_in, H_in);
     if (rc) return rc;
-    if (!cam || !centers || !valid || !cubes || !out_strides) return SP3D_ENULL;
-    const bool out_cl = (hm_layout & SP3D_OUT_CHANNELS_LAST) != 0;
-    const int io = ((hm_layout & SP3D_HM_BF16) ? 1 : 0) | ((hm_layout & SP3D_OUT_BF16) ? 2 : 0);
-    const bool one = (hm_layout & SP3D_HM_ONE_CHANNEL) != 0;       // reads either layout (launch_one)
-    if ((!one && (hm_layout & 0xff) != SP3D_LAYOUT_NHWC) || out_cl || w < 2 || h < 2) return SP3D_EUNSUPPORTED;
-    const int64_t sB = out_strides[0], sJ = out_strides[1], sX = out_strides[2], sY = out_strides[3];
-    // the planes must not overlap and must fit 32-bit in-plane offsets
-    if (sY < Z || sX < (int64_t)Y * sY || sJ < (int64_t)X * sX || sB < (int64_t)J * sJ) return SP3D_EINVAL;
-    if (sJ > 0x7fffffff) return SP3D_ERANGE;
-    g.sB = sB; g.sJ = (int)sJ; g.sX = (int)sX; g.sY = (int)sY;
-    g.dense = (sY == Z && sX == (int64_t)Y * Z && sJ == (int64_t)g.N && sB == (int64_t)J * g.N) ? 1 : 0;
-    // 16-byte pieces need 4-element aligned rows (and a 16-byte aligned base pointer); otherwise the kernels take their
-    // scalar store path, which is correct for any stride but slow
-    g.sample_of = sample_of;
-    Views v;
-    rc = load_views(v, hm_views, V);
+    // the one-channel read takes either layout
+    if ((!rq.one && rq.layout != SP3D_LAYOUT_NHWC) || rq.out_cl || w < 2 || h < 2) return SP3D_EUNSUPPORTED;
+    rc = set_result_strides(rq.g, out_strides, cubes);
     if (rc) return rc;
-    g.vec4 = ((g.dense || ((sY | sX | sJ | sB) & 3) == 0) && ((uintptr_t)cubes & 15) == 0) ? 1 : 0;
-    if (one) return launch_one(v, hm_layout & 0xff, Jp, cam, centers, valid, cubes, nullptr, g, false, io, (hipStream_t)stream);
-    return launch_nhwc(v, Jp, cam, centers, valid, cubes, nullptr, g, default_variant(g, false), false, io, (hipStream_t)stream);
+    rq.g.sample_of = sample_of;
+    return run_fwd(rq, default_tuning(rq.g, false), hm_views, cam, centers, valid, cubes, nullptr, stream);
 }
 
 extern "C" int sp3d_unproject_fwd_zdft(const float *const *hm_views, int Jp, const float *cam, const float *centers,
                                        const uint8_t *valid, float *spec, int B, int V, int J, int h, int w, int X, int Y,
                                        int Z, const float *grid_size, int W_in, int H_in, int SZ, void *stream)
 {
-    Geom g;
-    int rc = make_geom(g, B, V, J, h, w, X, Y, Z, grid_size, W_in, H_in);
+    FwdRequest rq;
+    const int rc = fwd_request(rq, SP3D_LAYOUT_NHWC, Jp, cam && centers && valid && spec, B, V, J, h, w, X, Y, Z,
+                               grid_size, W_in, H_in);
     if (rc) return rc;
-    if (!cam || !centers || !valid || !spec) return SP3D_ENULL;
     if (Jp != 16 || Z != ZDZ || SZ != ZDSZ || (X % BR) || (Y % BR) || w < 2 || h < 2 || (int64_t)h * w > (1 << 24) ||
         ((uintptr_t)spec & 127))
         return SP3D_EUNSUPPORTED;
-    Views v;
-    rc = load_views(v, hm_views, V);
-    if (rc) return rc;
-    return launch_nhwc(v, Jp, cam, centers, valid, spec, nullptr, g, 56 | SP3D_VARIANT_ZD, false, 0, (hipStream_t)stream);
+    rq.zd = true;
+    return run_fwd(rq, default_tuning(FWD_BRICK_STACKS), hm_views, cam, centers, valid, spec, nullptr, stream);
 }
 
 extern "C" int sp3d_unproject_fwd(const float *const *hm_views, int hm_layout, int Jp, const float *cam,
@@ -2306,21 +2277,55 @@ extern "C" int sp3d_unproject_bwd(const float *const *hm_views, const float *cam
                                       X, Y, Z, grid_size, W_in, H_in, stream);
 }
 
-// Not part of the drop-in ABI (declared in csrc/sp3d_tuning.h): same as sp3d_unproject_fwd for
-// the NHWC layout, with an explicit kernel variant, for A/B measurements (tools/ab_variants.py).
+// Not part of the drop-in ABI (declared in csrc/sp3d_tuning.h, which documents the word): same as sp3d_unproject_fwd for
+// the NHWC layout, with an explicit kernel choice, for A/B measurements (tools/ab_variants.py).
 extern "C" int sp3d_unproject_fwd_variant(const float *const *hm_views, int Jp, const float *cam, const float *centers,
                                           const uint8_t *valid, float *cubes, float *grids, int B, int V, int J,
                                           int h, int w, int X, int Y, int Z, const float *grid_size, int W_in,
                                           int H_in, int variant, void *stream)
 {
-    Geom g;
-    int rc = make_geom(g, B, V, J, h, w, X, Y, Z, grid_size, W_in, H_in);
+    FwdRequest rq;
+    const int rc = fwd_request(rq, SP3D_LAYOUT_NHWC | ((variant & SP3D_TUNING_CHANNELS_LAST) ? SP3D_OUT_CHANNELS_LAST : 0),
+                               Jp, cam && centers && valid && cubes, B, V, J, h, w, X, Y, Z, grid_size, W_in, H_in);
     if (rc) return rc;
-    if (!cam || !centers || !valid || !cubes) return SP3D_ENULL;
-    Views v;
-    rc = load_views(v, hm_views, V);
+    return run_fwd(rq, decode_tuning(variant), hm_views, cam, centers, valid, cubes, grids, stream);
+}
+
+// Measurement only (sp3d_tuning.h): the launches resolve_fwd() decides on for a request given as shapes.  No HIP call.
+extern "C" int sp3d_unproject_fwd_plan(int entry, int hm_layout, int Jp, const int64_t *out_strides, int B, int V, int J, int h,
+                                       int w, int X, int Y, int Z, int variant, char *names, int32_t *fields, int32_t *tuning,
+                                       int32_t *records)
+{
+    if (!names || !fields || !tuning || !records) return SP3D_ENULL;
+    if (entry < SP3D_PLAN_INDEXED || entry > SP3D_PLAN_TUNING) return SP3D_EINVAL;
+    const float grid_size[3] = {1.0f, 1.0f, 1.0f};
+    if (entry == SP3D_PLAN_ZDFT) hm_layout = SP3D_LAYOUT_NHWC;
+    if (entry == SP3D_PLAN_TUNING) hm_layout = SP3D_LAYOUT_NHWC | ((variant & SP3D_TUNING_CHANNELS_LAST) ? SP3D_OUT_CHANNELS_LAST : 0);
+    FwdRequest rq;
+    int rc = fwd_request(rq, hm_layout, Jp, true, B, V, J, h, w, X, Y, Z, grid_size, 1, 1);
+    if (!rc && entry == SP3D_PLAN_STRIDED && out_strides) rc = set_result_strides(rq.g, out_strides, nullptr);
     if (rc) return rc;
-    return launch_nhwc(v, Jp, cam, centers, valid, cubes, grids, g, variant & 0xffffff, (variant & 0x1000000) != 0, 0, (hipStream_t)stream);
+    if (entry == SP3D_PLAN_TRAIN) rq.g.pass_mask = reinterpret_cast<uint16_t *>(records);    // "there is one": never dereferenced
+    rq.zd = entry == SP3D_PLAN_ZDFT;
+    const FwdTuning t = entry == SP3D_PLAN_TUNING ? decode_tuning(variant)
+                                                  : (rq.zd ? default_tuning(FWD_BRICK_STACKS) : default_tuning(rq.g, rq.out_cl));
+    memcpy(tuning, &t, sizeof(t));
+    Launch plan[SP3D_PLAN_RECORDS];
+    rc = resolve_fwd(rq, t, plan, *records);
+    if (rc) return rc;
+    for (int i = 0; i < *records; ++i, names += SP3D_PLAN_NAME, fields += SP3D_PLAN_FIELDS) {
+        const Launch &L = plan[i];
+        const Geom &g = L.g;
+        snprintf(names, SP3D_PLAN_NAME, "%s", L.name);
+        const int32_t f[SP3D_PLAN_FIELDS] = {
+            (int32_t)(L.grid * L.grid_y), (int32_t)L.block, (int32_t)L.lds, L.nscalars, (int32_t)L.scalar[0], (int32_t)L.scalar[1],
+            (int32_t)L.scalar[2], (int32_t)L.scalar[3], g.J, g.xcd_chunk, g.xcd_order, g.xm_mode, g.xm_log2xps, g.xm_log2K, g.xm_rows,
+            g.xm_tiles, (int32_t)g.xm_magic_tiles, g.bk_nxy, g.bk_nby, (int32_t)g.bk_magic_nxy, (int32_t)g.bk_magic_nby,
+            g.blk_log2py, g.blk_w, g.blk_h, g.blk_nbx, g.blk_nzc, (int32_t)g.blk_magic_wh, (int32_t)g.blk_magic_h,
+            (int32_t)L.view_off, (int32_t)L.out_off, L.grids ? 1 : 0};
+        memcpy(fields, f, sizeof(f));
+    }
+    return SP3D_OK;
 }
 
 // forward with the gradient pass mask (uint16 per voxel, bit j = channel j passes gradient) for
@@ -2331,20 +2336,14 @@ extern "C" int sp3d_unproject_fwd_train(const float *const *hm_views, int hm_lay
                                         int w, int X, int Y, int Z, const float *grid_size, int W_in, int H_in,
                                         void *stream)
 {
-    Geom g;
-    int rc = make_geom(g, P, V, J, h, w, X, Y, Z, grid_size, W_in, H_in);
+    FwdRequest rq;
+    const int rc = fwd_request(rq, hm_layout, Jp, cam && centers && valid && cubes && pass_mask, P, V, J, h, w,
+                               X, Y, Z, grid_size, W_in, H_in);
     if (rc) return rc;
-    if (!cam || !centers || !valid || !cubes || !pass_mask) return SP3D_ENULL;
-    if ((hm_layout & 0xff) != SP3D_LAYOUT_NHWC || (hm_layout & (SP3D_HM_BF16 | SP3D_OUT_BF16 | SP3D_HM_ONE_CHANNEL)) || w < 2 || h < 2)
-        return SP3D_EUNSUPPORTED;
-    g.sample_of = sample_of;
-    g.pass_mask = pass_mask;
-    Views v;
-    rc = load_views(v, hm_views, V);
-    if (rc) return rc;
-    const bool train_cl = (hm_layout & SP3D_OUT_CHANNELS_LAST) != 0;
-    return launch_nhwc(v, Jp, cam, centers, valid, cubes, grids, g, default_variant(g, train_cl), train_cl, 0,
-                       (hipStream_t)stream);
+    if (rq.layout != SP3D_LAYOUT_NHWC || rq.io || rq.one || w < 2 || h < 2) return SP3D_EUNSUPPORTED;
+    rq.g.sample_of = sample_of;
+    rq.g.pass_mask = pass_mask;
+    return run_fwd(rq, default_tuning(rq.g, rq.out_cl), hm_views, cam, centers, valid, cubes, grids, stream);
 }
 
 // scatter: which kernel sp3d_unproject_bwd_packed[_det] launches - SP3D_SCATTER_AUTO (by voxel pitch), _PER_TAP (bwd2),

@@ -82,7 +82,12 @@ def test_unproject_fwd_vs_oracle_and_golden(dev, name, layout):
 
 
 @pytest.mark.parametrize("variant", [0, 1, 2, 4, 5, 6, 8, 12, 24, 28, 24 | (1 << 21), 24 | (1 << 17), 24 | (7 << 17),
-                                     56, 56 | (1 << 21), 56 | (1 << 17), 56 | (5 << 17), 120, 120 | (1 << 17)])
+                                     56, 56 | (1 << 21), 56 | (1 << 17), 56 | (5 << 17), 120, 120 | (1 << 17),
+                                     # words the measurement tools pass: every brick its own workgroup (both spellings
+                                     # equal the integer 120, so they carry ids of their own and 120 keeps its id),
+                                     # z-fastest order, the chunk map of the bricks
+                                     pytest.param(56 | 64, id="56|64"), pytest.param(120 | 64, id="120|64"), 56 | 256,
+                                     120 | (1 << 22), 56 | (1 << 22)])
 def test_nhwc_variants_bit_identical(dev, variant):
     case = gio.Case("unproj_coarse_full_96x72")
     base, _ = _hip_fwd(case, dev, "planar")

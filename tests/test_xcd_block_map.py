@@ -1,6 +1,6 @@
 """The brick unprojection's workgroup -> (sample, brick stack) maps, emulated on the host: every (sample, tile) exactly once.
 
-The brick kernels (selfpose3d_amd/csrc/sp3d_unproject.hip, launch_nhwc_jp) decode blockIdx.x through xcd_map_fast() with
+The brick kernels (selfpose3d_amd/csrc/sp3d_unproject.hip, resolve_group) decode blockIdx.x through xcd_map_fast() with
 fields the host fills in set_xcd_fields(), set_block_fields() and set_brick_fields() (selfpose3d_amd/csrc/sp3d_device.h:396-504);
 udiv_magic() is sp3d_device.h:80-86.  Since round 6 the default for B in {1, 2, 4} is the block map: octants of the (x, y)
 plane of brick columns at B = 1 on a square grid with an even side >= 4 (xm_mode 4, with a float square root and two
@@ -54,8 +54,9 @@ def xcd_slots_per_xcd(B, tiles, K):            # sp3d_device.h:356-365
 
 
 def launch_geom(B, nbx, nby, nzc, chunks=False):
-    """the host side of the brick launch (sp3d_unproject.hip launch_nhwc / launch_nhwc_jp): chunk size K, xcd_order bit 0
-    (centre-out for B <= 2), set_xcd_fields, set_brick_fields, set_block_fields -> (fields, grid size)"""
+    """the host side of the brick launch (sp3d_unproject.hip resolve_fwd / resolve_group): chunk size K, xcd_order bit 0
+    (centre-out for B <= 2), set_xcd_fields, set_brick_fields, set_block_fields -> (fields, grid size);
+    tests/test_fwd_launch_plan.py holds it against the library's own plan"""
     wgs = nbx * nby * nzc
     g = dict(B=B, xcd_order=1 if B <= 2 else 0)
     xps = 8 // B if (B <= 8 and 8 % B == 0) else 1
