@@ -100,7 +100,8 @@ enum {
      * in (>= 1); SP3D_LAYOUT_NHWC: Jp = pixel stride in elements of the (B, h, w, Jp) buffer (>= 1, any value).
      * J = channels written: 1, or 4 (the value and three zero channels); with SP3D_OUT_CHANNELS_LAST J must be 4.
      * Same bits as the other forward kernels give for that channel.  SP3D_EUNSUPPORTED, before any launch, for any
-     * other J, for either bf16 flag, for sp3d_unproject_fwd_train (no pass mask), for heat-maps narrower or lower
+     * other J, for either bf16 flag, for sp3d_unproject_fwd_train (its pass mask and a heat-map gradient of the one channel
+     * are sp3d_unproject_one_fwd_train / sp3d_unproject_one_bwd[_det], sp3d_one_train.h), for heat-maps narrower or lower
      * than 2 pixels or of more than 2^24 pixels, and for a sample of more than 2^31 bytes; SP3D_EINVAL for Jp < 1 and for a
      * layout byte that is neither SP3D_LAYOUT_PLANAR nor SP3D_LAYOUT_NHWC. */
     SP3D_HM_ONE_CHANNEL = 0x800
@@ -238,6 +239,11 @@ int sp3d_unproject_bwd_packed_det(const float *cam, const int32_t *sample_of, co
                                   const float *scale, int B, int P, int V, int J, int Jp, int h, int w, int X, int Y,
                                   int Z, const float *grid_size, int W_in, int H_in, int scatter, void *stream);
 int sp3d_fixed_to_float(const int64_t *acc, float *out, const float *scale, int64_t n, void *stream);
+
+/* The training pair of the one-channel unprojection (SP3D_HM_ONE_CHANNEL with a heat-map gradient): the forward that also
+ * writes the pass mask, and a backward that scatters the one channel into dense (V,B,h,w) planes, fp32 or deterministic.
+ * Declared and documented in sp3d_one_train.h. */
+#include "sp3d_one_train.h"
 
 /*
  * core.proposal.nms + ProposalLayer.get_real_loc (lib/core/proposal.py:28-48,

@@ -94,6 +94,11 @@ TUNING_SIGNATURES = {                           # selfpose3d_amd/csrc/sp3d_tunin
     "sp3d_debug_set_timeline": "i: p",
     "sp3d_debug_stamp": "i: pp",
 }
+ONE_TRAIN_SIGNATURES = {                        # include/sp3d_one_train.h (included by sp3d.h): required like SIGNATURES
+    "sp3d_unproject_one_fwd_train": "i: p ii ppppppp iiiiiiii p ii p",
+    "sp3d_unproject_one_bwd": "i: ppppp l pp iiiiiiii p ii p",
+    "sp3d_unproject_one_bwd_det": "i: ppppp l ppp iiiiiiii p ii p",
+}
 EXPORTS = list(SIGNATURES)
 
 _lib = None
@@ -143,7 +148,7 @@ def load():
             f"{LIB_PATH} not found - the HIP extension is not built. Run `python -m selfpose3d_amd.build` "
             "(hipcc, gfx950). There is no CPU fallback for the unprojection path.")
     lib = C.CDLL(LIB_PATH)
-    for table, required in ((SIGNATURES, True), (TUNING_SIGNATURES, False)):
+    for table, required in ((SIGNATURES, True), (ONE_TRAIN_SIGNATURES, True), (TUNING_SIGNATURES, False)):
         for name, sig in table.items():
             if required or hasattr(lib, name):
                 ret, args = sig.split(":")
@@ -295,7 +300,7 @@ def unproject_fwd(views: Sequence[torch.Tensor], layout: int, jp: int, cam: torc
     return cubes, grids
 
 
-PLAN_ENTRIES = ("indexed", "strided", "train", "zdft", "variant")      # SP3D_PLAN_* (csrc/sp3d_tuning.h)
+PLAN_ENTRIES = ("indexed", "strided", "train", "zdft", "variant", "one_train")      # SP3D_PLAN_* (csrc/sp3d_tuning.h)
 PLAN_FIELDS = ("workgroups", "block", "lds", "nscalars", "s0", "s1", "s2", "s3", "J", "xcd_chunk", "xcd_order", "xm_mode", "xm_log2xps",
                "xm_log2K", "xm_rows", "xm_tiles", "xm_magic_tiles", "bk_nxy", "bk_nby", "bk_magic_nxy", "bk_magic_nby", "blk_log2py",
                "blk_w", "blk_h", "blk_nbx", "blk_nzc", "blk_magic_wh", "blk_magic_h", "view_off", "out_off", "grids")
@@ -658,6 +663,72 @@ def unproject_bwd_packed(cam, centers, valid, grad_cubes: torch.Tensor, pass_mas
                                            int(scatter), _stream(dev))
         check(rc, "sp3d_unproject_bwd_packed")
     return packed if return_packed else [packed[c].permute(0, 3, 1, 2)[:, :J] for c in range(num_views)]
+
+
+def unproject_one_fwd_train(views: Sequence[torch.Tensor], layout: int, jp: int, cam: torch.Tensor, centers: torch.Tensor,
+                            valid: torch.Tensor, B: int, J: int, h: int, w: int, cube_size, grid_size, img_size,
+                            pass_mask: torch.Tensor, want_grids: bool = True, channels_last: bool = False,
+                            sample_of: Optional[torch.Tensor] = None):
+    """one-channel training forward (sp3d_unproject_one_fwd_train): ``views``, ``layout`` and ``jp`` as ``unproject_fwd`` takes
+    them with ``one_channel=True``; ``J`` = channels written, 1 or 4 (channels-last: 4).  Also fills ``pass_mask`` ((B, X*Y*Z)
+    int16, bit 0) for ``unproject_one_bwd``.  -> (cubes, grids | None)"""
+    lib = load()
+    dev = cam.device
+    _require_cam(cam)
+    X, Y, Z = (int(c) for c in cube_size)
+    if not all(v.dtype == torch.float32 and v.is_cuda for v in views):
+        raise Sp3dError("unproject_one_fwd_train: fp32 heat-map views on the GPU expected")
+    if pass_mask.dtype != torch.int16 or not pass_mask.is_contiguous() or pass_mask.numel() != B * X * Y * Z:
+        raise Sp3dError("unproject_one_fwd_train: pass_mask must be a contiguous int16 (B, X*Y*Z) tensor")
+    cubes = _empty_cl3d(B, J, X, Y, Z, dev) if channels_last else torch.empty((B, J, X, Y, Z), dtype=torch.float32, device=dev)
+    grids = torch.empty((B, X * Y * Z, 3), dtype=torch.float32, device=dev) if want_grids else None
+    flags = HM_ONE_CHANNEL | (OUT_CHANNELS_LAST if channels_last else 0)
+    rc = lib.sp3d_unproject_one_fwd_train(_ptr_array(views), layout | flags, jp, cam.data_ptr(), _opt(sample_of),
+                                          centers.data_ptr(), valid.data_ptr(), cubes.data_ptr(), _opt(grids),
+                                          pass_mask.data_ptr(), B, len(views), J, h, w, X, Y, Z, _f3(grid_size),
+                                          int(img_size[0]), int(img_size[1]), _stream(dev))
+    check(rc, "sp3d_unproject_one_fwd_train")
+    return cubes, grids
+
+
+def unproject_one_bwd(cam, centers, valid, grad_cubes: torch.Tensor, pass_mask: torch.Tensor, batch: int, num_views: int,
+                      h: int, w: int, cube_size, grid_size, img_size, sample_of: Optional[torch.Tensor] = None,
+                      deterministic: bool = False):
+    """one-channel scatter: channel 0 of ``grad_cubes`` (P,C,X,Y,Z) -> list[V] of (B,1,h,w) gradient views of one dense
+    (V,B,h,w) buffer.  A contiguous planar fp32 gradient is read in place at its cube stride (C*N: no slice copy); anything
+    else (channels-last, another dtype, a view) is reduced to channel 0 first.
+    ``deterministic``: 64-bit fixed point with integer atomics, scale = 2^(40 - ceil(log2 max|g|)) of that channel, as
+    ``unproject_bwd_packed`` builds it: bit-identical run to run, and to channel 0 of the packed deterministic scatter."""
+    lib = load()
+    dev = cam.device
+    _require_cam(cam)
+    P = int(grad_cubes.shape[0])
+    X, Y, Z = (int(c) for c in cube_size)
+    N = X * Y * Z
+    if grad_cubes.dtype == torch.float32 and grad_cubes.is_contiguous():
+        gc, stride = grad_cubes, int(grad_cubes.shape[1]) * N
+    else:
+        gc, stride = grad_cubes[:, :1].float().contiguous(), N
+    if deterministic:
+        # scale = 2^(40 - ceil(log2 max|g|)): computed on the device, no host synchronisation
+        gmax = gc[:, 0].abs().amax().clamp_min(1e-30)
+        scale = torch.exp2(40.0 - torch.ceil(torch.log2(gmax))).to(torch.float32).reshape(1)
+        fixed = torch.zeros((num_views, batch, h, w), dtype=torch.int64, device=dev)
+        rc = lib.sp3d_unproject_one_bwd_det(cam.data_ptr(), _opt(sample_of), centers.data_ptr(), valid.data_ptr(), gc.data_ptr(),
+                                            stride, pass_mask.data_ptr(), fixed.data_ptr(), scale.data_ptr(), int(batch), P,
+                                            num_views, h, w, X, Y, Z, _f3(grid_size), int(img_size[0]), int(img_size[1]),
+                                            _stream(dev))
+        check(rc, "sp3d_unproject_one_bwd_det")
+        out = torch.empty((num_views, batch, h, w), dtype=torch.float32, device=dev)
+        check(lib.sp3d_fixed_to_float(fixed.data_ptr(), out.data_ptr(), scale.data_ptr(), fixed.numel(), _stream(dev)),
+              "sp3d_fixed_to_float")
+    else:
+        out = torch.zeros((num_views, batch, h, w), dtype=torch.float32, device=dev)
+        rc = lib.sp3d_unproject_one_bwd(cam.data_ptr(), _opt(sample_of), centers.data_ptr(), valid.data_ptr(), gc.data_ptr(),
+                                        stride, pass_mask.data_ptr(), out.data_ptr(), int(batch), P, num_views, h, w, X, Y, Z,
+                                        _f3(grid_size), int(img_size[0]), int(img_size[1]), _stream(dev))
+        check(rc, "sp3d_unproject_one_bwd")
+    return [out[c].unsqueeze(1) for c in range(num_views)]
 
 
 def gaussian_target_3d(roots: torch.Tensor, gx: torch.Tensor, gy: torch.Tensor, gz: torch.Tensor, sigma: float):

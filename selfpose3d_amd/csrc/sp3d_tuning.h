@@ -33,7 +33,8 @@ int sp3d_unproject_fwd_variant(const float *const *hm_views, int Jp, const float
  * pointers, each entry's refusals) are not repeated here.
  *   entry        which entry point asks: _INDEXED (hm_layout with its flag bits as in include/sp3d.h), _STRIDED (the same,
  *                with out_strides, NULL = dense), _TRAIN (the same, with a pass mask), _ZDFT, _TUNING (NHWC fp32 and the
- *                word `variant`, bit 24 included; `variant` is read for this entry only)
+ *                word `variant`, bit 24 included; `variant` is read for this entry only), _ONE_TRAIN
+ *                (sp3d_unproject_one_fwd_train: SP3D_HM_ONE_CHANNEL implied, with a pass mask)
  *   names        SP3D_PLAN_NAME bytes per launch: the kernel with its template arguments, as a kernel trace prints it
  *                without namespaces and parameter list
  *   fields       SP3D_PLAN_FIELDS int32 per launch: workgroups, workgroup size, dynamic LDS bytes, number of kernel
@@ -44,7 +45,7 @@ int sp3d_unproject_fwd_variant(const float *const *hm_views, int Jp, const float
  *   tuning       SP3D_PLAN_TUNING_FIELDS int32: the decoded tuning in the order of the list above (bits 1:0 as the count 1, 2, 4)
  *   records      number of launches (at most SP3D_PLAN_RECORDS)
  * Returns SP3D_OK or the refusal. */
-enum { SP3D_PLAN_INDEXED, SP3D_PLAN_STRIDED, SP3D_PLAN_TRAIN, SP3D_PLAN_ZDFT, SP3D_PLAN_TUNING };
+enum { SP3D_PLAN_INDEXED, SP3D_PLAN_STRIDED, SP3D_PLAN_TRAIN, SP3D_PLAN_ZDFT, SP3D_PLAN_TUNING, SP3D_PLAN_ONE_TRAIN };
 enum { SP3D_PLAN_RECORDS = 2, SP3D_PLAN_NAME = 96, SP3D_PLAN_FIELDS = 31, SP3D_PLAN_TUNING_FIELDS = 12 };
 int sp3d_unproject_fwd_plan(int entry, int hm_layout, int Jp, const int64_t *out_strides, int B, int V, int J, int h, int w,
                             int X, int Y, int Z, int variant, char *names, int32_t *fields, int32_t *tuning, int32_t *records);

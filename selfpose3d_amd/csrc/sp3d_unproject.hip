@@ -690,8 +690,13 @@ __global__ __launch_bounds__(64 * NW) void unproject_pipe_kernel(Views hm, const
 //
 // Result: planar with g.J = 1 or 4 channels (dense or strided; channels 1-3 zeros), or channels-last (B,X,Y,Z,4) as
 // one 16-byte store {v, 0, 0, 0} per lane.
+//
+// MASK (sp3d_unproject_one_fwd_train): the lane also writes its voxel's word of g.pass_mask - bit 0 by the predicate of
+// pipe_tile / unproject_brick_kernel on the same fuse_pre value, so the words are the packed training forward's at J = 1
+// (an unseen voxel passes, a NaN-zeroed one does not, a cube that `valid` skips gets zeros).  One 2-byte store per lane,
+// 128 contiguous bytes per wave.  The MASK = false instantiations are the kernels of the inference path, unchanged.
 // ------------------------------------------------------------------------------------------
-template <int VT, int CS, bool OUTCL>
+template <int VT, int CS, bool OUTCL, bool MASK = false>
 __global__ __launch_bounds__(64) void unproject_one_kernel(Views hm, const float *__restrict__ cam,
                                                            const float *__restrict__ centers,
                                                            const uint8_t *__restrict__ valid, float *__restrict__ cubes,
@@ -715,6 +720,7 @@ __global__ __launch_bounds__(64) void unproject_one_kernel(Views hm, const float
     float *dst = OUTCL ? cubes + ((size_t)b * g.N + n) * 4
                        : cubes + (size_t)b * g.sB + (g.dense ? (size_t)n : (size_t)vx * g.sX + (size_t)vy * g.sY + vz);
     float out = 0.0f;
+    uint16_t word = 0;                              // MASK: this voxel's pass-mask word
     if (valid[b]) {
         const float x = linspace_step(g.Lx, g.stepx, g.X, vx) + centers[3 * b + 0];
         const float y = linspace_step(g.Ly, g.stepy, g.Y, vy) + centers[3 * b + 1];
@@ -782,11 +788,17 @@ __global__ __launch_bounds__(64) void unproject_one_kernel(Views hm, const float
         const float den = (float)(mymask & 0x7fffffffu) + 1e-6f;
         const float rden = (mymask & 0x80000000u) ? 0.0f : 1.0f / den;
         out = fuse_rcp(acc, den, rden);
+        if constexpr (MASK) {
+            // gradient pass mask (torch.clamp backward: 0 <= pre <= 1; a NaN-zeroed voxel, rden == 0, blocks it)
+            const float pre = fuse_pre(acc, den, rden);
+            word = (rden != 0.0f && pre >= 0.0f && pre <= 1.0f) ? 1 : 0;
+        }
     } else if (grids && inb) {                      // skipped sample: zeros (project_layer.py:48,51,54)
         float *gp = grids + ((size_t)b * g.N + n) * 3;
         gp[0] = 0.0f; gp[1] = 0.0f; gp[2] = 0.0f;
     }
     if (!inb) return;
+    if constexpr (MASK) g.pass_mask[(size_t)b * g.N + n] = word;
     if (OUTCL) {
         Store4<float>::store_nt(dst, make_float4(out, 0.0f, 0.0f, 0.0f));
     } else {
@@ -1449,6 +1461,87 @@ __global__ __launch_bounds__(64) void unproject_bwd2_kernel(const float *__restr
 }
 
 // ------------------------------------------------------------------------------------------
+// one-channel backward (sp3d_unproject_one_bwd[_det]): the scatter of bwd2 for ONE gradient channel, into dense (V,B,h,w)
+// planes instead of channel 0 of 16-byte pixels.  bwd2<4> runs this case on 16 of its 64 lanes and three of every four
+// atomics it issues add the zero gradient of a pad channel; here lane = voxel throughout and every atomic carries a value.
+//   pass 1   lane = voxel: sample_pos_fast per view -> view bits (+ bit 31: NaN position), den = popc + 1e-6
+//            g = (bit 0 of the pass-mask word && !dead) ? grad / den : 0; a wave without any g != 0 ends here
+//   pass 2   per view (wave-uniform loop, camera record in scalar registers): sample_pos_fast + make_record again - the
+//            calls of bwd2's phase P1, so offset and weights are bwd2's - then up to four atomics g * w on the lanes that see
+//            the view, each predicated on its weight.  Same fp32 products (grad / den) * w as bwd2: with DET the integers
+//            added are the same, so the result equals channel 0 of sp3d_unproject_bwd_packed_det bit for bit.
+// No LDS, no barrier: the record of a view lives in registers while its taps are issued.  grad_cubes: channel 0 of cube p is
+// N contiguous floats at p * grad_stride (N for a (P,1,..) gradient, 4N for a planar (P,4,..) one).
+// ------------------------------------------------------------------------------------------
+template <bool DET>
+__global__ __launch_bounds__(64) void unproject_one_bwd_kernel(const float *__restrict__ cam,
+                                                              const float *__restrict__ centers,
+                                                              const uint8_t *__restrict__ valid,
+                                                              const float *__restrict__ grad_cubes, long long grad_stride,
+                                                              const uint16_t *__restrict__ pass_mask,
+                                                              void *__restrict__ grad_hm_, size_t view_stride, Geom g,
+                                                              int tiles_per_sample, const float *__restrict__ scale_p)
+{
+    using ACC = typename std::conditional<DET, unsigned long long, float>::type;
+    ACC *grad_hm = reinterpret_cast<ACC *>(grad_hm_);
+    const double scale = DET ? (double)*scale_p : 1.0;
+    auto add = [&](ACC *p, float val) {
+        if constexpr (DET) atomicAdd(p, (unsigned long long)__double2ll_rn((double)val * scale));
+        else unsafeAtomicAdd(p, val);
+    };
+    int b, tile;
+    if (!xcd_map(blockIdx.x, g.B, tiles_per_sample, g.xcd_chunk, b, tile)) return;
+    const int n0 = tile * 64;
+    if (n0 >= g.N || !valid[b]) return;
+    const int bs = g.sample_of ? g.sample_of[b] : b;
+    const int lane = threadIdx.x;
+    const int nvox = min(64, g.N - n0);
+    const bool inb = lane < nvox;
+    const int n = n0 + (inb ? lane : 0);
+    int vx, rem, vy, vz;
+    udiv_magic((uint32_t)n, (uint32_t)g.YZ, g.magicYZ, vx, rem);
+    udiv_magic((uint32_t)rem, (uint32_t)g.Z, g.magicZ, vy, vz);
+    const float x = linspace_step(g.Lx, g.stepx, g.X, vx) + centers[3 * b + 0];
+    const float y = linspace_step(g.Ly, g.stepy, g.Y, vy) + centers[3 * b + 1];
+    const float z = linspace_step(g.Lz, g.stepz, g.Z, vz) + centers[3 * b + 2];
+    // the two loads of a voxel in flight while the views are projected (n is a valid voxel for every lane)
+    const uint32_t pm = (uint32_t)pass_mask[(size_t)b * g.N + n];
+    const float gl = grad_cubes[(size_t)b * (size_t)grad_stride + n];
+    uint32_t mymask = 0;
+    for (int c = 0; c < g.V; ++c) {
+        const float *cm = cam + ((size_t)bs * g.V + c) * SP3D_CAM_STRIDE;
+        float ix, iy;
+        bool isnan;
+        const bool bound = sample_pos_fast(cm, x, y, z, g, ix, iy, isnan) && inb;
+        if (bound) mymask |= (1u << c);
+        if (isnan && inb) mymask |= 0x80000000u;
+    }
+    // g = pass ? grad / den : 0     (autograd of project_layer.py:96-99)
+    const float den = (float)__popc(mymask & 0x7fffffffu) + 1e-6f;
+    const bool dead = (mymask & 0x80000000u) != 0 || (mymask & 0x7fffffffu) == 0;
+    float gv = 0.0f;
+    if (inb && !dead && (pm & 1u)) gv = gl / den;
+    const uint32_t views = gv != 0.0f ? (mymask & 0x7fffffffu) : 0u;      // voxels without gradient scatter nothing
+    if (__builtin_amdgcn_ballot_w64(views != 0u) == 0ull) return;
+    ACC *gbase = grad_hm + (size_t)bs * g.h * g.w;
+#pragma unroll 1
+    for (int c = 0; c < g.V; ++c) {
+        const float *cm = cam + ((size_t)bs * g.V + c) * SP3D_CAM_STRIDE;
+        float ix, iy;
+        bool isnan;
+        const bool bound = sample_pos_fast(cm, x, y, z, g, ix, iy, isnan) && inb;
+        const Rec r = make_record<1>(bound && !isnan, isnan ? 0.0f : ix, isnan ? 0.0f : iy, g.w, g.h);
+        if ((views >> c) & 1u) {
+            ACC *p = gbase + (size_t)c * view_stride + r.off;
+            if (r.w00 != 0.0f) add(p, gv * r.w00);
+            if (r.w10 != 0.0f) add(p + 1, gv * r.w10);
+            if (r.w01 != 0.0f) add(p + g.w, gv * r.w01);
+            if (r.w11 != 0.0f) add(p + g.w + 1, gv * r.w11);
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------
 // backward on DENSE grids (round 4, "bwd3"): a workgroup owns an 8x8x4 block of voxels and, per view, merges the block's tap
 // gradients in an LDS patch of the heat-map gradient before they go to memory.
 //
@@ -1786,6 +1879,7 @@ struct FwdRequest {
     int layout, Jp;      // SP3D_LAYOUT_* without the flag bits; channels (pixel stride) of a packed pixel
     int io;              // bit 0 = the heat-maps are bf16, bit 1 = the cubes are bf16
     bool one, out_cl, zd, out_aligned;   // one-channel read; channels-last result; z-spectrum result; result 16-byte aligned
+    bool one_train;      // one-channel read that also writes the pass mask (sp3d_unproject_one_fwd_train)
     Geom g;
 };
 
@@ -1810,7 +1904,7 @@ struct Launch {
 struct KernelKey {
     int jp, ps;          // channels gathered; channels between pixels
     int a, b;            // tile: XCD map, unroll; pipe: XCD map, waves; brick: z-spectrum, 0; one-channel: views, chunk; else 0, 0
-    int cl, io;          // channels-last result; FwdRequest::io
+    int cl, io;          // channels-last result; FwdRequest::io (one-channel: 4 = the kernel that also writes the pass mask)
 };
 using PackFn = void (*)(Views, float *, int, int, int);
 using PlanarFn = void (*)(Views, const float *, const float *, const uint8_t *, float *, float *, Geom);
@@ -1874,7 +1968,9 @@ static int find_brick_kernel(const KernelKey &key, const void *&fn, const char *
 
 // one-channel kernel: VT view slots gathered in chunks of CS
 #define SP3D_ONE(VT_, CS_) SP3D_ROW(OneFn, (KernelKey{1, 1, VT_, CS_, false, 0}), unproject_one_kernel, VT_, CS_, false) \
-    SP3D_ROW(OneFn, (KernelKey{1, 1, VT_, CS_, true, 0}), unproject_one_kernel, VT_, CS_, true)
+    SP3D_ROW(OneFn, (KernelKey{1, 1, VT_, CS_, true, 0}), unproject_one_kernel, VT_, CS_, true) \
+    SP3D_ROW(OneFn, (KernelKey{1, 1, VT_, CS_, false, 4}), unproject_one_kernel, VT_, CS_, false, true) \
+    SP3D_ROW(OneFn, (KernelKey{1, 1, VT_, CS_, true, 4}), unproject_one_kernel, VT_, CS_, true, true)
 #define SP3D_PLANAR(JC_) SP3D_ROW(PlanarFn, (KernelKey{JC_, JC_, 0, 0, 0, 0}), unproject_planar_kernel, JC_)
 static int find_one_or_planar_kernel(const KernelKey &key, const void *&fn, const char *&name)
 {
@@ -1970,7 +2066,7 @@ static int resolve_one(const FwdRequest &rq, Launch &L)
 {
     Geom &g = L.g;
     if ((rq.layout != SP3D_LAYOUT_PLANAR && rq.layout != SP3D_LAYOUT_NHWC) || rq.Jp < 1) return SP3D_EINVAL;
-    if (rq.io || g.pass_mask) return SP3D_EUNSUPPORTED;
+    if (rq.io || (g.pass_mask && !rq.one_train)) return SP3D_EUNSUPPORTED;
     if (!(g.J == 4 || (g.J == 1 && !rq.out_cl))) return SP3D_EUNSUPPORTED;
     if (g.w < 2 || g.h < 2 || (int64_t)g.h * g.w > (1 << 24)) return SP3D_EUNSUPPORTED;
     if (rq.out_cl && !rq.out_aligned) return SP3D_EUNSUPPORTED;
@@ -1984,7 +2080,7 @@ static int resolve_one(const FwdRequest &rq, Launch &L)
     const int64_t sample = rq.layout == SP3D_LAYOUT_NHWC ? (int64_t)g.h * row : (int64_t)rq.Jp * g.h * g.w;
     set_launch(L, xcd_grid_blocks(g.B, ptiles, g.xcd_chunk), 64, 0, 3, sample, (int)row, (int)px);
     const int vt = g.V <= 6 ? g.V : (g.V <= 8 ? 8 : (g.V <= 10 ? 10 : (g.V <= 12 ? 12 : 16)));
-    return find_one_or_planar_kernel(KernelKey{1, 1, vt, vt > 8 ? 8 : 4, rq.out_cl, 0}, L.fn, L.name);
+    return find_one_or_planar_kernel(KernelKey{1, 1, vt, vt > 8 ? 8 : 4, rq.out_cl, g.pass_mask ? 4 : 0}, L.fn, L.name);
 }
 
 // Jp = 32 (17..32 joints: the 17 COCO joints of the Shelf / Campus configurations).  A packed fp32 pixel is exactly one
@@ -2074,7 +2170,7 @@ static int fwd_request(FwdRequest &rq, int hm_layout, int Jp, bool ptrs, int B, 
     rq.io = ((hm_layout & SP3D_HM_BF16) ? 1 : 0) | ((hm_layout & SP3D_OUT_BF16) ? 2 : 0);
     rq.one = (hm_layout & SP3D_HM_ONE_CHANNEL) != 0;
     rq.out_cl = (hm_layout & SP3D_OUT_CHANNELS_LAST) != 0;
-    rq.zd = false; rq.out_aligned = true;
+    rq.zd = false; rq.out_aligned = true; rq.one_train = false;
     return SP3D_OK;
 }
 
@@ -2297,15 +2393,17 @@ extern "C" int sp3d_unproject_fwd_plan(int entry, int hm_layout, int Jp, const i
                                        int32_t *records)
 {
     if (!names || !fields || !tuning || !records) return SP3D_ENULL;
-    if (entry < SP3D_PLAN_INDEXED || entry > SP3D_PLAN_TUNING) return SP3D_EINVAL;
+    if (entry < SP3D_PLAN_INDEXED || entry > SP3D_PLAN_ONE_TRAIN) return SP3D_EINVAL;
     const float grid_size[3] = {1.0f, 1.0f, 1.0f};
     if (entry == SP3D_PLAN_ZDFT) hm_layout = SP3D_LAYOUT_NHWC;
     if (entry == SP3D_PLAN_TUNING) hm_layout = SP3D_LAYOUT_NHWC | ((variant & SP3D_TUNING_CHANNELS_LAST) ? SP3D_OUT_CHANNELS_LAST : 0);
+    if (entry == SP3D_PLAN_ONE_TRAIN) hm_layout |= SP3D_HM_ONE_CHANNEL;
     FwdRequest rq;
     int rc = fwd_request(rq, hm_layout, Jp, true, B, V, J, h, w, X, Y, Z, grid_size, 1, 1);
     if (!rc && entry == SP3D_PLAN_STRIDED && out_strides) rc = set_result_strides(rq.g, out_strides, nullptr);
     if (rc) return rc;
-    if (entry == SP3D_PLAN_TRAIN) rq.g.pass_mask = reinterpret_cast<uint16_t *>(records);    // "there is one": never dereferenced
+    rq.one_train = entry == SP3D_PLAN_ONE_TRAIN;
+    if (entry == SP3D_PLAN_TRAIN || rq.one_train) rq.g.pass_mask = reinterpret_cast<uint16_t *>(records);    // "there is one": never dereferenced
     rq.zd = entry == SP3D_PLAN_ZDFT;
     const FwdTuning t = entry == SP3D_PLAN_TUNING ? decode_tuning(variant)
                                                   : (rq.zd ? default_tuning(FWD_BRICK_STACKS) : default_tuning(rq.g, rq.out_cl));
@@ -2344,6 +2442,73 @@ extern "C" int sp3d_unproject_fwd_train(const float *const *hm_views, int hm_lay
     rq.g.sample_of = sample_of;
     rq.g.pass_mask = pass_mask;
     return run_fwd(rq, default_tuning(rq.g, rq.out_cl), hm_views, cam, centers, valid, cubes, grids, stream);
+}
+
+// One-channel training forward: sp3d_unproject_fwd_indexed with SP3D_HM_ONE_CHANNEL (implied) + the pass mask at J = 1, in
+// the words of sp3d_unproject_fwd_train.  The refusals are resolve_one's.
+extern "C" int sp3d_unproject_one_fwd_train(const float *const *hm_views, int hm_layout, int Jp, const float *cam,
+                                            const int32_t *sample_of, const float *centers, const uint8_t *valid,
+                                            float *cubes, float *grids, uint16_t *pass_mask, int P, int V, int J, int h,
+                                            int w, int X, int Y, int Z, const float *grid_size, int W_in, int H_in,
+                                            void *stream)
+{
+    FwdRequest rq;
+    const int rc = fwd_request(rq, hm_layout | SP3D_HM_ONE_CHANNEL, Jp, cam && centers && valid && cubes && pass_mask, P, V,
+                               J, h, w, X, Y, Z, grid_size, W_in, H_in);
+    if (rc) return rc;
+    rq.one_train = true;
+    rq.g.sample_of = sample_of;
+    rq.g.pass_mask = pass_mask;
+    rq.out_aligned = ((uintptr_t)cubes & 15) == 0;
+    return run_fwd(rq, default_tuning(rq.g, rq.out_cl), hm_views, cam, centers, valid, cubes, grids, stream);
+}
+
+// scale == nullptr: fp32 atomics into (V,B,h,w) float; else 64-bit fixed point into (V,B,h,w) int64
+static int one_bwd_impl(const float *cam, const int32_t *sample_of, const float *centers, const uint8_t *valid,
+                        const float *grad_cubes, int64_t grad_cube_stride, const uint16_t *pass_mask, void *grad_acc,
+                        const float *scale, int B, int P, int V, int h, int w, int X, int Y, int Z, const float *grid_size,
+                        int W_in, int H_in, void *stream)
+{
+    Geom g;
+    const int rc = make_geom(g, P, V, 1, h, w, X, Y, Z, grid_size, W_in, H_in);
+    if (rc) return rc;
+    if (B <= 0 || grad_cube_stride < (int64_t)g.N) return SP3D_EINVAL;
+    if (!cam || !centers || !valid || !grad_cubes || !pass_mask || !grad_acc) return SP3D_ENULL;
+    // a clamped 2x2 tap block needs a 2x2 image; its offset inside a plane is a 32-bit int of at most 2^24 pixels
+    if (w < 2 || h < 2 || (int64_t)h * w > (1 << 24)) return SP3D_EUNSUPPORTED;
+    g.sample_of = sample_of;
+    const int tiles = (g.N + 63) / 64;
+    const size_t view_stride = (size_t)B * h * w;
+    const long long gstride = (long long)grad_cube_stride;
+    dim3 grid(xcd_grid_blocks(P, tiles, g.xcd_chunk)), block(64);
+    hipStream_t s = (hipStream_t)stream;
+    if (scale)
+        hipLaunchKernelGGL(unproject_one_bwd_kernel<true>, grid, block, 0, s, cam, centers, valid, grad_cubes, gstride, pass_mask,
+                           grad_acc, view_stride, g, tiles, scale);
+    else
+        hipLaunchKernelGGL(unproject_one_bwd_kernel<false>, grid, block, 0, s, cam, centers, valid, grad_cubes, gstride, pass_mask,
+                           grad_acc, view_stride, g, tiles, scale);
+    return launch_status();
+}
+
+extern "C" int sp3d_unproject_one_bwd(const float *cam, const int32_t *sample_of, const float *centers, const uint8_t *valid,
+                                      const float *grad_cubes, int64_t grad_cube_stride, const uint16_t *pass_mask,
+                                      float *grad_hm, int B, int P, int V, int h, int w, int X, int Y, int Z,
+                                      const float *grid_size, int W_in, int H_in, void *stream)
+{
+    return one_bwd_impl(cam, sample_of, centers, valid, grad_cubes, grad_cube_stride, pass_mask, grad_hm, nullptr, B, P, V, h,
+                        w, X, Y, Z, grid_size, W_in, H_in, stream);
+}
+
+extern "C" int sp3d_unproject_one_bwd_det(const float *cam, const int32_t *sample_of, const float *centers,
+                                          const uint8_t *valid, const float *grad_cubes, int64_t grad_cube_stride,
+                                          const uint16_t *pass_mask, int64_t *grad_fixed, const float *scale, int B, int P,
+                                          int V, int h, int w, int X, int Y, int Z, const float *grid_size, int W_in, int H_in,
+                                          void *stream)
+{
+    if (!scale) return SP3D_ENULL;
+    return one_bwd_impl(cam, sample_of, centers, valid, grad_cubes, grad_cube_stride, pass_mask, grad_fixed, scale, B, P, V, h,
+                        w, X, Y, Z, grid_size, W_in, H_in, stream);
 }
 
 // scatter: which kernel sp3d_unproject_bwd_packed[_det] launches - SP3D_SCATTER_AUTO (by voxel pitch), _PER_TAP (bwd2),

@@ -152,8 +152,8 @@ class _UnprojectFn(torch.autograd.Function):
         hms = [x.detach() for x in heatmaps]
         io = layer.io_dtype
         # one channel of a wider tensor (the root-joint map of the ROOTNET_ROOTHM root nets): read where it lies by the
-        # one-channel kernel - no slice copy, no re-tiling pass, no pack-cache entry.  A heat-map gradient keeps the packed
-        # path below (its backward needs the pass mask).
+        # one-channel kernel - no slice copy, no re-tiling pass, no pack-cache entry.  Under this switch a heat-map gradient
+        # keeps the packed path below (its backward needs the pass mask); one_channel_grad is the switch for that case.
         one = one_channel_source(hms) if (layer.one_channel and mode == "nhwc" and io == torch.float32 and J == 1
                                           and not any(ctx.needs_input_grad[12:])) else None
         if one is not None:
@@ -161,6 +161,29 @@ class _UnprojectFn(torch.autograd.Function):
                                               cube_size, grid_size, layer.img_size, want_grids, channels_last=channels_last,
                                               sample_of=sample_of, out=out, one_channel=True)
             # nothing is saved for backward: no input of this call requires a gradient, so backward() is never entered
+            if grids is None:
+                grids = torch.empty(0, device=cubes.device)
+            ctx.mark_non_differentiable(grids)
+            return cubes, grids
+        # the same channel WITH a heat-map gradient (the root net's unprojection in the root-net and pose-net training stages),
+        # behind a switch of its own: the one-channel training forward writes the pass mask, backward() scatters the one
+        # channel into dense (V,B,h,w) planes - no slice copy, no re-tiling pass, no pack-cache entry, no pad channels
+        one_grad = one_channel_source(hms) if (layer.one_channel_grad and mode == "nhwc" and io == torch.float32 and J == 1
+                                               and any(ctx.needs_input_grad[12:])) else None
+        ctx.one_bwd = None
+        if one_grad is not None:
+            X, Y, Z = cube_size
+            mask = torch.empty((B, X * Y * Z), dtype=torch.int16, device=cam.device)
+            cubes, grids = _lib.unproject_one_fwd_train(hms, one_grad[0], one_grad[1], cam, centers, valid, B,
+                                                        4 if pad_channels else 1, h, w, cube_size, grid_size, layer.img_size,
+                                                        mask, want_grids, channels_last=channels_last, sample_of=sample_of)
+            ctx.packed_bwd = None
+            ctx.one_bwd = (mask, int(heatmaps[0].shape[0]), len(hms), h, w)
+            ctx.wide = False                      # the classifier answers for fp32 heat-maps only
+            ctx.layer = layer
+            ctx.geom = (tuple(grid_size), tuple(cube_size))
+            ctx.sample_of = sample_of
+            ctx.save_for_backward(cam, centers, valid)        # the one-channel backward reads no heat-map
             if grids is None:
                 grids = torch.empty(0, device=cubes.device)
             ctx.mark_non_differentiable(grids)
@@ -220,6 +243,12 @@ class _UnprojectFn(torch.autograd.Function):
             wide = lambda gs: tuple(x.double() for x in gs)
         else:
             wide = tuple
+        if ctx.one_bwd is not None:
+            mask, batch, nv, h, w = ctx.one_bwd
+            grads = _lib.unproject_one_bwd(cam, centers, valid, grad_cubes, mask, batch, nv, h, w, cube_size, grid_size,
+                                           ctx.layer.img_size, sample_of=ctx.sample_of,
+                                           deterministic=ctx.layer.deterministic_backward)
+            return (None,) * 12 + wide(grads)
         if ctx.packed_bwd is not None:
             mask, jp, batch, nv, J, h, w = ctx.packed_bwd
             grads = _lib.unproject_bwd_packed(cam, centers, valid, grad_cubes, mask, batch, nv, J, jp, h, w, cube_size,
@@ -253,6 +282,11 @@ class ProjectLayer(nn.Module):
         # tensor goes through the one-channel kernel, read in place (one_channel_source), instead of slice copy + re-tile +
         # packed kernel.  Same bits either way; off until tools/bench_roothm.py has recorded that it is faster
         self.one_channel = os.environ.get("SP3D_ONE_CHANNEL", "0") not in ("", "0")
+        # opt-in (SP3D_ONE_CHANNEL_GRAD=1 / ``one_channel_grad = True``), independent of ``one_channel``: the same kind of list
+        # WITH a heat-map gradient trains through the one-channel pair (_lib.unproject_one_fwd_train / unproject_one_bwd)
+        # instead of slice copy + re-tile + packed training forward + 4-channel scatter.  Same cubes, same deterministic
+        # gradient bits; off until tools/bench_roothm_grad.py has recorded that it is faster
+        self.one_channel_grad = os.environ.get("SP3D_ONE_CHANNEL_GRAD", "0") not in ("", "0")
 
     @contextlib.contextmanager
     def static_camera_table(self, table: torch.Tensor):
