@@ -457,6 +457,10 @@ int sp3d_upsample2x_scatter(const float *G, float *out, const float *shift, cons
 int sp3d_upsample2x_scatter_head(const float *G, float *head, const float *shift, const float *skip, const float *wout,
                                  const float *bout, int64_t batch, int X, int Y, int Z, int O, int J, void *stream);
 
+/* The whole layer (product, scatter, epilogue, optional output conv) in one kernel: sp3d_upconv2x_fused.
+ * Declared and documented in sp3d_upconv.h. */
+#include "sp3d_upconv.h"
+
 /*
  * GROUPED training-mode batch normalisation on channels-last tensors (round 5): what lets the training pose net run all
  * candidate slots - and the backbone all cameras - as ONE batch and still be the reference's per-call BatchNorm

@@ -99,6 +99,9 @@ ONE_TRAIN_SIGNATURES = {                        # include/sp3d_one_train.h (incl
     "sp3d_unproject_one_bwd": "i: ppppp l pp iiiiiiii p ii p",
     "sp3d_unproject_one_bwd_det": "i: ppppp l ppp iiiiiiii p ii p",
 }
+UPCONV_SIGNATURES = {                           # include/sp3d_upconv.h (included by sp3d.h): required like SIGNATURES
+    "sp3d_upconv2x_fused": "i: ppppppp l iiiiii p",
+}
 EXPORTS = list(SIGNATURES)
 
 _lib = None
@@ -148,7 +151,8 @@ def load():
             f"{LIB_PATH} not found - the HIP extension is not built. Run `python -m selfpose3d_amd.build` "
             "(hipcc, gfx950). There is no CPU fallback for the unprojection path.")
     lib = C.CDLL(LIB_PATH)
-    for table, required in ((SIGNATURES, True), (ONE_TRAIN_SIGNATURES, True), (TUNING_SIGNATURES, False)):
+    for table, required in ((SIGNATURES, True), (ONE_TRAIN_SIGNATURES, True), (UPCONV_SIGNATURES, True),
+                            (TUNING_SIGNATURES, False)):
         for name, sig in table.items():
             if required or hasattr(lib, name):
                 ret, args = sig.split(":")
@@ -923,37 +927,77 @@ def wino_fused_conv3d_(x: torch.Tensor, U: torch.Tensor, shift: torch.Tensor, mo
     return y
 
 
-def upsample2x_(x: torch.Tensor, w_gemm: torch.Tensor, shift: torch.Tensor, skip: torch.Tensor) -> torch.Tensor:
-    """ConvTranspose3d(k=2,s=2) + shift + ReLU + skip on channels_last_3d activations: one rocBLAS GEMM on the
-    (voxels, Cin) view with w_gemm (Cin, 8*O) [columns (i,j,k,o)] + sp3d_upsample2x_scatter."""
+def upconv_weights_split(w_gemm: torch.Tensor) -> torch.Tensor:
+    """(Cin, 8*O) GEMM-form weights of a ConvTranspose3d(2, stride 2) [columns (i,j,k,o)] -> the bf16 operand records
+    sp3d_upconv2x_fused reads: (8, O/32, Cin/8, 2, 32, 6, 4) bfloat16 = per (tap, 32 outputs) the three B operands {hi,lo}
+    {hi,hi} {mid,mid} of 4 channels each, channel = 8*chunk + 4*half + q (the records of conv_weights_split)"""
+    Cc, O = int(w_gemm.shape[0]), int(w_gemm.shape[1]) // 8
+    U = w_gemm.float().reshape(Cc, 8 * O // 32, 32).permute(1, 0, 2).contiguous()      # [(tap, o/32), c, o%32]
+    pc = wino_weights_split(U, 8)                                                       # [.., piece (mid,hi,lo), 4]
+    mid, hi, lo = pc[..., 0, :], pc[..., 1, :], pc[..., 2, :]
+    return torch.stack([hi, lo, hi, hi, mid, mid], -2).reshape(8, O // 32, Cc // 8, 2, 32, 6, 4).contiguous()
+
+
+def _require_upconv_split(w_split: torch.Tensor, Cc: int, O: int, x: torch.Tensor):
+    """the kernel reads Cc * 8 * O twelve-byte records behind this pointer: refuse anything that is not exactly that"""
+    if w_split.device != x.device or w_split.dtype != torch.bfloat16 or not w_split.is_contiguous() or \
+            w_split.numel() != Cc * 8 * O * 6:
+        raise Sp3dError(f"w_split must be upconv_weights_split(w_gemm) of the ({Cc}, {8 * O}) weight on {x.device}; got "
+                        f"{tuple(w_split.shape)}, {w_split.dtype}, {w_split.device}, contiguous={w_split.is_contiguous()}")
+
+
+def upconv_fused_covers(Cc: int, O: int, head: bool) -> bool:
+    """the shapes sp3d_upconv2x_fused has a kernel for; SP3D_FUSE_UPCONV=0 sends every shape down the GEMM + scatter path"""
+    if os.environ.get("SP3D_FUSE_UPCONV", "1") in ("0", ""):
+        return False
+    return (Cc, O, bool(head)) in ((64, 32, True), (128, 64, False))
+
+
+def upsample2x_(x: torch.Tensor, w_gemm: torch.Tensor, shift: torch.Tensor, skip: torch.Tensor,
+                w_split: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """ConvTranspose3d(k=2,s=2) + shift + ReLU + skip on channels_last_3d activations.  With w_split
+    (upconv_weights_split(w_gemm)) and a shape upconv_fused_covers: one kernel, sp3d_upconv2x_fused.  Otherwise: one rocBLAS
+    GEMM on the (voxels, Cin) view with w_gemm (Cin, 8*O) [columns (i,j,k,o)] + sp3d_upsample2x_scatter."""
     lib = load()
     _require_cuda(x, "x")
     B, Cc, X, Y, Z = (int(v) for v in x.shape)
     _require_cl3d_f32(x, "upsample2x_")
     O = int(w_gemm.shape[1]) // 8
-    G = torch.matmul(x.permute(0, 2, 3, 4, 1).reshape(-1, Cc), w_gemm)
     out = _empty_cl3d(B, O, 2 * X, 2 * Y, 2 * Z, x.device)
     skip = _as_cl3d(skip)
+    if w_split is not None and upconv_fused_covers(Cc, O, False):
+        _require_upconv_split(w_split, Cc, O, x)
+        check(lib.sp3d_upconv2x_fused(x.data_ptr(), w_split.data_ptr(), shift.data_ptr(), skip.data_ptr(), None, None,
+                                      out.data_ptr(), B, X, Y, Z, Cc, O, 0, _stream(x.device)), "sp3d_upconv2x_fused")
+        return out
+    G = torch.matmul(x.permute(0, 2, 3, 4, 1).reshape(-1, Cc), w_gemm)
     check(lib.sp3d_upsample2x_scatter(G.data_ptr(), out.data_ptr(), shift.data_ptr(), skip.data_ptr(), B, X, Y, Z, O,
                                       _stream(x.device)), "sp3d_upsample2x_scatter")
     return out
 
 
 def upsample2x_head_(x: torch.Tensor, w_gemm: torch.Tensor, shift: torch.Tensor, skip: torch.Tensor, w_out: torch.Tensor,
-                     b_out: torch.Tensor) -> torch.Tensor:
+                     b_out: torch.Tensor, w_split: Optional[torch.Tensor] = None) -> torch.Tensor:
     """upsample2x_ fused with the 1x1x1 output conv that is its only consumer: returns (B,J,2X,2Y,2Z) as a permuted view
-    of a (B,2X,2Y,2Z,J) tensor (for J = 1 that is also the dense NCDHW tensor)"""
+    of a (B,2X,2Y,2Z,J) tensor (for J = 1 that is also the dense NCDHW tensor).  With w_split (upconv_weights_split(w_gemm))
+    and a shape upconv_fused_covers: one kernel, sp3d_upconv2x_fused."""
     lib = load()
     _require_cuda(x, "x")
     B, Cc, X, Y, Z = (int(v) for v in x.shape)
     _require_cl3d_f32(x, "upsample2x_head_")
     O = int(w_gemm.shape[1]) // 8
     J = int(w_out.shape[0])
-    G = torch.matmul(x.permute(0, 2, 3, 4, 1).reshape(-1, Cc), w_gemm)
     skip = _as_cl3d(skip)
     wo = w_out.reshape(J, O).contiguous().float()
-    bo = (b_out if b_out is not None else torch.zeros(J, device=x.device)).contiguous().float()
     head = _empty_cl3d(B, J, 2 * X, 2 * Y, 2 * Z, x.device)
+    if w_split is not None and J <= 32 and upconv_fused_covers(Cc, O, True):
+        _require_upconv_split(w_split, Cc, O, x)
+        bo = None if b_out is None else b_out.contiguous().float()
+        check(lib.sp3d_upconv2x_fused(x.data_ptr(), w_split.data_ptr(), shift.data_ptr(), skip.data_ptr(), wo.data_ptr(),
+                                      _opt(bo), head.data_ptr(), B, X, Y, Z, Cc, O, J, _stream(x.device)), "sp3d_upconv2x_fused")
+        return head
+    G = torch.matmul(x.permute(0, 2, 3, 4, 1).reshape(-1, Cc), w_gemm)
+    bo = (b_out if b_out is not None else torch.zeros(J, device=x.device)).contiguous().float()
     check(lib.sp3d_upsample2x_scatter_head(G.data_ptr(), head.data_ptr(), shift.data_ptr(), skip.data_ptr(), wo.data_ptr(),
                                            bo.data_ptr(), B, X, Y, Z, O, J, _stream(x.device)), "sp3d_upsample2x_scatter_head")
     return head

@@ -14,6 +14,7 @@
 #include <stdint.h>
 
 #include "../../include/sp3d.h"
+#include "sp3d_split.h"
 
 namespace sp3d {
 
@@ -193,7 +194,6 @@ extern "C" int sp3d_wino_output(const float *M, float *y, const float *shift, co
 
 namespace sp3d {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 #ifdef SP3D_WF_TIMELINE
 __device__ unsigned long long *g_wf_tl = nullptr;
 #define WF_STAMP(slot) do { __builtin_amdgcn_sched_barrier(0); if (tl && lane == 0) tl[slot] = __builtin_readcyclecounter(); __builtin_amdgcn_sched_barrier(0); } while (0)
@@ -400,26 +400,6 @@ __global__ __launch_bounds__(64) void wino_fused_kernel(const float *__restrict_
 // so 8 channels cost 3 MFMAs of 8 passes instead of 4 of 16: 2.7x fewer matrix cycles; the weights are split once on
 // the host (U3: per (point, chunk, lane half, output) one 24-byte record [bm(4ch) bh(4ch) bl(4ch)]).
 // ------------------------------------------------------------------------------------------
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4_a8 __attribute__((ext_vector_type(4), aligned(8)));
-typedef unsigned u32x2_a8 __attribute__((ext_vector_type(2), aligned(8)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ unsigned pack_bf16(float a, float b)
-{
-    f32x2 f = {a, b};
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(f, bf16x2));
-}
-__device__ __forceinline__ float bf16_lo(unsigned u) { return __uint_as_float(u << 16); }
-__device__ __forceinline__ float bf16_hi(unsigned u) { return __uint_as_float(u & 0xffff0000u); }
-__device__ __forceinline__ f32x16 mfma_bf16(u32x4 a, u32x4 b, f32x16 c)
-{
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-}
-
 struct WfB { u32x4 mh; u32x2 l; };              // [bm01 bm23 bh01 bh23] [bl01 bl23]
 
 template <int C, int MODE>
@@ -1001,26 +981,6 @@ __device__ unsigned long long *g_cd_tl = nullptr;      // [wave 6][item 64][4] s
 #else
 #define CD_STAMP(slot) do { (void)item; } while (0)
 #endif
-
-// a = hi + mid + lo, each a bf16 (exact: 24 mantissa bits), as the two A operands {lo,hi} and {hi,mid} of 4 channels
-__device__ __forceinline__ void split3(const float4 a, u32x4 &q0, u32x4 &q1)
-{
-    const unsigned hi01 = pack_bf16(a.x, a.y), hi23 = pack_bf16(a.z, a.w);
-    // a non-finite input has a non-finite hi piece and (inf - inf | NaN - NaN) = NaN as its residual: v_med3_f32(r, 0, r)
-    // is r for every number and 0 for NaN (one instruction per value), so mid = lo = 0 and the value travels in the hi
-    // piece alone.  The outputs that come out non-finite are then EXACTLY those of an fp32 convolution; their kind is
-    // the convolution's or NaN (inf * w is formed from the weight's three pieces, whose signs differ):
-    // tests/test_gpu_parity.py::test_direct_conv3_split_kernel_nonfinite_inputs.
-    const float r0 = __builtin_amdgcn_fmed3f(a.x - bf16_lo(hi01), 0.0f, a.x - bf16_lo(hi01));
-    const float r1 = __builtin_amdgcn_fmed3f(a.y - bf16_hi(hi01), 0.0f, a.y - bf16_hi(hi01));
-    const float r2 = __builtin_amdgcn_fmed3f(a.z - bf16_lo(hi23), 0.0f, a.z - bf16_lo(hi23));
-    const float r3 = __builtin_amdgcn_fmed3f(a.w - bf16_hi(hi23), 0.0f, a.w - bf16_hi(hi23));
-    const unsigned mid01 = pack_bf16(r0, r1), mid23 = pack_bf16(r2, r3);
-    const unsigned lo01 = pack_bf16(r0 - bf16_lo(mid01), r1 - bf16_hi(mid01));
-    const unsigned lo23 = pack_bf16(r2 - bf16_lo(mid23), r3 - bf16_hi(mid23));
-    q0 = u32x4{lo01, lo23, hi01, hi23};
-    q1 = u32x4{hi01, hi23, mid01, mid23};
-}
 
 template <int C, int MODE>
 __global__ __launch_bounds__(64 * (4 + CD_PROD)) __attribute__((amdgpu_waves_per_eu(2, 2)))

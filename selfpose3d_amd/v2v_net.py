@@ -280,10 +280,12 @@ class _Res(NamedTuple):
 
 
 class _Up(NamedTuple):
-    """a folded ConvTranspose3d(2, stride 2): weight (Cin, Cout, 2, 2, 2), shift, and the weight in GEMM form (Cin, 8*Cout)"""
+    """a folded ConvTranspose3d(2, stride 2): weight (Cin, Cout, 2, 2, 2), shift, the weight in GEMM form (Cin, 8*Cout)
+    and, for the shapes the one-kernel form covers, the GEMM form in three bf16 pieces (_lib.upconv_weights_split)"""
     wT: torch.Tensor
     shift: torch.Tensor
     wg: torch.Tensor
+    split: Optional[torch.Tensor] = None
 
 
 class _FoldedV2V:
@@ -346,6 +348,7 @@ class _FoldedV2V:
         return _Conv(w, shift, u, split, direct)
 
     def _build(self):
+        from . import _lib
         n, layers = self.net, {}
         layers["front"] = _Conv(*self._fold(n.front_layers[0].block[0], n.front_layers[0].block[1]))
         ed = n.encoder_decoder
@@ -364,7 +367,9 @@ class _FoldedV2V:
             wT, sT = self._fold(blk[0], blk[1], transposed=True)
             # (Cin, Cout, 2,2,2) -> GEMM form (Cin, 8*Cout), columns ordered (i,j,k,o): see _up2x
             wg = wT.permute(0, 2, 3, 4, 1).reshape(wT.shape[0], 8 * wT.shape[1]).contiguous()
-            layers[name] = _Up(wT, sT, wg)
+            # 128 -> 64 and 64 -> 32 (+ output conv): product and scatter in one kernel (sp3d_upconv2x_fused)
+            fused = wg.is_cuda and (int(wT.shape[0]), int(wT.shape[1])) in ((128, 64), (64, 32))
+            layers[name] = _Up(wT, sT, wg, _lib.upconv_weights_split(wg) if fused else None)
         # the spectra belong to the old weights; the padded buffers go with them, a caller's view of one is then copied
         self.layers, self.spectra, self.xpad = layers, {}, {}
 
@@ -612,10 +617,10 @@ class _FoldedV2V:
         x = self._up2x(x, "decoder_upsample2", skip2)
         x = self._res(x, "decoder_res1")
         o = self.net.output_layer
-        wT, sT, wg = self.layers["decoder_upsample1"]
+        wT, sT, wg, w3 = self.layers["decoder_upsample1"]
         if self.net.winograd and is_cl(x) and wg.is_cuda and wT.shape[1] == 32 and x.dtype == torch.float32:
             # the last up-sampling layer's only consumer is the 1x1x1 output conv: one kernel, no 32-channel tensor
-            return _lib.upsample2x_head_(x, wg, sT, skip1, o.weight, o.bias)
+            return _lib.upsample2x_head_(x, wg, sT, skip1, o.weight, o.bias, w3)
         x = self._up2x(x, "decoder_upsample1", skip1)
         return self._conv1(x, o.weight, o.bias)
 
@@ -629,11 +634,12 @@ class _FoldedV2V:
 
     def _up2x(self, x, name, skip):
         """ConvTranspose3d(2, stride 2) + BN + ReLU + skip: no overlapping taps, so on channels-last activations it is
-        one GEMM + a scatter with the epilogue (sp3d_upsample2x_scatter) instead of MIOpen's backward-data kernel"""
+        one product + a scatter with the epilogue instead of MIOpen's backward-data kernel - in one kernel
+        (sp3d_upconv2x_fused) where the plan holds split weights, else a library GEMM + sp3d_upsample2x_scatter"""
         from . import _lib
-        wT, sT, wg = self.layers[name]
+        wT, sT, wg, w3 = self.layers[name]
         if self.net.winograd and is_cl(x) and wg.is_cuda and wT.shape[1] % 4 == 0:
-            return _lib.upsample2x_(x, wg, sT, skip)
+            return _lib.upsample2x_(x, wg, sT, skip, w3)
         return _lib.channel_shift_act_(F.conv_transpose3d(x, wT, None, 2), sT, 3, skip)
 
     def _conv1(self, x, w, bias=None):
