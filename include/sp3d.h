@@ -443,6 +443,10 @@ int sp3d_wino_fused_split64(const float *x, const void *U3, float *y, const floa
 int sp3d_conv3_split(const float *x, const void *W3, float *y, const float *shift, const float *residual, int mode, int B,
                      int X, int Y, int Z, int C, int O, void *stream);
 
+/* These two convolutions with a residual block's 1x1x1 skip projection on their accumulators: sp3d_conv3_split_skip,
+ * sp3d_wino_fused_split64_skip.  Declared and documented in sp3d_skip_fold.h. */
+#include "sp3d_skip_fold.h"
+
 /*
  * Scatter + epilogue of ConvTranspose3d(kernel 2, stride 2) -> BatchNorm -> ReLU (+ skip) (lib/models/v2v_net.py:57-69,
  * 100-108) once the layer has been computed as one GEMM G (batch*X*Y*Z, 8*O) with column order (i,j,k,o):

@@ -102,6 +102,10 @@ ONE_TRAIN_SIGNATURES = {                        # include/sp3d_one_train.h (incl
 UPCONV_SIGNATURES = {                           # include/sp3d_upconv.h (included by sp3d.h): required like SIGNATURES
     "sp3d_upconv2x_fused": "i: ppppppp l iiiiii p",
 }
+SKIP_FOLD_SIGNATURES = {                        # include/sp3d_skip_fold.h (included by sp3d.h): required like SIGNATURES
+    "sp3d_conv3_split_skip": "i: pppppp iiiiiii p",
+    "sp3d_wino_fused_split64_skip": "i: pppppp iiiiiii p",
+}
 EXPORTS = list(SIGNATURES)
 
 _lib = None
@@ -151,7 +155,7 @@ def load():
             f"{LIB_PATH} not found - the HIP extension is not built. Run `python -m selfpose3d_amd.build` "
             "(hipcc, gfx950). There is no CPU fallback for the unprojection path.")
     lib = C.CDLL(LIB_PATH)
-    for table, required in ((SIGNATURES, True), (ONE_TRAIN_SIGNATURES, True), (UPCONV_SIGNATURES, True),
+    for table, required in ((SIGNATURES, True), (ONE_TRAIN_SIGNATURES, True), (UPCONV_SIGNATURES, True), (SKIP_FOLD_SIGNATURES, True),
                             (TUNING_SIGNATURES, False)):
         for name, sig in table.items():
             if required or hasattr(lib, name):
@@ -858,18 +862,39 @@ def wino_weights_split(U: torch.Tensor, chunk: int = 8) -> torch.Tensor:
 
 def conv_weights_split(w: torch.Tensor) -> torch.Tensor:
     """(O,C,3,3,3) conv weights -> the bf16 operand records sp3d_conv3_split reads: (27, C/8, 2, O, 6, 4) bfloat16 = the
-    three B operands {hi,lo} {hi,hi} {mid,mid} of 4 channels each, tap = kz*9 + ky*3 + kx, channel = 8*chunk + 4*half + q"""
+    three B operands {hi,lo} {hi,hi} {mid,mid} of 4 channels each, tap = kz*9 + ky*3 + kx, channel = 8*chunk + 4*half + q.
+    A (O,C,1,1,1) weight gives the one-tap records (1, C/8, 2, O, 6, 4) of a folded skip projection."""
     O, Cc = int(w.shape[0]), int(w.shape[1])
-    pc = wino_weights_split(w.float().permute(4, 3, 2, 1, 0).reshape(27, Cc, O).contiguous(), 8)    # [.., piece (mid,hi,lo), 4]
+    taps = int(w.shape[2]) * int(w.shape[3]) * int(w.shape[4])      # 27, or 1: the 1x1x1 skip projection (sp3d_conv3_split_skip)
+    pc = wino_weights_split(w.float().permute(4, 3, 2, 1, 0).reshape(taps, Cc, O).contiguous(), 8)  # [.., piece (mid,hi,lo), 4]
     mid, hi, lo = pc[..., 0, :], pc[..., 1, :], pc[..., 2, :]
     return torch.stack([hi, lo, hi, hi, mid, mid], -2).contiguous()        # the B operands {bh,bl} {bh,bh} {bm,bm}
 
 
+def skip_fold_enabled() -> bool:
+    """SP3D_FOLD_SKIP=0 keeps the 1x1x1 skip projections of the plan's residual blocks a library GEMM + residual epilogue"""
+    return os.environ.get("SP3D_FOLD_SKIP", "1") not in ("0", "")
+
+
+def _require_skip(xs: torch.Tensor, skip_w: torch.Tensor, x: torch.Tensor, CS: int, numel: int, who: str):
+    """the folded skip's operands: xs the block input (B,CS,X,Y,Z) channels_last_3d on x's grid, skip_w exactly the records
+    the kernel reads behind the pointer"""
+    _require_cl3d_f32(xs, who)
+    if xs.device != x.device or tuple(xs.shape) != (x.shape[0], CS) + tuple(x.shape[2:]):
+        raise Sp3dError(f"{who}: xs must be ({x.shape[0]}, {CS}, ...) on the grid and device of x, got {tuple(xs.shape)} on {xs.device}")
+    if skip_w.device != x.device or skip_w.dtype != torch.bfloat16 or not skip_w.is_contiguous() or skip_w.numel() != numel:
+        raise Sp3dError(f"{who}: skip_w must be the split records of the ({x.shape[1]}, {CS}, 1, 1, 1) weight on {x.device}; got "
+                        f"{tuple(skip_w.shape)}, {skip_w.dtype}, {skip_w.device}, contiguous={skip_w.is_contiguous()}")
+
+
 def conv3_split_(x: torch.Tensor, W3: torch.Tensor, shift: torch.Tensor, mode: int,
-                 residual: Optional[torch.Tensor] = None) -> torch.Tensor:
+                 residual: Optional[torch.Tensor] = None, *, xs: Optional[torch.Tensor] = None,
+                 skip_w: Optional[torch.Tensor] = None) -> torch.Tensor:
     """3x3x3 stride-1 'same' conv of channels_last_3d x with the fused epilogue, direct (implicit GEMM) on the bf16 matrix
     pipe with exact three-piece splits; W3 = conv_weights_split(w).  Returns the channels_last_3d result (B,O,X,Y,Z).
-    (Round 3's chained form - split activations handed from layer to layer - measured no gain and was removed in round 4.)"""
+    (Round 3's chained form - split activations handed from layer to layer - measured no gain and was removed in round 4.)
+    With xs (B,16,X,Y,Z) and skip_w = conv_weights_split of the (32,16,1,1,1) skip weight: relu(conv3(x) + skip_w . xs + shift)
+    in the same kernel (sp3d_conv3_split_skip; mode must be 1 and residual None - the projection is the residual)."""
     lib = load()
     _require_cuda(x, "x")
     B, Cc, X, Y, Z = (int(v) for v in x.shape)
@@ -877,6 +902,14 @@ def conv3_split_(x: torch.Tensor, W3: torch.Tensor, shift: torch.Tensor, mode: i
     O = int(W3.shape[3])
     dev = x.device
     y = _empty_cl3d(B, O, X, Y, Z, dev)
+    if xs is not None or skip_w is not None:
+        if xs is None or skip_w is None or int(mode) != 1 or residual is not None:
+            raise Sp3dError("conv3_split_: the folded skip takes xs AND skip_w, mode 1 and no residual")
+        CS = 16
+        _require_skip(xs, skip_w, x, CS, CS * O * 6, "conv3_split_")
+        check(lib.sp3d_conv3_split_skip(x.data_ptr(), W3.data_ptr(), y.data_ptr(), shift.data_ptr(), xs.data_ptr(),
+                                        skip_w.data_ptr(), B, X, Y, Z, Cc, O, CS, _stream(dev)), "sp3d_conv3_split_skip")
+        return y
     if residual is not None:
         residual = _as_cl3d(residual)
     check(lib.sp3d_conv3_split(x.data_ptr(), W3.data_ptr(), y.data_ptr(), shift.data_ptr(), _opt(residual), int(mode),
@@ -906,16 +939,27 @@ def wino_conv3d_(x: torch.Tensor, U: torch.Tensor, shift: torch.Tensor, mode: in
 
 
 def wino_fused_conv3d_(x: torch.Tensor, U: torch.Tensor, shift: torch.Tensor, mode: int,
-                       residual: Optional[torch.Tensor] = None, U3: Optional[torch.Tensor] = None) -> torch.Tensor:
+                       residual: Optional[torch.Tensor] = None, U3: Optional[torch.Tensor] = None, *,
+                       xs: Optional[torch.Tensor] = None, skip_w: Optional[torch.Tensor] = None) -> torch.Tensor:
     """one-launch Winograd 3x3x3 conv (C = 16 | 32 -> O = 32; with U3 also C = 32 | 64 -> O = 64) of channels_last_3d x
     with the fused epilogue; with U3 (wino_weights_split(U, 8 | 16)) the products run as exact three-piece bf16 splits
-    on the bf16 matrix pipe"""
+    on the bf16 matrix pipe.  With U3, xs (B,32,X,Y,Z) and skip_w = wino_weights_split of the (1,32,64) skip weight, chunk 16
+    (C = O = 64): relu(conv3(x) + skip_w . xs + shift) in the same kernel (sp3d_wino_fused_split64_skip; mode 1, no residual)."""
     lib = load()
     _require_cuda(x, "x")
     B, Cc, X, Y, Z = (int(v) for v in x.shape)
     _require_cl3d_f32(x, "wino_fused_conv3d_")
     O = int(U.shape[2])
     y = _empty_cl3d(B, O, X, Y, Z, x.device)
+    if xs is not None or skip_w is not None:
+        if xs is None or skip_w is None or U3 is None or int(mode) != 1 or residual is not None:
+            raise Sp3dError("wino_fused_conv3d_: the folded skip takes U3, xs AND skip_w, mode 1 and no residual")
+        CS = 32
+        _require_skip(xs, skip_w, x, CS, CS * O * 3, "wino_fused_conv3d_")
+        check(lib.sp3d_wino_fused_split64_skip(x.data_ptr(), U3.data_ptr(), y.data_ptr(), shift.data_ptr(), xs.data_ptr(),
+                                               skip_w.data_ptr(), B, X, Y, Z, Cc, O, CS, _stream(x.device)),
+              "sp3d_wino_fused_split64_skip")
+        return y
     if residual is not None:
         residual = _as_cl3d(residual)
     if U3 is None:

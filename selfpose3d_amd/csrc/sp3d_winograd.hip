@@ -640,17 +640,28 @@ constexpr int W16_RX = 10, W16_RY = 10, W16_RZ = 4, W16_VS = 16;
 constexpr int W16_ROW = W16_RX * W16_VS + 4;
 constexpr int W16_LDS = W16_RY * W16_RZ * W16_ROW;               // 6 560 floats = 26 240 B
 
+// ReLU of the kernels that fold a skip projection: a NaN of the projection's input stays a NaN (torch.relu); fmaxf, which
+// the other instantiations keep, returns 0 for it
+__device__ __forceinline__ float relu_keep_nan(float v) { return v < 0.0f ? 0.0f : v; }
+
 __device__ __forceinline__ f32x4 mfma16_bf16(u32x4 a, u32x4 b, f32x4 c)
 {
     return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
 }
 
-template <int C, int MODE, int NBW, int KS>
+// SKIP: the 1x1x1 projection of a residual block's input on the same accumulators (they are final outputs: acc[a][n], a =
+// output position inside the tile, D rows = tiles), y = epilogue(conv3(x) + WS . xs + shift): xs (B,X,Y,Z,32) channels-last,
+// WS = [mid hi lo] records of one point [chunk 2][group 4][output 64].  Channel group kg takes skip chunk kg before the LDS
+// reduction, when the registers of the main loop are free: lane (tl, q) supplies A row = tile tl, channels 16 kg + 4 q .. + 3
+// of voxel (tile, a) - 8 rows, 8 splits and 48 matrix instructions per wave.
+template <int C, int MODE, int NBW, int KS, bool SKIP = false>
 __global__ __launch_bounds__(64 * (4 / NBW) * KS) __attribute__((amdgpu_waves_per_eu(NBW <= 2 ? 2 : 1))) void wino_fused16_kernel(const float *__restrict__ x,
                                                                           const unsigned *__restrict__ U3,
                                                                           float *__restrict__ y, const float *__restrict__ shift,
                                                                           const float *__restrict__ res, int B, int X, int Y,
-                                                                          int Z, int NBX, int NBY, int NBZ)
+                                                                          int Z, int NBX, int NBY, int NBZ,
+                                                                          const float *__restrict__ xs = nullptr,
+                                                                          const unsigned *__restrict__ WS = nullptr)
 {
     // workgroup = KS channel groups x (4 / NBW) output groups of one wave each: channel group kg owns the 16-channel
     // chunks kg, kg + KS, ... (its own staged region), output group ow owns outputs 16*NBW*ow ...; the KS partial sums
@@ -838,6 +849,45 @@ __global__ __launch_bounds__(64 * (4 / NBW) * KS) __attribute__((amdgpu_waves_pe
         }
     }
 
+    if (SKIP) {
+        constexpr int CS = 32;
+        static_assert(!SKIP || KS * 16 == CS, "one skip chunk per channel group");
+        // the lane's coordinates are derived again here, from a copy the compiler cannot trace: what it would otherwise carry
+        // through the main loop for this block costs that loop three spilled registers (252 + these)
+        int ln = lane;
+        asm volatile("" : "+v"(ln));
+        const int stl = ln & 15, sq = ln >> 4;
+        // rows first: voxels outside the volume (edge blocks) read a clamped address, their outputs are never stored
+        const float *xsb = xs + (int64_t)b * X * Y * Z * CS + 16 * kg + 4 * sq;
+        float4 sx[8];
+#pragma unroll
+        for (int a = 0; a < 8; ++a) {
+            const int xo = min(ox0 + 2 * (stl & 3) + (a >> 2), X - 1), yo = min(oy0 + 2 * (stl >> 2) + ((a >> 1) & 1), Y - 1);
+            const int zo = min(oz0 + (a & 1), Z - 1);
+            sx[a] = *reinterpret_cast<const float4 *>(xsb + ((xo * Y + yo) * Z + zo) * CS);
+        }
+        WfB sw[NBW];
+#pragma unroll
+        for (int n = 0; n < NBW; ++n) {
+            const unsigned *r = WS + ((kg * 4 + sq) * O + (ow * NBW + n) * 16 + stl) * 6;
+            sw[n].mh = *reinterpret_cast<const u32x4_a8 *>(r);
+            sw[n].l = *reinterpret_cast<const u32x2_a8 *>(r + 4);
+        }
+#pragma unroll
+        for (int a = 0; a < 8; ++a) {
+            const u32x6 p = split3_pieces(sx[a]);           // [lo01 lo23 hi01 hi23 mid01 mid23]
+            const u32x4 Qlh = split3_q0(p), Qhh = {p[2], p[3], p[2], p[3]}, Qmm = {p[4], p[5], p[4], p[5]};
+#pragma unroll
+            for (int n = 0; n < NBW; ++n) {
+                const u32x4 Bmh = sw[n].mh;
+                const u32x4 Bhl = {sw[n].mh.z, sw[n].mh.w, sw[n].l.x, sw[n].l.y};
+                acc[a][n] = mfma16_bf16(Qhh, Bmh, acc[a][n]);
+                acc[a][n] = mfma16_bf16(Qmm, Bmh, acc[a][n]);
+                acc[a][n] = mfma16_bf16(Qlh, Bhl, acc[a][n]);
+            }
+        }
+    }
+
     if (KS > 1) {                                   // partial sums of channel groups 1.. -> group 0, through LDS
         __syncthreads();                            // every region has been read for the last time
         f32x4 *red = reinterpret_cast<f32x4 *>(lds);
@@ -883,7 +933,7 @@ __global__ __launch_bounds__(64 * (4 / NBW) * KS) __attribute__((amdgpu_waves_pe
                 for (int v = 0; v < 4; ++v) {
                     float val = acc[a][n][v] + sh;
                     if (MODE == 2) val += rv[a][v];
-                    if (MODE >= 1) val = fmaxf(val, 0.0f);
+                    if (MODE >= 1) val = SKIP ? relu_keep_nan(val) : fmaxf(val, 0.0f);
                     if (MODE == 3) val += rv[a][v];
                     y[obase + off[v] + (((a >> 2) * Y + ((a >> 1) & 1)) * Z + (a & 1)) * O] = val;
                 }
@@ -922,7 +972,7 @@ __global__ __launch_bounds__(64 * (4 / NBW) * KS) __attribute__((amdgpu_waves_pe
                     const int64_t idx = ((((int64_t)b * X + xo) * Y + yo) * Z + zo) * O + o;
                     float val = acc[a][n][v] + sh;
                     if (MODE == 2) val += rv[a][v];
-                    if (MODE >= 1) val = fmaxf(val, 0.0f);
+                    if (MODE >= 1) val = SKIP ? relu_keep_nan(val) : fmaxf(val, 0.0f);
                     if (MODE == 3) val += rv[a][v];
                     y[idx] = val;
                 }
@@ -982,13 +1032,21 @@ __device__ unsigned long long *g_cd_tl = nullptr;      // [wave 6][item 64][4] s
 #define CD_STAMP(slot) do { (void)item; } while (0)
 #endif
 
-template <int C, int MODE>
+// SKIP: the 1x1x1 projection of a residual block's input on the same accumulators, y = epilogue(conv3(x) + WS . xs + shift):
+// xs (B,X,Y,Z,16) channels-last, WS = CdRec records of one tap [chunk 2][half 2][output 32].  Consumer waves only: lane
+// (t, h) is A row = voxel (4 wave + i, t & 7, t >> 3), channels 8 chunk + 4 h .. + 3 - one float4 per (i, chunk), split
+// and multiplied (24 matrix instructions) between the last step of the block's last chunk and the epilogue: once per block a
+// workgroup walks.  A voxel of xs is 64 bytes, one cache line for both chunks and both lane halves: the last (dy,dz) step
+// requests the first value of each row (4 registers - all eight rows held over that step spill: 256 + 72 B of scratch), the
+// rest are cache hits after the step.
+template <int C, int MODE, bool SKIP = false>
 __global__ __launch_bounds__(64 * (4 + CD_PROD)) __attribute__((amdgpu_waves_per_eu(2, 2)))
 void conv3_split_kernel(const float *__restrict__ x, const unsigned *__restrict__ W3, float *__restrict__ y,
                         const float *__restrict__ shift, const float *__restrict__ res, int B, int X, int Y, int Z, int NBX,
-                        int NBY, int NBZ, int nblocks)
+                        int NBY, int NBZ, int nblocks, const float *__restrict__ xs = nullptr,
+                        const unsigned *__restrict__ WS = nullptr)
 {
-    constexpr int O = 32, NCH = C / 8;
+    constexpr int O = 32, NCH = C / 8, CS = 16;
     // operand roles: a split result wants (voxel, 4 consecutive channels) per lane = weights as the A operand (rows), an
     // fp32-only result wants (channel, 16 voxels) per lane = full 128-byte rows per store instruction (the transposed form's
     // 32-byte pieces cost 8-10 k cycles per block against 3-6 k)
@@ -1120,9 +1178,25 @@ void conv3_split_kernel(const float *__restrict__ x, const unsigned *__restrict_
         Opnd a0, a1;
         load_a(0, a0);
         const int q0 = item * 9;
+        float s0[4];                                       // SKIP: the first value of each xs row of this lane
+        unsigned so[4];                                    // ... and the rows' element offsets in the sample
         CD_STAMP(0);
 #pragma unroll
         for (int st = 0; st < 9; ++st) {
+            if (SKIP && st == 8 && cc == NCH - 1) {
+                // voxels outside the volume (edge blocks) read a clamped address; their rows are never stored
+                int b, ox0, oy0, oz0;
+                decode(item, b, ox0, oy0, oz0);
+                // wave-uniform sample base + a 32-bit lane offset (a sample of xs is below 2^31 bytes: the entry's range check)
+                const float *xb = xs + (int64_t)b * X * Y * Z * CS;
+                const int ys = min(oy0 + (t & 7), Y - 1), zs = min(oz0 + (t >> 3), Z - 1);
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    const int xv = min(ox0 + 4 * wave + i, X - 1);
+                    so[i] = (unsigned)(((xv * Y + ys) * Z + zs) * CS + 4 * h);
+                    s0[i] = xb[so[i]];
+                }
+            }
             __builtin_amdgcn_sched_barrier(0);
             w1 = load_w(min(q0 + st + 1, n_items * 9 - 1));             // unconditional: a branch here costs the register renaming
             if (st + 1 < 9) load_a(st + 1, a1);
@@ -1153,6 +1227,43 @@ void conv3_split_kernel(const float *__restrict__ x, const unsigned *__restrict_
             w0 = w1;
         }
         CD_STAMP(1);
+        if (SKIP && cc == NCH - 1) {
+            float4 sv[2][4];                               // xs rows of this lane, [chunk][i]
+            {
+                // the rest of a voxel's 64 bytes: the cache line was requested a step ago
+                int b, ox0, oy0, oz0;
+                decode(item, b, ox0, oy0, oz0);
+                const float *xb = xs + (int64_t)b * X * Y * Z * CS;
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    const float *p = xb + so[i];
+                    sv[0][i] = make_float4(s0[i], p[1], p[2], p[3]);
+                    sv[1][i] = *reinterpret_cast<const float4 *>(p + 8);
+                }
+            }
+            // the weight records (L2 hits: 6 KB shared by every workgroup) arrive while the rows are split
+            CdRec ws[2];
+#pragma unroll
+            for (int c2 = 0; c2 < 2; ++c2) {
+                const unsigned *r = WS + (unsigned)(((c2 * 2 + h) * O + t) * 12);
+                ws[c2].hl = *reinterpret_cast<const u32x4 *>(r);
+                ws[c2].hh = *reinterpret_cast<const u32x4 *>(r + 4);
+                ws[c2].mm = *reinterpret_cast<const u32x4 *>(r + 8);
+            }
+#pragma unroll
+            for (int c2 = 0; c2 < 2; ++c2) {
+                __builtin_amdgcn_sched_barrier(0);         // one chunk's pieces at a time: both would not fit the registers
+                u32x4 lh[4], hm[4];
+#pragma unroll
+                for (int i = 0; i < 4; ++i) split3(sv[c2][i], lh[i], hm[i]);
+#pragma unroll
+                for (int i = 0; i < 4; ++i) acc[i] = mfma_bf16(lh[i], ws[c2].hl, acc[i]);
+#pragma unroll
+                for (int i = 0; i < 4; ++i) acc[i] = mfma_bf16(hm[i], ws[c2].hh, acc[i]);
+#pragma unroll
+                for (int i = 0; i < 4; ++i) acc[i] = mfma_bf16(hm[i], ws[c2].mm, acc[i]);
+            }
+        }
         if (cc == NCH - 1) {
             // D of the 32x32 MFMA: lane (col = t, h) holds rows m = 8 (v >> 2) + (v & 3) + 4 h, v = 0..15, of every accumulator;
             // row m of accumulator i is voxel (x = 4 wave + i, y = m & 7, z = m >> 3).  Each accumulator goes through the wave's
@@ -1173,7 +1284,7 @@ void conv3_split_kernel(const float *__restrict__ x, const unsigned *__restrict_
                         const int64_t idx = obase + (((int64_t)i * Y + (v & 3)) * Z + (v >> 2)) * O;
                         float val = acc[i][v] + sh;
                         if (MODE == 2) val += res[idx];
-                        if (MODE >= 1) val = fmaxf(val, 0.0f);
+                        if (MODE >= 1) val = SKIP ? relu_keep_nan(val) : fmaxf(val, 0.0f);
                         if (MODE == 3) val += res[idx];
 #if SP3D_W16_ABLATE & 16
                         if (val == 123.456f)
@@ -1201,7 +1312,8 @@ void conv3_split_kernel(const float *__restrict__ x, const unsigned *__restrict_
                         float4 rr = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
                         if (MODE >= 2) rr = *reinterpret_cast<const float4 *>(res + vox * O + 4 * g);
                         if (MODE == 2) { a.x += rr.x; a.y += rr.y; a.z += rr.z; a.w += rr.w; }
-                        if (MODE >= 1) { a.x = fmaxf(a.x, 0.0f); a.y = fmaxf(a.y, 0.0f); a.z = fmaxf(a.z, 0.0f); a.w = fmaxf(a.w, 0.0f); }
+                        if (MODE >= 1 && SKIP) { a.x = relu_keep_nan(a.x); a.y = relu_keep_nan(a.y); a.z = relu_keep_nan(a.z); a.w = relu_keep_nan(a.w); }
+                        if (MODE >= 1 && !SKIP) { a.x = fmaxf(a.x, 0.0f); a.y = fmaxf(a.y, 0.0f); a.z = fmaxf(a.z, 0.0f); a.w = fmaxf(a.w, 0.0f); }
                         if (MODE == 3) { a.x += rr.x; a.y += rr.y; a.z += rr.z; a.w += rr.w; }
 #if SP3D_W16_ABLATE & 16
                         if (a.x == 123.456f)
@@ -1294,7 +1406,7 @@ extern "C" int sp3d_wino_fused_split64(const float *x, const void *U3, float *y,
     hipStream_t s = (hipStream_t)stream;
     const unsigned *u3 = reinterpret_cast<const unsigned *>(U3);
     const dim3 grid((unsigned)blocks), block(64 * (4 / nbw) * ks);
-#define SP3D_WF(C_, M_) hipLaunchKernelGGL((wino_fused16_kernel<C_, M_, 2, 2>), grid, block, 0, s, x, u3, y, shift, residual, B, X, Y, Z, NBX, NBY, NBZ)
+#define SP3D_WF(C_, M_) hipLaunchKernelGGL((wino_fused16_kernel<C_, M_, 2, 2>), grid, block, 0, s, x, u3, y, shift, residual, B, X, Y, Z, NBX, NBY, NBZ, (const float *)nullptr, (const unsigned *)nullptr)
 #define SP3D_WFM(C_) switch (mode) { case 0: SP3D_WF(C_, 0); break; case 1: SP3D_WF(C_, 1); break; case 2: SP3D_WF(C_, 2); break; default: SP3D_WF(C_, 3); }
     if (C == 32) { SP3D_WFM(32) } else { SP3D_WFM(64) }
 #undef SP3D_WFM
@@ -1303,15 +1415,12 @@ extern "C" int sp3d_wino_fused_split64(const float *x, const void *U3, float *y,
     return e == hipSuccess ? SP3D_OK : (int)e;
 }
 
-extern "C" int sp3d_conv3_split(const float *x, const void *W3, float *y, const float *shift, const float *residual, int mode,
-                                int B, int X, int Y, int Z, int C, int O, void *stream)
+// launch of conv3_split_kernel behind sp3d_conv3_split (xs == nullptr) and sp3d_conv3_split_skip (C = 32, mode 1, the skip
+// term of xs / WS on the accumulators); the arguments are validated
+static int conv3_split_launch(const float *x, const void *W3, float *y, const float *shift, const float *residual, int mode,
+                              const float *xs, const void *WS, int B, int X, int Y, int Z, int C, void *stream)
 {
     using namespace sp3d;
-    if (B <= 0 || X <= 0 || Y <= 0 || Z <= 0 || mode < 0 || mode > 3) return SP3D_EINVAL;
-    if (!x || !W3 || !y || !shift || (mode >= 2 && !residual)) return SP3D_ENULL;
-    if (O != 32 || (C != 16 && C != 32) || (reinterpret_cast<uintptr_t>(W3) & 15)) return SP3D_EUNSUPPORTED;
-    if (reinterpret_cast<uintptr_t>(y) & 15) return SP3D_EUNSUPPORTED;
-    if ((int64_t)X * Y * Z * C * 2 > 0x7fffffff) return SP3D_ERANGE;
     const int NBX = (X + CD_BX - 1) / CD_BX, NBY = (Y + CD_BY - 1) / CD_BY, NBZ = (Z + CD_BZ - 1) / CD_BZ;
     const int64_t blocks = (int64_t)B * NBX * NBY * NBZ;
     if (blocks > 0x7fffffff) return SP3D_ERANGE;
@@ -1330,19 +1439,62 @@ extern "C" int sp3d_conv3_split(const float *x, const void *W3, float *y, const 
     const dim3 grid((unsigned)nwg), block(64 * (4 + CD_PROD));
     const size_t lds = (size_t)2 * CD_BUFS * sizeof(unsigned) + 4 * 1024 * sizeof(float);
     hipStream_t s = (hipStream_t)stream;
-    const unsigned *w3 = reinterpret_cast<const unsigned *>(W3);
+    const unsigned *w3 = reinterpret_cast<const unsigned *>(W3), *wsk = reinterpret_cast<const unsigned *>(WS);
     // the attribute is per device: remember it per device (a process that drives several GPUs launches on each)
     int cd_dev = 0;
     { const hipError_t ed = hipGetDevice(&cd_dev); if (ed != hipSuccess) return (int)ed; }
     if (cd_dev < 0 || cd_dev >= 64) cd_dev = 63;
-#define SP3D_CD(C_, M_) { static bool attr_dev[64] = {}; bool &attr = attr_dev[cd_dev]; if (!attr || cd_dev == 63) { hipError_t ea = hipFuncSetAttribute(reinterpret_cast<const void *>(conv3_split_kernel<C_, M_>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); if (ea != hipSuccess) return (int)ea; attr = true; } \
-    hipLaunchKernelGGL((conv3_split_kernel<C_, M_>), grid, block, lds, s, x, w3, y, shift, residual, B, X, Y, Z, NBX, NBY, NBZ, (int)blocks); }
-#define SP3D_CDI(C_) switch (mode) { case 0: SP3D_CD(C_, 0); break; case 1: SP3D_CD(C_, 1); break; case 2: SP3D_CD(C_, 2); break; default: SP3D_CD(C_, 3); }
-    if (C == 16) { SP3D_CDI(16) } else { SP3D_CDI(32) }
+#define SP3D_CD(C_, M_, S_) { static bool attr_dev[64] = {}; bool &attr = attr_dev[cd_dev]; if (!attr || cd_dev == 63) { hipError_t ea = hipFuncSetAttribute(reinterpret_cast<const void *>(conv3_split_kernel<C_, M_, S_>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); if (ea != hipSuccess) return (int)ea; attr = true; } \
+    hipLaunchKernelGGL((conv3_split_kernel<C_, M_, S_>), grid, block, lds, s, x, w3, y, shift, residual, B, X, Y, Z, NBX, NBY, NBZ, (int)blocks, xs, wsk); }
+#define SP3D_CDI(C_) switch (mode) { case 0: SP3D_CD(C_, 0, false); break; case 1: SP3D_CD(C_, 1, false); break; case 2: SP3D_CD(C_, 2, false); break; default: SP3D_CD(C_, 3, false); }
+    if (xs) { SP3D_CD(32, 1, true) } else if (C == 16) { SP3D_CDI(16) } else { SP3D_CDI(32) }
 #undef SP3D_CDI
 #undef SP3D_CD
     const hipError_t e = hipGetLastError();
     return e == hipSuccess ? SP3D_OK : (int)e;
+}
+
+extern "C" int sp3d_wino_fused_split64_skip(const float *x, const void *U3, float *y, const float *shift, const float *xs,
+                                            const void *WS, int B, int X, int Y, int Z, int C, int O, int CS, void *stream)
+{
+    using namespace sp3d;
+    if (B <= 0 || X <= 0 || Y <= 0 || Z <= 0) return SP3D_EINVAL;
+    if (!x || !U3 || !y || !shift || !xs || !WS) return SP3D_ENULL;
+    if (O != 64 || C != 64 || CS != 32 || (reinterpret_cast<uintptr_t>(U3) & 7)) return SP3D_EUNSUPPORTED;
+    if ((reinterpret_cast<uintptr_t>(WS) & 7) || (reinterpret_cast<uintptr_t>(xs) & 15)) return SP3D_EUNSUPPORTED;
+    if ((int64_t)X * Y * Z * CS > 0x7fffffff) return SP3D_ERANGE;          // the kernel's 32-bit offsets inside a sample of xs
+    const int NBX = (X + 7) / 8, NBY = (Y + 7) / 8, NBZ = (Z + 1) / 2;
+    const int64_t blocks = (int64_t)B * NBX * NBY * NBZ;
+    if (blocks > 0x7fffffff) return SP3D_ERANGE;
+    hipStream_t s = (hipStream_t)stream;
+    const dim3 grid((unsigned)blocks), block(64 * 2 * 2);                  // the configuration of sp3d_wino_fused_split64
+    hipLaunchKernelGGL((wino_fused16_kernel<64, 1, 2, 2, true>), grid, block, 0, s, x, reinterpret_cast<const unsigned *>(U3), y, shift,
+                       (const float *)nullptr, B, X, Y, Z, NBX, NBY, NBZ, xs, reinterpret_cast<const unsigned *>(WS));
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? SP3D_OK : (int)e;
+}
+
+extern "C" int sp3d_conv3_split(const float *x, const void *W3, float *y, const float *shift, const float *residual, int mode,
+                                int B, int X, int Y, int Z, int C, int O, void *stream)
+{
+    if (B <= 0 || X <= 0 || Y <= 0 || Z <= 0 || mode < 0 || mode > 3) return SP3D_EINVAL;
+    if (!x || !W3 || !y || !shift || (mode >= 2 && !residual)) return SP3D_ENULL;
+    if (O != 32 || (C != 16 && C != 32) || (reinterpret_cast<uintptr_t>(W3) & 15)) return SP3D_EUNSUPPORTED;
+    if (reinterpret_cast<uintptr_t>(y) & 15) return SP3D_EUNSUPPORTED;
+    if ((int64_t)X * Y * Z * C * 2 > 0x7fffffff) return SP3D_ERANGE;
+    return conv3_split_launch(x, W3, y, shift, residual, mode, nullptr, nullptr, B, X, Y, Z, C, stream);
+}
+
+extern "C" int sp3d_conv3_split_skip(const float *x, const void *W3, float *y, const float *shift, const float *xs,
+                                     const void *WS, int B, int X, int Y, int Z, int C, int O, int CS, void *stream)
+{
+    if (B <= 0 || X <= 0 || Y <= 0 || Z <= 0) return SP3D_EINVAL;
+    if (!x || !W3 || !y || !shift || !xs || !WS) return SP3D_ENULL;
+    if (O != 32 || C != 32 || CS != 16) return SP3D_EUNSUPPORTED;
+    if ((reinterpret_cast<uintptr_t>(W3) | reinterpret_cast<uintptr_t>(WS) | reinterpret_cast<uintptr_t>(xs) |
+         reinterpret_cast<uintptr_t>(y)) & 15) return SP3D_EUNSUPPORTED;
+    if ((int64_t)X * Y * Z * C * 2 > 0x7fffffff) return SP3D_ERANGE;
+    return conv3_split_launch(x, W3, y, shift, nullptr, 1, xs, WS, B, X, Y, Z, C, stream);
 }
 
 extern "C" int sp3d_debug_conv3_timeline(void *dev_buffer)

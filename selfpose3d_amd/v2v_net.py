@@ -277,6 +277,11 @@ class _Res(NamedTuple):
     c1: _Conv
     c2: _Conv
     skip: Optional[torch.Tensor]
+    # the projection in the record forms of the kernels that compute it on the second conv's accumulators (no GEMM, no
+    # projected tensor): 16 -> 32 for conv3_split_ (_lib.conv_weights_split), 32 -> 64 for wino_fused_conv3d_ with split
+    # weights (_lib.wino_weights_split, chunk 16)
+    skip_direct: Optional[torch.Tensor] = None
+    skip_split: Optional[torch.Tensor] = None
 
 
 class _Up(NamedTuple):
@@ -357,11 +362,16 @@ class _FoldedV2V:
             blk = n.front_layers[1] if name == "front_res" else getattr(ed, name)
             w1, s1 = self._fold(blk.res_branch[0], blk.res_branch[1])
             w2, s2 = self._fold(blk.res_branch[3], blk.res_branch[4])
-            ws = None
+            ws = sd = sp = None
             if len(blk.skip_con) > 0:              # the skip's shift rides on the second conv's epilogue
                 ws, ss = self._fold(blk.skip_con[0], blk.skip_con[1])
                 s2 = (s2 + ss).contiguous()
-            layers[name] = _Res(self._conv3_record(w1, s1), self._conv3_record(w2, s2), ws)
+                co, ci = int(ws.shape[0]), int(ws.shape[1])
+                if ws.is_cuda and (co, ci) == (32, 16):
+                    sd = _lib.conv_weights_split(ws)
+                if ws.is_cuda and (co, ci) == (64, 32):
+                    sp = _lib.wino_weights_split(ws.reshape(co, ci).t().reshape(1, ci, co).contiguous(), 16)
+            layers[name] = _Res(self._conv3_record(w1, s1), self._conv3_record(w2, s2), ws, sd, sp)
         for name in ("decoder_upsample2", "decoder_upsample1"):
             blk = getattr(ed, name).block
             wT, sT = self._fold(blk[0], blk[1], transposed=True)
@@ -373,26 +383,51 @@ class _FoldedV2V:
         # the spectra belong to the old weights; the padded buffers go with them, a caller's view of one is then copied
         self.layers, self.spectra, self.xpad = layers, {}, {}
 
-    def _conv3(self, x, c: "_Conv", mode, residual=None):
-        """3x3x3 conv + fused epilogue on the route conv3_route names (weights on the GPU and channels-last x)"""
+    def _route(self, x, c: "_Conv") -> str:
+        n = self.net
+        if c.u is None or not is_cl(x):
+            return "library"
+        return conv3_route(int(c.w.shape[1]), int(c.w.shape[0]), (x.shape[0],) + tuple(x.shape[2:]), n.winograd,
+                           getattr(n, "wino_split", True), getattr(n, "direct_conv", True))
+
+    def _conv3(self, x, c: "_Conv", mode, residual=None, xs=None, skip_w=None):
+        """3x3x3 conv + fused epilogue on the route conv3_route names (weights on the GPU and channels-last x); xs, skip_w:
+        the block input and its projection records for the two kernels that fold the skip (_folded_skip chose them)"""
         from . import _lib
-        n, route = self.net, "library"
-        split = getattr(n, "wino_split", True)
-        if c.u is not None and is_cl(x):
-            route = conv3_route(int(c.w.shape[1]), int(c.w.shape[0]), (x.shape[0],) + tuple(x.shape[2:]), n.winograd, split,
-                                getattr(n, "direct_conv", True))
+        route = self._route(x, c)
+        split = getattr(self.net, "wino_split", True)
         if route == "conv3_split_":
-            return _lib.conv3_split_(x, c.direct, c.shift, mode, residual)
+            return _lib.conv3_split_(x, c.direct, c.shift, mode, residual, xs=xs, skip_w=skip_w)
         if route == "wino_fused_conv3d_":
-            return _lib.wino_fused_conv3d_(x, c.u, c.shift, mode, residual, c.split if split else None)
+            return _lib.wino_fused_conv3d_(x, c.u, c.shift, mode, residual, c.split if split else None, xs=xs, skip_w=skip_w)
+        assert xs is None and skip_w is None, route
         if route == "wino_conv3d_":
             return _lib.wino_conv3d_(x, c.u, c.shift, mode, residual)
         return _lib.channel_shift_act_(F.conv3d(x, c.w, None, 1, 1), c.shift, mode, residual)
 
+    def _folded_skip(self, x, h, r: "_Res"):
+        """the projection records of block r for the kernel its second conv takes on h, or None: that kernel has no folded
+        form (other widths, the library, the three-launch Winograd, fp32 Winograd products), x is not a dense float32
+        channels-last tensor of the projection's input width, or SP3D_FOLD_SKIP=0"""
+        from . import _lib
+        if r.skip is None or not _lib.skip_fold_enabled() or not (is_cl(x) and x.is_cuda and x.dtype == torch.float32):
+            return None
+        route, widths = self._route(h, r.c2), (int(r.c2.w.shape[1]), int(r.c2.w.shape[0]), int(x.shape[1]))
+        if route == "conv3_split_" and widths == (32, 32, 16):
+            return r.skip_direct
+        if route == "wino_fused_conv3d_" and getattr(self.net, "wino_split", True) and widths == (64, 64, 32):
+            return r.skip_split
+        return None
+
     def _res(self, x, name):
         r = self.layers[name]
         h = self._conv3(x, r.c1, 1)
-        return self._conv3(h, r.c2, 2, x if r.skip is None else self._conv1(x, r.skip))
+        if r.skip is None:
+            return self._conv3(h, r.c2, 2, x)
+        rec = self._folded_skip(x, h, r)
+        if rec is not None:                         # relu(conv3(h) + W . x + shift): neither the GEMM nor its product exists
+            return self._conv3(h, r.c2, 1, xs=x, skip_w=rec)
+        return self._conv3(h, r.c2, 2, self._conv1(x, r.skip))
 
     # -- library GEMM selection (OPT-IN) ---------------------------------------------------------------------------
     # The plan's GEMMs (batched Winograd products, transposed-conv and 1x1x1 GEMMs) are plain library calls; which
