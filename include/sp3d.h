@@ -101,7 +101,7 @@ enum {
      * J = channels written: 1, or 4 (the value and three zero channels); with SP3D_OUT_CHANNELS_LAST J must be 4.
      * Same bits as the other forward kernels give for that channel.  SP3D_EUNSUPPORTED, before any launch, for any
      * other J, for either bf16 flag, for sp3d_unproject_fwd_train (its pass mask and a heat-map gradient of the one channel
-     * are sp3d_unproject_one_fwd_train / sp3d_unproject_one_bwd[_det], sp3d_one_train.h), for heat-maps narrower or lower
+     * are sp3d_unproject_one_fwd_train / sp3d_unproject_one_bwd[_det] below), for heat-maps narrower or lower
      * than 2 pixels or of more than 2^24 pixels, and for a sample of more than 2^31 bytes; SP3D_EINVAL for Jp < 1 and for a
      * layout byte that is neither SP3D_LAYOUT_PLANAR nor SP3D_LAYOUT_NHWC. */
     SP3D_HM_ONE_CHANNEL = 0x800
@@ -240,10 +240,58 @@ int sp3d_unproject_bwd_packed_det(const float *cam, const int32_t *sample_of, co
                                   int Z, const float *grid_size, int W_in, int H_in, int scatter, void *stream);
 int sp3d_fixed_to_float(const int64_t *acc, float *out, const float *scale, int64_t n, void *stream);
 
-/* The training pair of the one-channel unprojection (SP3D_HM_ONE_CHANNEL with a heat-map gradient): the forward that also
- * writes the pass mask, and a backward that scatters the one channel into dense (V,B,h,w) planes, fp32 or deterministic.
- * Declared and documented in sp3d_one_train.h. */
-#include "sp3d_one_train.h"
+/* The training pair of the one-channel unprojection (SP3D_HM_ONE_CHANNEL with a heat-map gradient) - the root-joint map of the
+ * ROOTNET_ROOTHM root nets: the forward that also writes the pass mask, and a backward that scatters the one channel into
+ * dense (V,B,h,w) planes, fp32 or deterministic. */
+
+/*
+ * sp3d_unproject_fwd_indexed with SP3D_HM_ONE_CHANNEL that also writes the pass mask.  The addressing is the one-channel
+ * forward's: hm_layout = SP3D_LAYOUT_PLANAR or SP3D_LAYOUT_NHWC, optionally | SP3D_OUT_CHANNELS_LAST; SP3D_HM_ONE_CHANNEL is
+ * accepted and implied; Jp as documented at SP3D_HM_ONE_CHANNEL.  The result forms are the same: J = 1 planar, J = 4 planar
+ * (channels 1-3 zero) or channels-last (P,X,Y,Z,4); same bits.
+ *   pass_mask  (P, X*Y*Z) uint16 in the format of sp3d_unproject_fwd_train at J = 1: bit 0 set where the pre-clamp value
+ *              lies in [0,1] and the voxel is not NaN-zeroed (a voxel no view sees has a pre-clamp value of 0: set); bits
+ *              1..15 zero; the words of a cube that `valid` skips are zero.  The words are those the packed training forward
+ *              writes for the contiguous channel, so either forward's mask serves either backward.
+ * SP3D_EUNSUPPORTED, before any launch, for J other than 1 or 4, a channels-last result with J = 1, either bf16 flag,
+ * heat-maps narrower or lower than 2 pixels or of more than 2^24 pixels, a sample of more than 2^31 bytes; SP3D_EINVAL for
+ * Jp < 1, V > SP3D_MAX_VIEWS, an unknown layout byte; SP3D_ENULL for a missing pointer (grids may be NULL).
+ * sp3d_unproject_fwd_train itself keeps refusing SP3D_HM_ONE_CHANNEL.
+ */
+int sp3d_unproject_one_fwd_train(const float *const *hm_views, int hm_layout, int Jp, const float *cam,
+                                 const int32_t *sample_of, const float *centers, const uint8_t *valid, float *cubes,
+                                 float *grids, uint16_t *pass_mask, int P, int V, int J, int h, int w, int X, int Y, int Z,
+                                 const float *grid_size, int W_in, int H_in, void *stream);
+
+/*
+ * Gradient of that forward w.r.t. the one heat-map channel; reads no heat-map.  One lane per voxel, one memory atomic per
+ * non-zero tap: no pad channels are scattered (sp3d_unproject_bwd_packed at Jp = 4 adds three zeros per value).
+ *   grad_cubes        channel 0 of cube p is X*Y*Z contiguous floats at grad_cubes + p * grad_cube_stride: the stride is
+ *                     X*Y*Z for a (P,1,X,Y,Z) gradient and 4*X*Y*Z for a planar (P,4,X,Y,Z) one (no slice copy);
+ *                     SP3D_EINVAL below X*Y*Z
+ *   pass_mask         (P, X*Y*Z) uint16, bit 0 read (sp3d_unproject_one_fwd_train's or sp3d_unproject_fwd_train's words)
+ *   grad_hm           (V,B,h,w) fp32, dense, ZERO-FILLED by the caller: plane (c, sample_of[p]) receives cube p's taps in
+ *                     view c (fp32 atomics: the summation order is the hardware's)
+ * The products added are (grad / den) * w, formed as sp3d_unproject_bwd_packed forms them.
+ * SP3D_EINVAL for a dimension <= 0 or V > SP3D_MAX_VIEWS, SP3D_ERANGE for sizes beyond 32-bit voxel indexing, SP3D_ENULL for
+ * a missing pointer (sample_of may be NULL), SP3D_EUNSUPPORTED for heat-maps narrower or lower than 2 pixels or of more than
+ * 2^24 pixels - all before any launch.
+ */
+int sp3d_unproject_one_bwd(const float *cam, const int32_t *sample_of, const float *centers, const uint8_t *valid,
+                           const float *grad_cubes, int64_t grad_cube_stride, const uint16_t *pass_mask, float *grad_hm,
+                           int B, int P, int V, int h, int w, int X, int Y, int Z, const float *grid_size, int W_in,
+                           int H_in, void *stream);
+
+/*
+ * DETERMINISTIC form: round(v * scale) is added to grad_fixed (V,B,h,w) int64 (zero-filled by the caller) with integer
+ * atomics, under the contract of sp3d_unproject_bwd_packed_det (`scale`: DEVICE float 2^k, |v * scale| < 2^50).  The integers
+ * are those sp3d_unproject_bwd_packed_det adds to channel 0 for the same gradient, mask and scale, whichever scatter it
+ * uses: the sums are equal bit for bit.  sp3d_fixed_to_float converts back.
+ */
+int sp3d_unproject_one_bwd_det(const float *cam, const int32_t *sample_of, const float *centers, const uint8_t *valid,
+                               const float *grad_cubes, int64_t grad_cube_stride, const uint16_t *pass_mask,
+                               int64_t *grad_fixed, const float *scale, int B, int P, int V, int h, int w, int X, int Y,
+                               int Z, const float *grid_size, int W_in, int H_in, void *stream);
 
 /*
  * core.proposal.nms + ProposalLayer.get_real_loc (lib/core/proposal.py:28-48,
@@ -443,9 +491,26 @@ int sp3d_wino_fused_split64(const float *x, const void *U3, float *y, const floa
 int sp3d_conv3_split(const float *x, const void *W3, float *y, const float *shift, const float *residual, int mode, int B,
                      int X, int Y, int Z, int C, int O, void *stream);
 
-/* These two convolutions with a residual block's 1x1x1 skip projection on their accumulators: sp3d_conv3_split_skip,
- * sp3d_wino_fused_split64_skip.  Declared and documented in sp3d_skip_fold.h. */
-#include "sp3d_skip_fold.h"
+/* These two convolutions as the second 3x3x3 convolution of a residual block that changes its channel count, with the
+ * block's 1x1x1 skip projection computed on the same accumulators. */
+
+/* y = relu(conv3(x) + WS . xs + shift): sp3d_conv3_split (its x, W3, y, shift and its refusals) with the projection of the
+ * block's input xs (B,X,Y,Z,CS) channels-last as more K of the same products - the projected tensor never exists.
+ * WS: the 48-byte records of sp3d_conv3_split for a one-tap (O,CS,1,1,1) weight, index (chunk*2 + half)*O + o, channel =
+ * 8*chunk + 4*half + q (_lib.conv_weights_split).  The projection's own shift is expected in `shift`.
+ * (C, O, CS) = (32, 32, 16), anything else SP3D_EUNSUPPORTED; xs and WS 16-byte aligned (SP3D_EUNSUPPORTED), non-NULL
+ * (SP3D_ENULL).  ReLU lets NaN through (torch.relu). */
+int sp3d_conv3_split_skip(const float *x, const void *W3, float *y, const float *shift, const float *xs, const void *WS,
+                          int B, int X, int Y, int Z, int C, int O, int CS, void *stream);
+
+/* The same for the half-resolution blocks: sp3d_wino_fused_split64 (its x, U3, y, shift and its refusals) with
+ * y = relu(conv3(x) + WS . xs + shift), xs (B,X,Y,Z,CS) channels-last.  WS: the 24-byte records [mid(4ch) hi(4ch) lo(4ch)] of
+ * sp3d_wino_fused_split64 for one point, index (chunk*4 + group)*O + o, channel = 16*chunk + 4*group + q
+ * (_lib.wino_weights_split of the (1, CS, O) weight, chunk 16).  (C, O, CS) = (64, 64, 32), anything else
+ * SP3D_EUNSUPPORTED; WS 8-byte and xs 16-byte aligned (SP3D_EUNSUPPORTED), non-NULL (SP3D_ENULL); a sample of xs has fewer
+ * than 2^31 elements (SP3D_ERANGE).  ReLU lets NaN through (torch.relu). */
+int sp3d_wino_fused_split64_skip(const float *x, const void *U3, float *y, const float *shift, const float *xs, const void *WS,
+                                 int B, int X, int Y, int Z, int C, int O, int CS, void *stream);
 
 /*
  * Scatter + epilogue of ConvTranspose3d(kernel 2, stride 2) -> BatchNorm -> ReLU (+ skip) (lib/models/v2v_net.py:57-69,
@@ -461,9 +526,17 @@ int sp3d_upsample2x_scatter(const float *G, float *out, const float *shift, cons
 int sp3d_upsample2x_scatter_head(const float *G, float *head, const float *shift, const float *skip, const float *wout,
                                  const float *bout, int64_t batch, int X, int Y, int Z, int O, int J, void *stream);
 
-/* The whole layer (product, scatter, epilogue, optional output conv) in one kernel: sp3d_upconv2x_fused.
- * Declared and documented in sp3d_upconv.h. */
-#include "sp3d_upconv.h"
+/* ConvTranspose3d(kernel 2, stride 2) -> BatchNorm -> ReLU (+ skip) (+ 1x1x1 output conv) in one kernel: the product G of
+ * sp3d_upsample2x_scatter[_head] on v_mfma_f32_32x32x16_bf16 with exact three-piece bf16 splits of both operands
+ * (fp32 accuracy, fp32 accumulation) and their epilogues on its accumulators - G never exists.
+ * x (batch,X,Y,Z,CIN) channels-last; w_split: 48-byte records of bf16 = the three B operands {hi,lo} {hi,hi} {mid,mid}
+ * (4 input channels each) at index ((((tap*(O/32) + o/32)*(CIN/8) + chunk)*2 + half)*32 + o%32, tap = 4i + 2j + k, channel =
+ * 8*chunk + 4*half + q (_lib.upconv_weights_split), 16-byte aligned.
+ * w_out == NULL: out (batch,2X,2Y,2Z,O) = relu(x.W + shift[o]) + skip, (CIN,O) = (128,64); J is ignored.
+ * w_out (J,32):  out (batch,2X,2Y,2Z,J) = b_out[j] + sum_o w_out[j][o] * (that), (CIN,O) = (64,32), 1 <= J <= 32, b_out NULL = 0.
+ * ReLU lets NaN through (torch.relu).  skip and out must have fewer than 2^31 elements (SP3D_ERANGE). */
+int sp3d_upconv2x_fused(const float *x, const void *w_split, const float *shift, const float *skip, const float *w_out,
+                        const float *b_out, float *out, int64_t batch, int X, int Y, int Z, int CIN, int O, int J, void *stream);
 
 /*
  * GROUPED training-mode batch normalisation on channels-last tensors (round 5): what lets the training pose net run all

@@ -50,6 +50,9 @@ SIGNATURES = {                                  # include/sp3d.h, in the header'
     "sp3d_unproject_bwd_packed": "i: ppppppp iiiiiiiiii p iii p",
     "sp3d_unproject_bwd_packed_det": "i: pppppppp iiiiiiiiii p iii p",
     "sp3d_fixed_to_float": "i: ppp l p",
+    "sp3d_unproject_one_fwd_train": "i: p ii ppppppp iiiiiiii p ii p",
+    "sp3d_unproject_one_bwd": "i: ppppp l pp iiiiiiii p ii p",
+    "sp3d_unproject_one_bwd_det": "i: ppppp l ppp iiiiiiii p ii p",
     "sp3d_nms_topk_workspace_bytes": "l: iiiii",
     "sp3d_nms_topk": "i: p iiiii ppppppp",
     "sp3d_nms_proposals": "i: p iiiii pp f pppppp",
@@ -82,8 +85,11 @@ SIGNATURES = {                                  # include/sp3d.h, in the header'
     "sp3d_wino_fused_split": "i: ppppp iiiiiii p",
     "sp3d_wino_fused_split64": "i: ppppp iiiiiii p",
     "sp3d_conv3_split": "i: ppppp iiiiiii p",
+    "sp3d_conv3_split_skip": "i: pppppp iiiiiii p",
+    "sp3d_wino_fused_split64_skip": "i: pppppp iiiiiii p",
     "sp3d_upsample2x_scatter": "i: pppp l iiii p",
     "sp3d_upsample2x_scatter_head": "i: pppppp l iiiii p",
+    "sp3d_upconv2x_fused": "i: ppppppp l iiiiii p",
     "sp3d_gbn_workspace_bytes": "l: ii",
     "sp3d_gbn_forward": "i: pp i pp i l iii pppp dd i ppppppp",
     "sp3d_gbn_backward": "i: ppp i pp i l ii ppppp i ppppppp",
@@ -93,18 +99,6 @@ TUNING_SIGNATURES = {                           # selfpose3d_amd/csrc/sp3d_tunin
     "sp3d_unproject_fwd_plan": "i: iii p iiiiiiiii pppp",
     "sp3d_debug_set_timeline": "i: p",
     "sp3d_debug_stamp": "i: pp",
-}
-ONE_TRAIN_SIGNATURES = {                        # include/sp3d_one_train.h (included by sp3d.h): required like SIGNATURES
-    "sp3d_unproject_one_fwd_train": "i: p ii ppppppp iiiiiiii p ii p",
-    "sp3d_unproject_one_bwd": "i: ppppp l pp iiiiiiii p ii p",
-    "sp3d_unproject_one_bwd_det": "i: ppppp l ppp iiiiiiii p ii p",
-}
-UPCONV_SIGNATURES = {                           # include/sp3d_upconv.h (included by sp3d.h): required like SIGNATURES
-    "sp3d_upconv2x_fused": "i: ppppppp l iiiiii p",
-}
-SKIP_FOLD_SIGNATURES = {                        # include/sp3d_skip_fold.h (included by sp3d.h): required like SIGNATURES
-    "sp3d_conv3_split_skip": "i: pppppp iiiiiii p",
-    "sp3d_wino_fused_split64_skip": "i: pppppp iiiiiii p",
 }
 EXPORTS = list(SIGNATURES)
 
@@ -155,8 +149,7 @@ def load():
             f"{LIB_PATH} not found - the HIP extension is not built. Run `python -m selfpose3d_amd.build` "
             "(hipcc, gfx950). There is no CPU fallback for the unprojection path.")
     lib = C.CDLL(LIB_PATH)
-    for table, required in ((SIGNATURES, True), (ONE_TRAIN_SIGNATURES, True), (UPCONV_SIGNATURES, True), (SKIP_FOLD_SIGNATURES, True),
-                            (TUNING_SIGNATURES, False)):
+    for table, required in ((SIGNATURES, True), (TUNING_SIGNATURES, False)):
         for name, sig in table.items():
             if required or hasattr(lib, name):
                 ret, args = sig.split(":")

@@ -1,6 +1,6 @@
 // sp3d_split.h - the exact three-piece bf16 split of fp32 operands and the bf16 matrix instruction the split kernels run on
-// (sp3d_winograd.hip: wino_fused3_kernel, wino_fused3_64_kernel, conv3_split_kernel; sp3d_upconv.hip:
-// upconv2x_fused_kernel).  a = hi + mid + lo, each a bf16 (8+8+8 mantissa bits: exact); the six products whose weight is
+// (sp3d_wino_fused.hip: wino_fused3_kernel, wino_fused16_kernel; sp3d_conv3_direct.hip: conv3_split_kernel;
+// sp3d_upconv.hip: upconv2x_fused_kernel).  a = hi + mid + lo, each a bf16 (8+8+8 mantissa bits: exact); the six products whose weight is
 // >= 2^-16 relative - hh, hm, mh, hl, lh, mm - are formed exactly by v_mfma_f32_32x32x16_bf16 and accumulated in fp32.
 #ifndef SP3D_SPLIT_H
 #define SP3D_SPLIT_H

@@ -1,185 +1,17 @@
-// sp3d_winograd.hip - input / output transforms of Winograd F(2x2x2, 3x3x3) for the low-resolution 3x3x3 convolutions
-// of the V2V nets in inference (reference: the `Res3DBlock`s of lib/models/v2v_net.py:23-45 at 1/4 resolution).
-//
-// At 1/4 resolution (20x20x5 voxels, 128 channels, batch 4) a 3x3x3 convolution is a GEMM with only 8 000 rows;
-// MIOpen's implicit-GEMM kernels reach 60 TFLOP/s there (112 us per layer).  Winograd needs 64 multiplies per 8 outputs
-// instead of 216, as 64 independent (tiles x C) x (C x O) products - one batched fp32 GEMM (rocBLAS through torch.bmm,
-// 36 us) - between two memory-bound transforms, which are these kernels:
-//   wino_input : channels-last activations (B,X,Y,Z,C) -> V[64][tiles][C],  V = B^T d B  along each axis
-//   wino_output: M[64][tiles][O] -> channels-last (B,X,Y,Z,O), y = A^T m A, fused with the layer's epilogue
-//                (shift [+ residual] [+ ReLU], the modes of sp3d_channel_shift_act)
-// lane = channel (coalesced 4-byte accesses across the channel-contiguous layouts), one thread = one (tile, channel).
-// The weight transform U = G g G^T is done once per plan on the host side of the binding (torch).
+// sp3d_wino_fused.hip - Winograd F(2x2x2, 3x3x3) as ONE kernel per layer for the full- and half-resolution 3x3x3
+// convolutions of the V2V nets in inference: wino_fused_kernel (fp32 matrix pipe), wino_fused3_kernel (the same on the
+// bf16 pipe with exact three-piece splits) at full resolution, wino_fused16_kernel at half resolution, and their C
+// entries.  The three-launch form of the quarter resolution is sp3d_wino.hip, the direct convolution sp3d_conv3_direct.hip.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "../../include/sp3d.h"
+#include "sp3d_conv3_host.h"
 #include "sp3d_split.h"
-
-namespace sp3d {
-
-__device__ __forceinline__ void bt4(float &d0, float &d1, float &d2, float &d3)
-{
-    const float t0 = d0 - d2, t1 = d1 + d2, t2 = d2 - d1, t3 = d1 - d3;
-    d0 = t0; d1 = t1; d2 = t2; d3 = t3;
-}
-
-__global__ __launch_bounds__(256) void wino_input_kernel(const float *__restrict__ x, float *__restrict__ V, int B, int X,
-                                                        int Y, int Z, int C, int TX, int TY, int TZ)
-{
-    const int64_t T = (int64_t)B * TX * TY * TZ;
-    const int64_t gid = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (gid >= T * C) return;
-    const int c = (int)(gid % C);
-    int64_t t = gid / C;
-    const int tz = (int)(t % TZ); int64_t r = t / TZ;
-    const int ty = (int)(r % TY); r /= TY;
-    const int tx = (int)(r % TX);
-    const int b = (int)(r / TX);
-    float d[4][4][4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int xi = 2 * tx - 1 + i;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int yj = 2 * ty - 1 + j;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const int zk = 2 * tz - 1 + k;
-                const bool in = xi >= 0 && xi < X && yj >= 0 && yj < Y && zk >= 0 && zk < Z;
-                d[i][j][k] = in ? x[((((int64_t)b * X + xi) * Y + yj) * Z + zk) * C + c] : 0.0f;
-            }
-        }
-    }
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) bt4(d[i][j][0], d[i][j][1], d[i][j][2], d[i][j][3]);
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int k = 0; k < 4; ++k) bt4(d[i][0][k], d[i][1][k], d[i][2][k], d[i][3][k]);
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-#pragma unroll
-        for (int k = 0; k < 4; ++k) bt4(d[0][j][k], d[1][j][k], d[2][j][k], d[3][j][k]);
-    const int64_t plane = T * C;
-    float *v = V + t * C + c;
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-#pragma unroll
-            for (int k = 0; k < 4; ++k) v[(int64_t)((i * 4 + j) * 4 + k) * plane] = d[i][j][k];
-}
-
-template <int MODE>
-__global__ __launch_bounds__(256) void wino_output_kernel(const float *__restrict__ M, float *__restrict__ y,
-                                                         const float *__restrict__ shift, const float *__restrict__ res,
-                                                         int B, int X, int Y, int Z, int O, int TX, int TY, int TZ)
-{
-    const int64_t T = (int64_t)B * TX * TY * TZ;
-    const int64_t gid = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (gid >= T * O) return;
-    const int o = (int)(gid % O);
-    int64_t t = gid / O;
-    const int tz = (int)(t % TZ); int64_t r = t / TZ;
-    const int ty = (int)(r % TY); r /= TY;
-    const int tx = (int)(r % TX);
-    const int b = (int)(r / TX);
-    const int64_t plane = T * O;
-    const float *m = M + t * O + o;
-    // A^T along x while loading: two rows of (4 x 4)
-    float a[2][4][4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const float m0 = m[(int64_t)((0 * 4 + j) * 4 + k) * plane], m1 = m[(int64_t)((1 * 4 + j) * 4 + k) * plane];
-            const float m2 = m[(int64_t)((2 * 4 + j) * 4 + k) * plane], m3 = m[(int64_t)((3 * 4 + j) * 4 + k) * plane];
-            a[0][j][k] = (m0 + m1) + m2;
-            a[1][j][k] = (m1 - m2) - m3;
-        }
-    const float sh = shift[o];
-    // residual values first (clamped addresses, no predicate): inside the bounds branches below each was a load -> wait ->
-    // store round trip of its own
-    float rv[2][2][2];
-    if (MODE >= 2) {
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int j = 0; j < 2; ++j)
-#pragma unroll
-                for (int k = 0; k < 2; ++k) {
-                    const int xo = min(2 * tx + i, X - 1), yo = min(2 * ty + j, Y - 1), zo = min(2 * tz + k, Z - 1);
-                    rv[i][j][k] = res[((((int64_t)b * X + xo) * Y + yo) * Z + zo) * O + o];
-                }
-    }
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-        float bq[2][4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            bq[0][k] = (a[i][0][k] + a[i][1][k]) + a[i][2][k];
-            bq[1][k] = (a[i][1][k] - a[i][2][k]) - a[i][3][k];
-        }
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const float c0 = (bq[j][0] + bq[j][1]) + bq[j][2], c1 = (bq[j][1] - bq[j][2]) - bq[j][3];
-            const int xo = 2 * tx + i, yo = 2 * ty + j;
-            if (xo >= X || yo >= Y) continue;
-#pragma unroll
-            for (int k = 0; k < 2; ++k) {
-                const int zo = 2 * tz + k;
-                if (zo >= Z) continue;
-                const int64_t idx = ((((int64_t)b * X + xo) * Y + yo) * Z + zo) * O + o;
-                float v = (k == 0 ? c0 : c1) + sh;
-                if (MODE == 2) v += rv[i][j][k];
-                if (MODE >= 1) v = fmaxf(v, 0.0f);
-                if (MODE == 3) v += rv[i][j][k];
-                y[idx] = v;
-            }
-        }
-    }
-}
-
-} // namespace sp3d
-
-using namespace sp3d;
-
-extern "C" int sp3d_wino_input(const float *x, float *V, int B, int X, int Y, int Z, int C, void *stream)
-{
-    if (B <= 0 || X <= 0 || Y <= 0 || Z <= 0 || C <= 0) return SP3D_EINVAL;
-    if (!x || !V) return SP3D_ENULL;
-    const int TX = (X + 1) / 2, TY = (Y + 1) / 2, TZ = (Z + 1) / 2;
-    const int64_t n = (int64_t)B * TX * TY * TZ * C;
-    if ((n + 255) / 256 > 0x7fffffff) return SP3D_ERANGE;
-    hipLaunchKernelGGL(wino_input_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x, V, B, X, Y, Z,
-                       C, TX, TY, TZ);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? SP3D_OK : (int)e;
-}
-
-extern "C" int sp3d_wino_output(const float *M, float *y, const float *shift, const float *residual, int mode, int B, int X,
-                                int Y, int Z, int O, void *stream)
-{
-    if (B <= 0 || X <= 0 || Y <= 0 || Z <= 0 || O <= 0 || mode < 0 || mode > 3) return SP3D_EINVAL;
-    if (!M || !y || !shift || (mode >= 2 && !residual)) return SP3D_ENULL;
-    const int TX = (X + 1) / 2, TY = (Y + 1) / 2, TZ = (Z + 1) / 2;
-    const int64_t n = (int64_t)B * TX * TY * TZ * O;
-    if ((n + 255) / 256 > 0x7fffffff) return SP3D_ERANGE;
-    const dim3 grid((unsigned)((n + 255) / 256)), block(256);
-    hipStream_t s = (hipStream_t)stream;
-#define SP3D_WO(MODE_) hipLaunchKernelGGL((wino_output_kernel<MODE_>), grid, block, 0, s, M, y, shift, residual, B, X, Y, Z, O, TX, TY, TZ)
-    switch (mode) { case 0: SP3D_WO(0); break; case 1: SP3D_WO(1); break; case 2: SP3D_WO(2); break; default: SP3D_WO(3); }
-#undef SP3D_WO
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? SP3D_OK : (int)e;
-}
 
 // ------------------------------------------------------------------------------------------
 // Fused Winograd F(2x2x2, 3x3x3) for the FULL-resolution 3x3x3 layers (C = 16 or 32 -> O = 32), where the
-// transformed tensor of the three-launch form above would be 524 MB.  One wave = a block of 4x4x2 tiles (8x8x4
+// transformed tensor of the three-launch form (sp3d_wino.hip) would be 524 MB.  One wave = a block of 4x4x2 tiles (8x8x4
 // outputs x 32 channels); nothing but x, U and y touches memory:
 //   per chunk of 8 input channels: stage the 10x10x6 input region in LDS (20.2 KB, 16-byte aligned rows);
 //   per transform point: each lane builds its A operand on the fly - V[p][tile][c] is a signed sum of 8 region
@@ -188,9 +20,6 @@ extern "C" int sp3d_wino_output(const float *M, float *y, const float *shift, co
 //   the inverse transform is linear: along x it is folded into the MFMA accumulation, along y,z it is applied to
 //     the accumulators on the VALU; nothing transformed is ever stored.
 // ------------------------------------------------------------------------------------------
-#ifndef SP3D_W16_ABLATE
-#define SP3D_W16_ABLATE 0      // measurement builds only (tools/diag_w16.py): 1 no MFMA, 2 no weight loads, 4 no split, 8 no LDS reads
-#endif
 
 namespace sp3d {
 
@@ -640,10 +469,6 @@ constexpr int W16_RX = 10, W16_RY = 10, W16_RZ = 4, W16_VS = 16;
 constexpr int W16_ROW = W16_RX * W16_VS + 4;
 constexpr int W16_LDS = W16_RY * W16_RZ * W16_ROW;               // 6 560 floats = 26 240 B
 
-// ReLU of the kernels that fold a skip projection: a NaN of the projection's input stays a NaN (torch.relu); fmaxf, which
-// the other instantiations keep, returns 0 for it
-__device__ __forceinline__ float relu_keep_nan(float v) { return v < 0.0f ? 0.0f : v; }
-
 __device__ __forceinline__ f32x4 mfma16_bf16(u32x4 a, u32x4 b, f32x4 c)
 {
     return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
@@ -981,379 +806,28 @@ __global__ __launch_bounds__(64 * (4 / NBW) * KS) __attribute__((amdgpu_waves_pe
     }
 }
 
-
-// ------------------------------------------------------------------------------------------
-// Direct 3x3x3 convolution on the bf16 matrix pipe at fp32 accuracy (implicit GEMM, no Winograd).
-// With exact three-piece splits a multiply costs 3 bf16 MFMA slots, and the bf16 pipe is 16x the fp32 one: the 2.25x
-// multiplication saving of (x-folded) Winograd no longer pays for its operand transforms - the fused Winograd kernels
-// above are VALU-bound (183 VALU instructions per 18 MFMAs, every step re-transforms and re-splits its operands).  Here
-// an input value is split ONCE when its region is staged (pieces stored in LDS: 24 B per voxel and 4-channel group,
-// [lo hi mid]), the A operand of tap (dx,dy,dz) is the staged record of the shifted voxel - read with a compile-time LDS
-// offset, no VALU at all - and the accumulators ARE the outputs.  Per (tap, 32-voxel block): 3 LDS reads + 3 MFMAs
-//     {lo,hi} x {bh,bl}  +  {hi,mid} x {bh,bh}  +  {hi,mid} x {bm,bm}      (A quads are consecutive registers)
-// Block = 8x8x2 outputs (4 MFMA row blocks) x NB*32 output channels per wave, 8-channel chunks, region 10x10x4 voxels
-// = 19.2 KB of LDS.  Weights: per (tap, chunk, lane half, output) one 24-byte record [mid hi lo] (conv_weights_split).
-// ------------------------------------------------------------------------------------------
-// Workgroup = 4 consumer waves + 4 producer waves (one of each per SIMD), persistent over output blocks of 16x8x4 voxels.
-//   consumers (wave = z layer, 4 row blocks of 16x2 voxels x 32 outputs): per tap 8 ds_read_b128 + 3 global_load_dwordx4
-//     + 12 matrix instructions, nothing else; operands one tap ahead, weights three taps ahead (across chunk boundaries);
-//   producers: fetch the 18x10x6 region of the NEXT (block, 8-channel chunk) item, split it, write it to the other LDS
-//     buffer.  They are separate waves because vmcnt is in-order: a consumer that had the region loads of the next chunk
-//     in flight waited for them at its next weight wait (58 us of 207), and between workgroups nobody covered the first
-//     chunk's latency.  One barrier per item.
-// LDS per buffer: one plane per 4-channel group (lane half); a voxel is the two A operands ready to use, 8 dwords
-// [lo hi | hi mid]; rows of 18 voxels (144 dwords), z planes of 10 rows + 4 dwords: with lane = (y = t & 7, z = t >> 3) the
-// 16 lanes of a ds_read_b128 group sit on 16 distinct 4-bank slots (searched over row / plane pitches).
-// A consumer wave owns 4 consecutive x of the block and ALL its (y,z): the operand of region voxel x' serves the taps
-// dx = x' - x of every x it owns, so a (dy,dz) step reads 6 operands for 36 matrix instructions instead of 12 - the LDS
-// (85 of its 128 B/clk with one operand read per tap and row block) was what the matrix pipe and the loader waves waited on.
-constexpr int CD_BX = 16, CD_BY = 8, CD_BZ = 4;
-constexpr int CD_RX = CD_BX + 2, CD_RY = CD_BY + 2, CD_RZ = CD_BZ + 2, CD_VOX = 8, CD_ROW = CD_RX * CD_VOX, CD_ZP = CD_RY * CD_ROW + 4;
-constexpr int CD_PLANE = CD_RZ * CD_ZP;                                // 8 664 dwords
-constexpr int CD_BUF = 2 * CD_PLANE;                                   // 17 328 dwords = 69 312 B per buffer
-constexpr int CD_NV4 = CD_RX * CD_RY * CD_RZ * 2;                      // float4 per item: 2 160
-constexpr int CD_PROD = 4;                                             // producer waves: one per SIMD
-constexpr int CD_PER = (CD_NV4 + 64 * CD_PROD - 1) / (64 * CD_PROD);   // 9 float4 per producer lane
-// buffer stride in dwords (17 408 = 69 632 B: the LDS layout the bank-conflict search was done for; CD_BUF rounded up to 68 x 256)
-constexpr int CD_BUFS = ((CD_BUF / 4 + 63) / 64) * 256;
-#ifndef SP3D_WG_ABLATE
-#define SP3D_WG_ABLATE 0
-#endif
-struct CdRec { u32x4 hl, hh, mm; };                                    // weight record: B operands {bh,bl} {bh,bh} {bm,bm}
-
-
-#ifdef SP3D_CD_TIMELINE
-__device__ unsigned long long *g_cd_tl = nullptr;      // [wave 6][item 64][4] s_memtime stamps of workgroup 0
-#define CD_STAMP(slot) do { __builtin_amdgcn_sched_barrier(0); if (g_cd_tl && blockIdx.x == 0 && lane == 0 && item < 64) { g_cd_tl[(wave * 64 + item) * 4 + (slot)] = __builtin_readcyclecounter(); \
-    /* the constant 100 MHz counter next to the first and the latest stamp of wave 0: cycles per microsecond = the clock the kernel ran at */ \
-    if (wave == 0 && (slot) == 0 && item == 0) { g_cd_tl[(7 * 64 + 62) * 4 + 0] = wall_clock64(); g_cd_tl[(7 * 64 + 62) * 4 + 1] = __builtin_readcyclecounter(); } \
-    if (wave == 0 && (slot) == 3) { g_cd_tl[(7 * 64 + 63) * 4 + 0] = wall_clock64(); g_cd_tl[(7 * 64 + 63) * 4 + 1] = __builtin_readcyclecounter(); } } __builtin_amdgcn_sched_barrier(0); } while (0)
-#else
-#define CD_STAMP(slot) do { (void)item; } while (0)
-#endif
-
-// SKIP: the 1x1x1 projection of a residual block's input on the same accumulators, y = epilogue(conv3(x) + WS . xs + shift):
-// xs (B,X,Y,Z,16) channels-last, WS = CdRec records of one tap [chunk 2][half 2][output 32].  Consumer waves only: lane
-// (t, h) is A row = voxel (4 wave + i, t & 7, t >> 3), channels 8 chunk + 4 h .. + 3 - one float4 per (i, chunk), split
-// and multiplied (24 matrix instructions) between the last step of the block's last chunk and the epilogue: once per block a
-// workgroup walks.  A voxel of xs is 64 bytes, one cache line for both chunks and both lane halves: the last (dy,dz) step
-// requests the first value of each row (4 registers - all eight rows held over that step spill: 256 + 72 B of scratch), the
-// rest are cache hits after the step.
-template <int C, int MODE, bool SKIP = false>
-__global__ __launch_bounds__(64 * (4 + CD_PROD)) __attribute__((amdgpu_waves_per_eu(2, 2)))
-void conv3_split_kernel(const float *__restrict__ x, const unsigned *__restrict__ W3, float *__restrict__ y,
-                        const float *__restrict__ shift, const float *__restrict__ res, int B, int X, int Y, int Z, int NBX,
-                        int NBY, int NBZ, int nblocks, const float *__restrict__ xs = nullptr,
-                        const unsigned *__restrict__ WS = nullptr)
-{
-    constexpr int O = 32, NCH = C / 8, CS = 16;
-    // operand roles: a split result wants (voxel, 4 consecutive channels) per lane = weights as the A operand (rows), an
-    // fp32-only result wants (channel, 16 voxels) per lane = full 128-byte rows per store instruction (the transposed form's
-    // 32-byte pieces cost 8-10 k cycles per block against 3-6 k)
-    extern __shared__ __attribute__((aligned(16))) unsigned cd_lds[];      // 2 x CD_BUFS dwords + 4 x 1024 floats of scratch
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, t = lane & 31, h = lane >> 5;
-    const int my_blocks = ((int)blockIdx.x < nblocks) ? (nblocks - 1 - (int)blockIdx.x) / (int)gridDim.x + 1 : 0;
-    const int n_items = my_blocks * NCH;
-    auto decode = [&](int item, int &b, int &ox0, int &oy0, int &oz0) {
-        int bid = (int)blockIdx.x + (item / NCH) * (int)gridDim.x;
-        const int bz = bid % NBZ; bid /= NBZ;
-        const int by = bid % NBY; bid /= NBY;
-        const int bx = bid % NBX;
-        b = bid / NBX;
-        ox0 = bx * CD_BX; oy0 = by * CD_BY; oz0 = bz * CD_BZ;
-    };
-
-    if (wave >= 4) {
-        // ---------------- producers: item k -> buffer k & 1 ----------------
-        const int pt = tid - 256;                                          // 0 .. 64*CD_PROD-1
-        // fp32 input.  VALU issue on a SIMD goes to the older wave first: without priority the (younger) producers got the
-        // slots the consumer's matrix stream left over - 28 cycles per instruction, 14 k cycles per item against the
-        // consumers' 12 k
-        __builtin_amdgcn_s_setprio(2);
-        // the producers get one issue slot per consumer matrix instruction (324 per item): everything that does not depend
-        // on the item is computed once - LDS offset, offset inside the sample, region coordinates
-        float4 d[CD_PER];
-        int lo_[CD_PER], rel[CD_PER], vxyz[CD_PER];
-#pragma unroll
-        for (int u = 0; u < CD_PER; ++u) {
-            const int idx = pt + 64 * CD_PROD * u;
-            const int v = idx >> 1, half = idx & 1;
-            const int vx = v % CD_RX, vy = (v / CD_RX) % CD_RY, vz = v / (CD_RX * CD_RY);
-            lo_[u] = idx < CD_NV4 ? half * CD_PLANE + vz * CD_ZP + vy * CD_ROW + vx * CD_VOX : -1;
-            rel[u] = ((vx * Y + vy) * Z + vz) * C + half * 4;
-            vxyz[u] = idx < CD_NV4 ? (vx | (vy << 8) | (vz << 16)) : 0x00ffffff;      // 255: never in range
-        }
-        auto issue = [&](int k) {                                          // loads of item k: in flight until iteration k
-            int b, ox0, oy0, oz0;
-            decode(k, b, ox0, oy0, oz0);
-            // element offset of region voxel (0,0,0), chunk k % NCH; may be negative at the volume border (never read there)
-            const int64_t vox0 = (((int64_t)b * X + (ox0 - 1)) * Y + (oy0 - 1)) * Z + (oz0 - 1);
-            const float *xb = x + vox0 * C + (k % NCH) * 8;
-            // voxel (vx,vy,vz) is inside the volume iff vx in [xlo, xhi) ...: wave-uniform bounds
-            const int xlo = 1 - ox0, xhi = X + 1 - ox0, ylo = 1 - oy0, yhi = Y + 1 - oy0, zlo = 1 - oz0, zhi = Z + 1 - oz0;
-#pragma unroll
-            for (int u = 0; u < CD_PER; ++u) {
-                const int vx = vxyz[u] & 255, vy = (vxyz[u] >> 8) & 255, vz = vxyz[u] >> 16;
-                const bool in = vx >= xlo && vx < xhi && vy >= ylo && vy < yhi && vz >= zlo && vz < zhi;
-                d[u] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-                if (in) d[u] = *reinterpret_cast<const float4 *>(xb + rel[u]);
-            }
-        };
-        if (n_items > 0) issue(0);
-        for (int k = 0; k <= n_items; ++k) {
-            if (k < n_items) {
-                { const int item = k; CD_STAMP(0); }
-                unsigned *buf = cd_lds + (k & 1) * CD_BUFS;
-#ifdef SP3D_CD_TIMELINE
-                __builtin_amdgcn_s_waitcnt(0);            // vmcnt(0) lgkmcnt(0): separates the load wait from the split
-                { const int item = k; CD_STAMP(3); }      // (slot 3 is overwritten after the barrier for consumers only)
-#endif
-#pragma unroll
-                for (int u = 0; u < CD_PER; ++u) {
-                    u32x4 q0, q1;
-                    split3(d[u], q0, q1);
-                    if (lo_[u] >= 0) {
-                        unsigned *p = buf + lo_[u];
-                        *reinterpret_cast<u32x4 *>(p) = q0;
-                        *reinterpret_cast<u32x4 *>(p + 4) = q1;
-                    }
-                }
-                { const int item = k; CD_STAMP(1); }
-                if (k + 1 < n_items) issue(k + 1);                         // one item ahead: its latency hides behind the barrier
-            }
-            if (k < n_items) { const int item = k; CD_STAMP(2); }
-            __syncthreads();
-        }
-        return;
-    }
-
-    // ---------------- consumers: item k - 1 from buffer (k - 1) & 1 ----------------
-    // lane (t, h): output voxels (x = 4 wave + i, y = t & 7, z = t >> 3), i = 0..3 (one accumulator each); operand j = 0..5
-    // of step (dy,dz) is region voxel (4 wave + j, y + dy, z + dz), channel group h
-    const int a_off = h * CD_PLANE + (t >> 3) * CD_ZP + (t & 7) * CD_ROW + 4 * wave * CD_VOX;
-    // weight record of (tap, chunk, lane half h, output t): 12 dwords
-    const unsigned *wl = W3 + ((int64_t)h * O + t) * 12;
-    struct W3Rec { CdRec d[3]; };                      // the three dx taps of one (dy,dz) step
-    auto load_w = [&](int q) {                         // q = flattened (item, step) index; weights depend on (chunk, step)
-        const int cc = (q / 9) % NCH, st = q % 9;
-        const unsigned *r = wl + ((int64_t)(3 * st) * NCH + cc) * 2 * O * 12;
-        W3Rec w;
-#pragma unroll
-        for (int dx = 0; dx < 3; ++dx) {
-#if SP3D_W16_ABLATE & 2
-            // measurement build: no weight loads (what would LDS-broadcast weights be worth at most?)
-            (void)r; w.d[dx].hl = u32x4{0x3f803f80u + (unsigned)q, 0x3f803f80u, 0x3f803f80u + (unsigned)dx, 0x3f803f80u};
-            w.d[dx].hh = w.d[dx].hl ^ 0x00010001u; w.d[dx].mm = w.d[dx].hl ^ 0x00020002u;
-#else
-            w.d[dx].hl = *reinterpret_cast<const u32x4 *>(r + (int64_t)dx * NCH * 2 * O * 12);
-            w.d[dx].hh = *reinterpret_cast<const u32x4 *>(r + (int64_t)dx * NCH * 2 * O * 12 + 4);
-            w.d[dx].mm = *reinterpret_cast<const u32x4 *>(r + (int64_t)dx * NCH * 2 * O * 12 + 8);
-#endif
-        }
-        return w;
-    };
-    struct Opnd { u32x4 lh[6], hm[6]; };
-    f32x16 acc[4];
-    W3Rec w0, w1;                                      // weights of flattened step q, q+1
-    if (n_items > 0) w0 = load_w(0);
-    __syncthreads();                                   // item 0 staged
-    for (int k = 1; k <= n_items; ++k) {
-        const int item = k - 1, cc = item % NCH;
-        const unsigned *ab = cd_lds + (item & 1) * CD_BUFS + a_off;
-        if (cc == 0) {
-#pragma unroll
-            for (int m = 0; m < 4; ++m)
-#pragma unroll
-                for (int v = 0; v < 16; ++v) acc[m][v] = 0.0f;
-        }
-        auto load_a = [&](int st, Opnd &a) {
-            const int dz = st / 3, dy = st % 3;
-#pragma unroll
-            for (int j = 0; j < 6; ++j) {
-                const unsigned *p = ab + dz * CD_ZP + dy * CD_ROW + j * CD_VOX;
-                a.lh[j] = *reinterpret_cast<const u32x4 *>(p);
-                a.hm[j] = *reinterpret_cast<const u32x4 *>(p + 4);
-            }
-        };
-        Opnd a0, a1;
-        load_a(0, a0);
-        const int q0 = item * 9;
-        float s0[4];                                       // SKIP: the first value of each xs row of this lane
-        unsigned so[4];                                    // ... and the rows' element offsets in the sample
-        CD_STAMP(0);
-#pragma unroll
-        for (int st = 0; st < 9; ++st) {
-            if (SKIP && st == 8 && cc == NCH - 1) {
-                // voxels outside the volume (edge blocks) read a clamped address; their rows are never stored
-                int b, ox0, oy0, oz0;
-                decode(item, b, ox0, oy0, oz0);
-                // wave-uniform sample base + a 32-bit lane offset (a sample of xs is below 2^31 bytes: the entry's range check)
-                const float *xb = xs + (int64_t)b * X * Y * Z * CS;
-                const int ys = min(oy0 + (t & 7), Y - 1), zs = min(oz0 + (t >> 3), Z - 1);
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    const int xv = min(ox0 + 4 * wave + i, X - 1);
-                    so[i] = (unsigned)(((xv * Y + ys) * Z + zs) * CS + 4 * h);
-                    s0[i] = xb[so[i]];
-                }
-            }
-            __builtin_amdgcn_sched_barrier(0);
-            w1 = load_w(min(q0 + st + 1, n_items * 9 - 1));             // unconditional: a branch here costs the register renaming
-            if (st + 1 < 9) load_a(st + 1, a1);
-#pragma unroll
-            for (int dx = 0; dx < 3; ++dx) {
-#pragma unroll
-                for (int i = 0; i < 4; ++i) acc[i] = mfma_bf16(a0.lh[i + dx], w0.d[dx].hl, acc[i]);
-#pragma unroll
-                for (int i = 0; i < 4; ++i) acc[i] = mfma_bf16(a0.hm[i + dx], w0.d[dx].hh, acc[i]);
-#pragma unroll
-                for (int i = 0; i < 4; ++i) acc[i] = mfma_bf16(a0.hm[i + dx], w0.d[dx].mm, acc[i]);
-            }
-            // issue order: one load between matrix instructions (a wave blocked on LDS issue cannot issue its matrix
-            // instructions either: tools/conv3_timeline.py)
-#pragma unroll
-            for (int r = 0; r < 12; ++r) {
-                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);      // 1 MFMA
-                __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);      // 1 DS read
-            }
-#pragma unroll
-            for (int r = 0; r < 9; ++r) {
-                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);      // 1 MFMA
-                __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);      // 1 VMEM read
-            }
-            __builtin_amdgcn_sched_group_barrier(0x008, 15, 0);
-            __builtin_amdgcn_sched_barrier(0);
-            a0 = a1;
-            w0 = w1;
-        }
-        CD_STAMP(1);
-        if (SKIP && cc == NCH - 1) {
-            float4 sv[2][4];                               // xs rows of this lane, [chunk][i]
-            {
-                // the rest of a voxel's 64 bytes: the cache line was requested a step ago
-                int b, ox0, oy0, oz0;
-                decode(item, b, ox0, oy0, oz0);
-                const float *xb = xs + (int64_t)b * X * Y * Z * CS;
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    const float *p = xb + so[i];
-                    sv[0][i] = make_float4(s0[i], p[1], p[2], p[3]);
-                    sv[1][i] = *reinterpret_cast<const float4 *>(p + 8);
-                }
-            }
-            // the weight records (L2 hits: 6 KB shared by every workgroup) arrive while the rows are split
-            CdRec ws[2];
-#pragma unroll
-            for (int c2 = 0; c2 < 2; ++c2) {
-                const unsigned *r = WS + (unsigned)(((c2 * 2 + h) * O + t) * 12);
-                ws[c2].hl = *reinterpret_cast<const u32x4 *>(r);
-                ws[c2].hh = *reinterpret_cast<const u32x4 *>(r + 4);
-                ws[c2].mm = *reinterpret_cast<const u32x4 *>(r + 8);
-            }
-#pragma unroll
-            for (int c2 = 0; c2 < 2; ++c2) {
-                __builtin_amdgcn_sched_barrier(0);         // one chunk's pieces at a time: both would not fit the registers
-                u32x4 lh[4], hm[4];
-#pragma unroll
-                for (int i = 0; i < 4; ++i) split3(sv[c2][i], lh[i], hm[i]);
-#pragma unroll
-                for (int i = 0; i < 4; ++i) acc[i] = mfma_bf16(lh[i], ws[c2].hl, acc[i]);
-#pragma unroll
-                for (int i = 0; i < 4; ++i) acc[i] = mfma_bf16(hm[i], ws[c2].hh, acc[i]);
-#pragma unroll
-                for (int i = 0; i < 4; ++i) acc[i] = mfma_bf16(hm[i], ws[c2].mm, acc[i]);
-            }
-        }
-        if (cc == NCH - 1) {
-            // D of the 32x32 MFMA: lane (col = t, h) holds rows m = 8 (v >> 2) + (v & 3) + 4 h, v = 0..15, of every accumulator;
-            // row m of accumulator i is voxel (x = 4 wave + i, y = m & 7, z = m >> 3).  Each accumulator goes through the wave's
-            // 4 KB of LDS scratch [voxel][channel] and comes back as (voxel, 4 channels) per lane: shift, residual, ReLU,
-            // the fp32 result as float4 (128 B per voxel over 8 lanes) and / or the split operands for the next layer
-            int b, ox0, oy0, oz0;
-            decode(item, b, ox0, oy0, oz0);
-            if (ox0 + CD_BX <= X && oy0 + CD_BY <= Y && oz0 + CD_BZ <= Z) {
-                // fp32 result only, interior block: straight from the accumulators, lane (t, h) owns channel t of voxels
-                // (x = 4 wave + i, y = 4 h + (v & 3), z = v >> 2); 128-byte rows per store, no LDS round trip (3 k cycles
-                // against 6-9 k for the transposed form below)
-                const float sh = shift[t];
-                const int64_t obase = ((((int64_t)b * X + ox0 + 4 * wave) * Y + oy0 + 4 * h) * Z + oz0) * O + t;
-#pragma unroll
-                for (int i = 0; i < 4; ++i)
-#pragma unroll
-                    for (int v = 0; v < 16; ++v) {
-                        const int64_t idx = obase + (((int64_t)i * Y + (v & 3)) * Z + (v >> 2)) * O;
-                        float val = acc[i][v] + sh;
-                        if (MODE == 2) val += res[idx];
-                        if (MODE >= 1) val = SKIP ? relu_keep_nan(val) : fmaxf(val, 0.0f);
-                        if (MODE == 3) val += res[idx];
-#if SP3D_W16_ABLATE & 16
-                        if (val == 123.456f)
-#endif
-                        y[idx] = val;
-                    }
-            } else {
-            float *scr = reinterpret_cast<float *>(cd_lds + 2 * CD_BUFS) + wave * 1024;
-            const int g = lane & 7;                                          // channel group of this lane on the way out
-            const float4 sh4 = *reinterpret_cast<const float4 *>(shift + 4 * g);
-#pragma unroll
-            for (int mb = 0; mb < 4; ++mb) {
-#pragma unroll
-                for (int v = 0; v < 16; ++v) scr[(8 * (v >> 2) + (v & 3) + 4 * h) * 32 + t] = acc[mb][v];
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                __builtin_amdgcn_wave_barrier();
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const int m = (lane >> 3) + 8 * r;
-                    float4 a = *reinterpret_cast<const float4 *>(scr + m * 32 + 4 * g);
-                    const int xo = ox0 + 4 * wave + mb, yo = oy0 + (m & 7), zo = oz0 + (m >> 3);
-                    if (xo < X && yo < Y && zo < Z) {
-                        const int64_t vox = (((int64_t)b * X + xo) * Y + yo) * Z + zo;
-                        a.x += sh4.x; a.y += sh4.y; a.z += sh4.z; a.w += sh4.w;
-                        float4 rr = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-                        if (MODE >= 2) rr = *reinterpret_cast<const float4 *>(res + vox * O + 4 * g);
-                        if (MODE == 2) { a.x += rr.x; a.y += rr.y; a.z += rr.z; a.w += rr.w; }
-                        if (MODE >= 1 && SKIP) { a.x = relu_keep_nan(a.x); a.y = relu_keep_nan(a.y); a.z = relu_keep_nan(a.z); a.w = relu_keep_nan(a.w); }
-                        if (MODE >= 1 && !SKIP) { a.x = fmaxf(a.x, 0.0f); a.y = fmaxf(a.y, 0.0f); a.z = fmaxf(a.z, 0.0f); a.w = fmaxf(a.w, 0.0f); }
-                        if (MODE == 3) { a.x += rr.x; a.y += rr.y; a.z += rr.z; a.w += rr.w; }
-#if SP3D_W16_ABLATE & 16
-                        if (a.x == 123.456f)
-#endif
-                        *reinterpret_cast<float4 *>(y + vox * O + 4 * g) = a;
-                    }
-                }
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                __builtin_amdgcn_wave_barrier();
-            }
-            }
-        }
-        CD_STAMP(2);
-        __syncthreads();
-        CD_STAMP(3);
-    }
-}
-
-
 } // namespace sp3d
+
+using namespace sp3d;
+
+// the checks the four entries share: x, weights, y, shift and (mode >= 2) the residual; `supported` is the entry's own
+static int wino_fused_check(const void *x, const void *U, const void *y, const void *shift, const void *residual, int mode, int B,
+                            int X, int Y, int Z, bool supported, const Conv3Grid &g)
+{
+    return conv3_check(B, X, Y, Z, mode, x && U && y && shift && (mode < 2 || residual), supported, g.blocks <= 0x7fffffff);
+}
 
 extern "C" int sp3d_wino_fused(const float *x, const float *U, float *y, const float *shift, const float *residual, int mode,
                                int B, int X, int Y, int Z, int C, int O, void *stream)
 {
-    using namespace sp3d;
-    if (B <= 0 || X <= 0 || Y <= 0 || Z <= 0 || mode < 0 || mode > 3) return SP3D_EINVAL;
-    if (!x || !U || !y || !shift || (mode >= 2 && !residual)) return SP3D_ENULL;
-    if (O != 32 || (C != 16 && C != 32)) return SP3D_EUNSUPPORTED;
-    const int NBX = (X + 7) / 8, NBY = (Y + 7) / 8, NBZ = (Z + 3) / 4;
-    const int64_t blocks = (int64_t)B * NBX * NBY * NBZ;
-    if (blocks > 0x7fffffff) return SP3D_ERANGE;
-    const dim3 grid((unsigned)blocks), block(64);
-    hipStream_t s = (hipStream_t)stream;
-#define SP3D_WF(C_, M_) hipLaunchKernelGGL((wino_fused_kernel<C_, M_>), grid, block, 0, s, x, U, y, shift, residual, B, X, Y, Z, NBX, NBY, NBZ)
-#define SP3D_WFM(C_) switch (mode) { case 0: SP3D_WF(C_, 0); break; case 1: SP3D_WF(C_, 1); break; case 2: SP3D_WF(C_, 2); break; default: SP3D_WF(C_, 3); }
-    if (C == 16) { SP3D_WFM(16) } else { SP3D_WFM(32) }
-#undef SP3D_WFM
-#undef SP3D_WF
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? SP3D_OK : (int)e;
+    const Conv3Grid g = conv3_grid(B, X, Y, Z, 8, 8, 4);
+    if (const int rc = wino_fused_check(x, U, y, shift, residual, mode, B, X, Y, Z, O == 32 && (C == 16 || C == 32), g)) return rc;
+    auto launch = [&](auto c, auto m) {
+        hipLaunchKernelGGL((wino_fused_kernel<decltype(c)::value, decltype(m)::value>), dim3((unsigned)g.blocks), dim3(64), 0,
+                           (hipStream_t)stream, x, U, y, shift, residual, B, X, Y, Z, g.NBX, g.NBY, g.NBZ);
+    };
+    with_mode(mode, [&](auto m) { if (C == 16) launch(int_c<16>{}, m); else launch(int_c<32>{}, m); });
+    return launch_status();
 }
 
 extern "C" int sp3d_debug_wino_fused_timeline(void *dev_buffer)
@@ -1370,140 +844,49 @@ extern "C" int sp3d_debug_wino_fused_timeline(void *dev_buffer)
 extern "C" int sp3d_wino_fused_split(const float *x, const void *U3, float *y, const float *shift, const float *residual, int mode,
                                      int B, int X, int Y, int Z, int C, int O, void *stream)
 {
-    using namespace sp3d;
-    if (B <= 0 || X <= 0 || Y <= 0 || Z <= 0 || mode < 0 || mode > 3) return SP3D_EINVAL;
-    if (!x || !U3 || !y || !shift || (mode >= 2 && !residual)) return SP3D_ENULL;
-    if (O != 32 || (C != 16 && C != 32) || (reinterpret_cast<uintptr_t>(U3) & 7)) return SP3D_EUNSUPPORTED;
-    const int NBX = (X + 7) / 8, NBY = (Y + 7) / 8, NBZ = (Z + 3) / 4;
-    const int64_t blocks = (int64_t)B * NBX * NBY * NBZ;
-    if (blocks > 0x7fffffff) return SP3D_ERANGE;
-    const dim3 grid((unsigned)blocks), block(64);
-    hipStream_t s = (hipStream_t)stream;
-    const unsigned *u3 = reinterpret_cast<const unsigned *>(U3);
-#define SP3D_WF(C_, M_) hipLaunchKernelGGL((wino_fused3_kernel<C_, M_>), grid, block, 0, s, x, u3, y, shift, residual, B, X, Y, Z, NBX, NBY, NBZ)
-#define SP3D_WFM(C_) switch (mode) { case 0: SP3D_WF(C_, 0); break; case 1: SP3D_WF(C_, 1); break; case 2: SP3D_WF(C_, 2); break; default: SP3D_WF(C_, 3); }
-    if (C == 16) { SP3D_WFM(16) } else { SP3D_WFM(32) }
-#undef SP3D_WFM
-#undef SP3D_WF
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? SP3D_OK : (int)e;
+    const Conv3Grid g = conv3_grid(B, X, Y, Z, 8, 8, 4);
+    const bool supported = O == 32 && (C == 16 || C == 32) && !(reinterpret_cast<uintptr_t>(U3) & 7);
+    if (const int rc = wino_fused_check(x, U3, y, shift, residual, mode, B, X, Y, Z, supported, g)) return rc;
+    auto launch = [&](auto c, auto m) {
+        hipLaunchKernelGGL((wino_fused3_kernel<decltype(c)::value, decltype(m)::value>), dim3((unsigned)g.blocks), dim3(64), 0,
+                           (hipStream_t)stream, x, reinterpret_cast<const unsigned *>(U3), y, shift, residual, B, X, Y, Z, g.NBX,
+                           g.NBY, g.NBZ);
+    };
+    with_mode(mode, [&](auto m) { if (C == 16) launch(int_c<16>{}, m); else launch(int_c<32>{}, m); });
+    return launch_status();
 }
+
+// waves per block of wino_fused16_kernel: two output groups x two input-channel groups of one wave each (2 waves per SIMD
+// resident): best of the {1,2,4} x {1,2} configurations measured at (4,64,40,40,10) / (4,32,40,40,10) / (8,64,32,32,32) in
+// round 2; the others are no longer instantiated
+constexpr int W16_NBW = 2, W16_KS = 2;
 
 extern "C" int sp3d_wino_fused_split64(const float *x, const void *U3, float *y, const float *shift, const float *residual,
                                        int mode, int B, int X, int Y, int Z, int C, int O, void *stream)
 {
-    using namespace sp3d;
-    if (B <= 0 || X <= 0 || Y <= 0 || Z <= 0 || mode < 0 || mode > 3) return SP3D_EINVAL;
-    if (!x || !U3 || !y || !shift || (mode >= 2 && !residual)) return SP3D_ENULL;
-    if (O != 64 || (C != 32 && C != 64) || (reinterpret_cast<uintptr_t>(U3) & 7)) return SP3D_EUNSUPPORTED;
-    const int NBX = (X + 7) / 8, NBY = (Y + 7) / 8, NBZ = (Z + 1) / 2;
-    const int64_t blocks = (int64_t)B * NBX * NBY * NBZ;
-    if (blocks > 0x7fffffff) return SP3D_ERANGE;
-    // waves per block: two output groups x two input-channel groups of one wave each (2 waves per SIMD resident): best of the
-    // {1,2,4} x {1,2} configurations measured at (4,64,40,40,10) / (4,32,40,40,10) / (8,64,32,32,32) in round 2; the others
-    // are no longer instantiated
-    constexpr int nbw = 2, ks = 2;
-    hipStream_t s = (hipStream_t)stream;
-    const unsigned *u3 = reinterpret_cast<const unsigned *>(U3);
-    const dim3 grid((unsigned)blocks), block(64 * (4 / nbw) * ks);
-#define SP3D_WF(C_, M_) hipLaunchKernelGGL((wino_fused16_kernel<C_, M_, 2, 2>), grid, block, 0, s, x, u3, y, shift, residual, B, X, Y, Z, NBX, NBY, NBZ, (const float *)nullptr, (const unsigned *)nullptr)
-#define SP3D_WFM(C_) switch (mode) { case 0: SP3D_WF(C_, 0); break; case 1: SP3D_WF(C_, 1); break; case 2: SP3D_WF(C_, 2); break; default: SP3D_WF(C_, 3); }
-    if (C == 32) { SP3D_WFM(32) } else { SP3D_WFM(64) }
-#undef SP3D_WFM
-#undef SP3D_WF
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? SP3D_OK : (int)e;
-}
-
-// launch of conv3_split_kernel behind sp3d_conv3_split (xs == nullptr) and sp3d_conv3_split_skip (C = 32, mode 1, the skip
-// term of xs / WS on the accumulators); the arguments are validated
-static int conv3_split_launch(const float *x, const void *W3, float *y, const float *shift, const float *residual, int mode,
-                              const float *xs, const void *WS, int B, int X, int Y, int Z, int C, void *stream)
-{
-    using namespace sp3d;
-    const int NBX = (X + CD_BX - 1) / CD_BX, NBY = (Y + CD_BY - 1) / CD_BY, NBZ = (Z + CD_BZ - 1) / CD_BZ;
-    const int64_t blocks = (int64_t)B * NBX * NBY * NBZ;
-    if (blocks > 0x7fffffff) return SP3D_ERANGE;
-    static int cu_count[64] = {0};                     // per device, queried once (hipGetDeviceProperties is slow)
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < 64) {
-        if (cu_count[dev] == 0) {
-            int n = 0;
-            cu_count[dev] = (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0) ? n : 256;
-        }
-        cus = cu_count[dev];
-    }
-    // persistent workgroups, one per CU (158 KB of LDS each), an equal number of blocks each
-    const int rounds = (int)((blocks + cus - 1) / cus);
-    const int nwg = (int)((blocks + rounds - 1) / rounds);
-    const dim3 grid((unsigned)nwg), block(64 * (4 + CD_PROD));
-    const size_t lds = (size_t)2 * CD_BUFS * sizeof(unsigned) + 4 * 1024 * sizeof(float);
-    hipStream_t s = (hipStream_t)stream;
-    const unsigned *w3 = reinterpret_cast<const unsigned *>(W3), *wsk = reinterpret_cast<const unsigned *>(WS);
-    // the attribute is per device: remember it per device (a process that drives several GPUs launches on each)
-    int cd_dev = 0;
-    { const hipError_t ed = hipGetDevice(&cd_dev); if (ed != hipSuccess) return (int)ed; }
-    if (cd_dev < 0 || cd_dev >= 64) cd_dev = 63;
-#define SP3D_CD(C_, M_, S_) { static bool attr_dev[64] = {}; bool &attr = attr_dev[cd_dev]; if (!attr || cd_dev == 63) { hipError_t ea = hipFuncSetAttribute(reinterpret_cast<const void *>(conv3_split_kernel<C_, M_, S_>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); if (ea != hipSuccess) return (int)ea; attr = true; } \
-    hipLaunchKernelGGL((conv3_split_kernel<C_, M_, S_>), grid, block, lds, s, x, w3, y, shift, residual, B, X, Y, Z, NBX, NBY, NBZ, (int)blocks, xs, wsk); }
-#define SP3D_CDI(C_) switch (mode) { case 0: SP3D_CD(C_, 0, false); break; case 1: SP3D_CD(C_, 1, false); break; case 2: SP3D_CD(C_, 2, false); break; default: SP3D_CD(C_, 3, false); }
-    if (xs) { SP3D_CD(32, 1, true) } else if (C == 16) { SP3D_CDI(16) } else { SP3D_CDI(32) }
-#undef SP3D_CDI
-#undef SP3D_CD
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? SP3D_OK : (int)e;
+    const Conv3Grid g = conv3_grid(B, X, Y, Z, 8, 8, 2);
+    const bool supported = O == 64 && (C == 32 || C == 64) && !(reinterpret_cast<uintptr_t>(U3) & 7);
+    if (const int rc = wino_fused_check(x, U3, y, shift, residual, mode, B, X, Y, Z, supported, g)) return rc;
+    auto launch = [&](auto c, auto m) {
+        hipLaunchKernelGGL((wino_fused16_kernel<decltype(c)::value, decltype(m)::value, W16_NBW, W16_KS>), dim3((unsigned)g.blocks),
+                           dim3(64 * (4 / W16_NBW) * W16_KS), 0, (hipStream_t)stream, x, reinterpret_cast<const unsigned *>(U3), y,
+                           shift, residual, B, X, Y, Z, g.NBX, g.NBY, g.NBZ, (const float *)nullptr, (const unsigned *)nullptr);
+    };
+    with_mode(mode, [&](auto m) { if (C == 32) launch(int_c<32>{}, m); else launch(int_c<64>{}, m); });
+    return launch_status();
 }
 
 extern "C" int sp3d_wino_fused_split64_skip(const float *x, const void *U3, float *y, const float *shift, const float *xs,
                                             const void *WS, int B, int X, int Y, int Z, int C, int O, int CS, void *stream)
 {
-    using namespace sp3d;
-    if (B <= 0 || X <= 0 || Y <= 0 || Z <= 0) return SP3D_EINVAL;
-    if (!x || !U3 || !y || !shift || !xs || !WS) return SP3D_ENULL;
-    if (O != 64 || C != 64 || CS != 32 || (reinterpret_cast<uintptr_t>(U3) & 7)) return SP3D_EUNSUPPORTED;
-    if ((reinterpret_cast<uintptr_t>(WS) & 7) || (reinterpret_cast<uintptr_t>(xs) & 15)) return SP3D_EUNSUPPORTED;
-    if ((int64_t)X * Y * Z * CS > 0x7fffffff) return SP3D_ERANGE;          // the kernel's 32-bit offsets inside a sample of xs
-    const int NBX = (X + 7) / 8, NBY = (Y + 7) / 8, NBZ = (Z + 1) / 2;
-    const int64_t blocks = (int64_t)B * NBX * NBY * NBZ;
-    if (blocks > 0x7fffffff) return SP3D_ERANGE;
-    hipStream_t s = (hipStream_t)stream;
-    const dim3 grid((unsigned)blocks), block(64 * 2 * 2);                  // the configuration of sp3d_wino_fused_split64
-    hipLaunchKernelGGL((wino_fused16_kernel<64, 1, 2, 2, true>), grid, block, 0, s, x, reinterpret_cast<const unsigned *>(U3), y, shift,
-                       (const float *)nullptr, B, X, Y, Z, NBX, NBY, NBZ, xs, reinterpret_cast<const unsigned *>(WS));
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? SP3D_OK : (int)e;
-}
-
-extern "C" int sp3d_conv3_split(const float *x, const void *W3, float *y, const float *shift, const float *residual, int mode,
-                                int B, int X, int Y, int Z, int C, int O, void *stream)
-{
-    if (B <= 0 || X <= 0 || Y <= 0 || Z <= 0 || mode < 0 || mode > 3) return SP3D_EINVAL;
-    if (!x || !W3 || !y || !shift || (mode >= 2 && !residual)) return SP3D_ENULL;
-    if (O != 32 || (C != 16 && C != 32) || (reinterpret_cast<uintptr_t>(W3) & 15)) return SP3D_EUNSUPPORTED;
-    if (reinterpret_cast<uintptr_t>(y) & 15) return SP3D_EUNSUPPORTED;
-    if ((int64_t)X * Y * Z * C * 2 > 0x7fffffff) return SP3D_ERANGE;
-    return conv3_split_launch(x, W3, y, shift, residual, mode, nullptr, nullptr, B, X, Y, Z, C, stream);
-}
-
-extern "C" int sp3d_conv3_split_skip(const float *x, const void *W3, float *y, const float *shift, const float *xs,
-                                     const void *WS, int B, int X, int Y, int Z, int C, int O, int CS, void *stream)
-{
-    if (B <= 0 || X <= 0 || Y <= 0 || Z <= 0) return SP3D_EINVAL;
-    if (!x || !W3 || !y || !shift || !xs || !WS) return SP3D_ENULL;
-    if (O != 32 || C != 32 || CS != 16) return SP3D_EUNSUPPORTED;
-    if ((reinterpret_cast<uintptr_t>(W3) | reinterpret_cast<uintptr_t>(WS) | reinterpret_cast<uintptr_t>(xs) |
-         reinterpret_cast<uintptr_t>(y)) & 15) return SP3D_EUNSUPPORTED;
-    if ((int64_t)X * Y * Z * C * 2 > 0x7fffffff) return SP3D_ERANGE;
-    return conv3_split_launch(x, W3, y, shift, nullptr, 1, xs, WS, B, X, Y, Z, C, stream);
-}
-
-extern "C" int sp3d_debug_conv3_timeline(void *dev_buffer)
-{
-#ifdef SP3D_CD_TIMELINE
-    unsigned long long *p = (unsigned long long *)dev_buffer;
-    return (int)hipMemcpyToSymbol(HIP_SYMBOL(sp3d::g_cd_tl), &p, sizeof(p));
-#else
-    (void)dev_buffer;
-    return SP3D_EUNSUPPORTED;
-#endif
+    const Conv3Grid g = conv3_grid(B, X, Y, Z, 8, 8, 2);
+    const bool supported = O == 64 && C == 64 && CS == 32 && !((reinterpret_cast<uintptr_t>(U3) | reinterpret_cast<uintptr_t>(WS)) & 7) &&
+                           !(reinterpret_cast<uintptr_t>(xs) & 15);
+    // (the kernel's 32-bit offsets inside a sample of xs)
+    const bool in_range = (int64_t)X * Y * Z * CS <= 0x7fffffff && g.blocks <= 0x7fffffff;
+    if (const int rc = conv3_check(B, X, Y, Z, 1, x && U3 && y && shift && xs && WS, supported, in_range)) return rc;
+    hipLaunchKernelGGL((wino_fused16_kernel<64, 1, W16_NBW, W16_KS, true>), dim3((unsigned)g.blocks),
+                       dim3(64 * (4 / W16_NBW) * W16_KS), 0, (hipStream_t)stream, x, reinterpret_cast<const unsigned *>(U3), y,
+                       shift, (const float *)nullptr, B, X, Y, Z, g.NBX, g.NBY, g.NBZ, xs, reinterpret_cast<const unsigned *>(WS));
+    return launch_status();
 }

@@ -68,7 +68,11 @@ def test_signature_tables_match_the_headers():
         assert sorted(bound) == sorted(declared), sorted(set(bound) ^ set(declared))
         for name in declared:
             assert bound[name] == declared[name], (name, table[name])
-    assert len(_lib.SIGNATURES) == 51 and _lib.EXPORTS == list(_lib.SIGNATURES)
+    assert len(_lib.SIGNATURES) == 57 and _lib.EXPORTS == list(_lib.SIGNATURES)
+    # by name, not by count alone: the entries that once had headers and tables of their own
+    for name in ("sp3d_unproject_one_fwd_train", "sp3d_unproject_one_bwd", "sp3d_unproject_one_bwd_det", "sp3d_upconv2x_fused",
+                 "sp3d_conv3_split_skip", "sp3d_wino_fused_split64_skip"):
+        assert name in _lib.SIGNATURES, name
     assert not set(_lib.SIGNATURES) & set(_lib.TUNING_SIGNATURES)
     # the rule itself, on prototypes written here (a parser that returned nothing would pass the loop above vacuously)
     assert _lib.SIGNATURES["sp3d_abi_version"] == "i:" and _table_signatures({"f": "l: p i l f d"})["f"] == \
@@ -183,6 +187,60 @@ def test_argument_validation_before_any_launch(lib):
     assert lib.sp3d_nms_topk_workspace_bytes(1, 64, 64, 64, 10) == 16 * 8 * 2 * 10 * 8
     assert lib.sp3d_soft_argmax(dummy, dummy, dummy, 0, 15, 64, C.c_float(100.0), None) == -1
     assert b"NULL" in lib.sp3d_error_string(-2)
+
+
+def test_conv3_entries_refuse_in_the_documented_order(lib):
+    """the C entries of the 3x3x3 convolutions (csrc/sp3d_wino.hip, sp3d_wino_fused.hip, sp3d_conv3_direct.hip) share one
+    argument check: SP3D_EINVAL, then SP3D_ENULL, then SP3D_EUNSUPPORTED, then SP3D_ERANGE, all before the first HIP call.
+    EVERY call below breaks at least one rule - the dummy pointers are never dereferenced, with or without a GPU."""
+    hdr = open(os.path.join(ROOT, "include", "sp3d.h")).read()
+    EINVAL, ENULL, ERANGE, EUNSUPPORTED = (int(re.search(name + r"\s*=\s*(-?\d+)", hdr).group(1))
+                                           for name in ("SP3D_EINVAL", "SP3D_ENULL", "SP3D_ERANGE", "SP3D_EUNSUPPORTED"))
+    assert len({0, EINVAL, ENULL, ERANGE, EUNSUPPORTED}) == 5
+    d, off4 = C.c_void_p(0x1000), C.c_void_p(0x1004)
+    big = dict(B=1 << 20, X=1024, Y=1024, Z=1024)
+
+    def with_mode(name, Cin, Oout):          # (x, weights, y, shift, residual, mode, B, X, Y, Z, C, O, stream)
+        def call(x=d, w=d, res=None, mode=0, B=1, X=8, Y=8, Z=8, O=Oout):
+            return getattr(lib, name)(x, w, d, d, res, mode, B, X, Y, Z, Cin, O, None)
+        return call
+
+    def with_skip(name, Cin, Oout, CS):      # (x, weights, y, shift, xs, WS, B, X, Y, Z, C, O, CS, stream)
+        def call(x=d, w=d, xs=d, B=1, X=8, Y=8, Z=8, O=Oout):
+            return getattr(lib, name)(x, w, d, d, xs, d, B, X, Y, Z, Cin, O, CS, None)
+        return call
+
+    moded = [with_mode("sp3d_wino_fused", 32, 32), with_mode("sp3d_wino_fused_split", 32, 32),
+             with_mode("sp3d_wino_fused_split64", 64, 64), with_mode("sp3d_conv3_split", 32, 32)]
+    skips = [with_skip("sp3d_wino_fused_split64_skip", 64, 64, 32), with_skip("sp3d_conv3_split_skip", 32, 32, 16)]
+    for f in moded + skips:
+        assert f(B=0) == EINVAL
+        assert f(x=None) == ENULL
+        assert f(O=48) == EUNSUPPORTED
+        assert f(**big) == ERANGE
+        # the order: the earlier rule answers for a call that breaks several
+        assert f(B=0, x=None, O=48) == EINVAL
+        assert f(x=None, O=48, **big) == ENULL
+        assert f(O=48, **big) == EUNSUPPORTED
+    for f in moded:
+        assert f(mode=4) == EINVAL and f(mode=-1) == EINVAL and f(mode=4, x=None) == EINVAL
+        assert f(mode=2) == ENULL and f(mode=3) == ENULL          # a residual mode without the residual
+        assert f(mode=2, O=48) == ENULL
+    for f in moded[1:] + skips:                                    # the split weights' alignment (the fp32 U has none)
+        assert f(w=off4) == EUNSUPPORTED and f(w=off4, **big) == EUNSUPPORTED
+    for f in skips:
+        assert f(xs=None) == ENULL and f(xs=None, O=48) == ENULL
+        assert f(xs=off4) == EUNSUPPORTED
+    # the three-launch transforms: any channel count is supported, so there is no third code
+    wi, wo = lib.sp3d_wino_input, lib.sp3d_wino_output
+    assert wi(d, d, 0, 8, 8, 8, 32, None) == EINVAL and wi(d, d, 1, 8, 8, 8, 0, None) == EINVAL
+    assert wi(None, d, 1, 8, 8, 8, 32, None) == ENULL and wi(None, d, 0, 8, 8, 8, 32, None) == EINVAL
+    assert wi(d, d, 1 << 20, 1024, 1024, 1024, 32, None) == ERANGE and wi(d, None, 1 << 20, 1024, 1024, 1024, 32, None) == ENULL
+    assert wo(d, d, d, None, 0, 0, 8, 8, 8, 32, None) == EINVAL and wo(d, d, d, None, 4, 1, 8, 8, 8, 32, None) == EINVAL
+    assert wo(d, d, d, None, 0, 1, 8, 8, 8, 0, None) == EINVAL
+    assert wo(None, d, d, None, 0, 1, 8, 8, 8, 32, None) == ENULL and wo(d, d, d, None, 2, 1, 8, 8, 8, 32, None) == ENULL
+    assert wo(d, d, d, None, 1, 1 << 20, 1024, 1024, 1024, 32, None) == ERANGE
+    assert wo(d, d, d, None, 2, 1 << 20, 1024, 1024, 1024, 32, None) == ENULL
 
 
 def test_missing_library_fails_loudly(monkeypatch, tmp_path):

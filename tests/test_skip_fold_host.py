@@ -1,16 +1,15 @@
 """Host side of the folded 1x1x1 skip projections (sp3d_conv3_split_skip, sp3d_wino_fused_split64_skip): the weight records
-hold the projection exactly in the order the kernels and include/sp3d_skip_fold.h index them, the header matches the
-binding's table, and both entries refuse bad arguments before anything reaches the GPU runtime (no GPU needed: every call
-below is refused, the dummy pointers are never dereferenced)."""
+hold the projection exactly in the order the kernels and include/sp3d.h index them, and both entries refuse bad arguments
+before anything reaches the GPU runtime (no GPU needed: every call below is refused, the dummy pointers are never
+dereferenced)."""
 import ctypes as C
 import os
 
 import pytest
 import torch
 
-from tests.test_host_cabi import ROOT, _header_signatures, _table_signatures
+from tests.test_host_cabi import ROOT
 
-ENTRIES = ["sp3d_conv3_split_skip", "sp3d_wino_fused_split64_skip"]
 EINVAL, ENULL, ERANGE, EUNSUPPORTED = -1, -2, -3, -4
 
 
@@ -27,21 +26,6 @@ def test_error_codes_are_the_headers():
     for name, val in (("SP3D_EINVAL", EINVAL), ("SP3D_ENULL", ENULL), ("SP3D_ERANGE", ERANGE), ("SP3D_EUNSUPPORTED", EUNSUPPORTED)):
         m = re.search(name + r"\s*=\s*(-?\d+)", src)
         assert m and int(m.group(1)) == val, name
-
-
-def test_new_entries_are_declared_once_and_match_their_header():
-    """include/sp3d_skip_fold.h against the binding's table, both ways, by the rule of tests/test_host_cabi.py; sp3d.h includes
-    the header and its own table is untouched"""
-    from selfpose3d_amd import _lib
-    declared = _header_signatures(os.path.join(ROOT, "include", "sp3d_skip_fold.h"))
-    bound = _table_signatures(_lib.SKIP_FOLD_SIGNATURES)
-    assert sorted(declared) == sorted(bound) == sorted(ENTRIES)
-    for name in declared:
-        assert bound[name] == declared[name], name
-    others = set(_lib.SIGNATURES) | set(_lib.TUNING_SIGNATURES) | set(_lib.ONE_TRAIN_SIGNATURES) | set(_lib.UPCONV_SIGNATURES)
-    assert not set(_lib.SKIP_FOLD_SIGNATURES) & others
-    with open(os.path.join(ROOT, "include", "sp3d.h")) as fh:
-        assert '#include "sp3d_skip_fold.h"' in fh.read()
 
 
 def _wild(shape, g):

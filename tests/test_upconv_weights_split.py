@@ -1,24 +1,6 @@
 """_lib.upconv_weights_split (host side of sp3d_upconv2x_fused): the records hold the GEMM-form weight exactly, in the order
-the kernel and include/sp3d_upconv.h index them."""
-import os
-
+the kernel and include/sp3d.h index them."""
 import torch
-
-from tests.test_host_cabi import ROOT, _header_signatures, _table_signatures
-
-
-def test_new_entry_is_declared_once_and_matches_its_header():
-    """include/sp3d_upconv.h against the binding's table, both ways, by the rule of tests/test_host_cabi.py; sp3d.h includes
-    the header and its own table is untouched"""
-    from selfpose3d_amd import _lib
-    declared = _header_signatures(os.path.join(ROOT, "include", "sp3d_upconv.h"))
-    bound = _table_signatures(_lib.UPCONV_SIGNATURES)
-    assert sorted(declared) == sorted(bound) == ["sp3d_upconv2x_fused"]
-    for name in declared:
-        assert bound[name] == declared[name], name
-    assert not set(_lib.UPCONV_SIGNATURES) & (set(_lib.SIGNATURES) | set(_lib.TUNING_SIGNATURES) | set(_lib.ONE_TRAIN_SIGNATURES))
-    with open(os.path.join(ROOT, "include", "sp3d.h")) as fh:
-        assert '#include "sp3d_upconv.h"' in fh.read()
 
 
 def test_upconv_weight_records_reproduce_the_weight_exactly():
