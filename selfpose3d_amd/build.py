@@ -13,10 +13,11 @@ import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
-SOURCES = ["sp3d_unproject.hip", "sp3d_proposal.hip", "sp3d_epilogue.hip", "sp3d_upconv.hip", "sp3d_synth.hip", "sp3d_fftconv.hip", "sp3d_wino.hip",
+SOURCES = ["sp3d_unproject.hip", "sp3d_unproject_tile.hip", "sp3d_unproject_pipe.hip", "sp3d_unproject_brick.hip", "sp3d_unproject_one.hip",
+           "sp3d_unproject_bwd.hip", "sp3d_proposal.hip", "sp3d_epilogue.hip", "sp3d_upconv.hip", "sp3d_synth.hip", "sp3d_fftconv.hip", "sp3d_wino.hip",
            "sp3d_wino_fused.hip", "sp3d_conv3_direct.hip", "sp3d_fft.hip", "sp3d_gbn.hip"]
 HEADERS = [os.path.join("..", "pk_src1.py"), "sp3d_conv3_host.h", "sp3d_device.h", "sp3d_proj_pk.h", "sp3d_split.h", "sp3d_tuning.h",
-           "sp3d_twiddles.h", os.path.join("..", "..", "include", "sp3d.h")]
+           "sp3d_twiddles.h", "sp3d_unproject_host.h", "sp3d_unproject_pipe.h", os.path.join("..", "..", "include", "sp3d.h")]
 LIB = os.path.join(HERE, "libsp3d.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-munsafe-fp-atomics", "-fPIC", "-shared",
@@ -117,7 +118,7 @@ def _compile_objects(objdir: str, extra_flags=(), verbose: bool = False, host_fl
     from concurrent.futures import ThreadPoolExecutor
     os.makedirs(objdir, exist_ok=True)
     cflags = [f for f in FLAGS if f != "-shared"]
-    with ThreadPoolExecutor(max_workers=len(SOURCES)) as pool:
+    with ThreadPoolExecutor(max_workers=min(len(SOURCES), 16)) as pool:      # at most 16 compiles at once: the build boxes give a command 16 CPUs
         futs = [pool.submit(_compile_one, src, objdir, cflags + list(extra_flags) + PER_SOURCE_FLAGS.get(src, []), verbose, host_flags)
                 for src in SOURCES]
         return [f.result() for f in futs]

@@ -1,7 +1,7 @@
 // sp3d_conv3_host.h - what the sources of the 3x3x3 convolutions share (sp3d_wino.hip, sp3d_wino_fused.hip,
 // sp3d_conv3_direct.hip).  Device side: the measurement switch and the ReLU of the kernels that fold a skip projection.
 // Host side: the pieces every C entry of the three files is made of - the argument check in the ABI's return-code order,
-// the grid of output blocks, the run-time mode as a compile-time constant, and the launch epilogue.
+// the grid of output blocks and the run-time mode as a compile-time constant (the launch epilogue is sp3d_device.h's).
 #ifndef SP3D_CONV3_HOST_H
 #define SP3D_CONV3_HOST_H
 #include <hip/hip_runtime.h>
@@ -10,6 +10,7 @@
 #include <type_traits>
 
 #include "../../include/sp3d.h"
+#include "sp3d_device.h"
 
 #ifndef SP3D_W16_ABLATE
 #define SP3D_W16_ABLATE 0      // measurement builds only (tools/diag_w16.py): 1 no MFMA, 2 no weight loads, 4 no split, 8 no LDS reads
@@ -50,13 +51,6 @@ template <class F> inline auto with_mode(int mode, F &&f)
     case 2: return f(int_c<2>{});
     default: return f(int_c<3>{});
     }
-}
-
-// return code of the launch just made
-inline int launch_status()
-{
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? SP3D_OK : (int)e;
 }
 
 } // namespace sp3d

@@ -504,4 +504,11 @@ __device__ __forceinline__ bool xcd_map_fast(int bid, const Geom &g, int &b, int
     return b < g.B;
 }
 
+// host: return code of the launch just made (what a C entry returns after its last launch)
+inline int launch_status()
+{
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? SP3D_OK : (int)e;
+}
+
 } // namespace sp3d

@@ -12,6 +12,7 @@
 #include <stdint.h>
 
 #include "../../include/sp3d.h"
+#include "sp3d_device.h"
 
 namespace sp3d {
 
@@ -68,8 +69,7 @@ extern "C" int sp3d_channel_shift_act(float *y, const float *shift, const float 
         switch (mode) { case 0: SP3D_EPI(0, false); break; case 1: SP3D_EPI(1, false); break; case 2: SP3D_EPI(2, false); break; default: SP3D_EPI(3, false); }
     }
 #undef SP3D_EPI
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? SP3D_OK : (int)e;
+    return launch_status();
 }
 
 // ------------------------------------------------------------------------------------------
@@ -173,8 +173,7 @@ extern "C" int sp3d_upsample2x_scatter(const float *G, float *out, const float *
     const int blocks = (int)((total + 255) / 256 < 16384 ? (total + 255) / 256 : 16384);
     hipLaunchKernelGGL(sp3d::upsample2x_scatter_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, G, out, shift, skip, n_in,
                        X, Y, Z, O);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? SP3D_OK : (int)e;
+    return launch_status();
 }
 
 
@@ -189,8 +188,7 @@ extern "C" int sp3d_upsample2x_scatter_head(const float *G, float *head, const f
     const int blocks = (int)((total + 255) / 256 < 16384 ? (total + 255) / 256 : 16384);
     hipLaunchKernelGGL(sp3d::upsample2x_scatter_head_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, G, head, shift,
                        skip, wout, bout, n_in, X, Y, Z, J);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? SP3D_OK : (int)e;
+    return launch_status();
 }
 
 
@@ -249,8 +247,7 @@ extern "C" int sp3d_fetch_ring(const float *ring, float *dst, uint32_t *counter,
     if (R <= 0 || n <= 0) return SP3D_EINVAL;
     if (!ring || !dst || !counter) return SP3D_ENULL;
     hipLaunchKernelGGL(sp3d::fetch_ring_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, ring, dst, counter, R, n);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? SP3D_OK : (int)e;
+    return launch_status();
 }
 
 
@@ -338,8 +335,7 @@ extern "C" int sp3d_maxpool2x_cl(const float *x, float *y, int B, int X, int Y, 
     const int64_t blocks = (n + 255) / 256;
     hipLaunchKernelGGL(sp3d::maxpool2x_cl_kernel, dim3((unsigned)(blocks > 65535 * 16 ? 65535 * 16 : blocks)), dim3(256), 0,
                        (hipStream_t)stream, x, y, B, X, Y, Z, C);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? SP3D_OK : (int)e;
+    return launch_status();
 }
 
 
@@ -356,6 +352,5 @@ extern "C" int sp3d_crop_shift_act_cl(const float *src, float *dst, const float 
     if (blocks > 0x7fffffff) return SP3D_EINVAL;
     hipLaunchKernelGGL(sp3d::crop_shift_act_cl_kernel, dim3((unsigned)blocks), dim3(256), lds, (hipStream_t)stream, src, dst,
                        shift, X, Y, Z, C, SX, SY, SZ, relu);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? SP3D_OK : (int)e;
+    return launch_status();
 }

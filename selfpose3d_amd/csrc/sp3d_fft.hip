@@ -19,6 +19,7 @@
 #include <tuple>
 
 #include "../../include/sp3d.h"
+#include "sp3d_device.h"
 #include "sp3d_twiddles.h"
 
 namespace {
@@ -377,8 +378,7 @@ extern "C" int sp3d_zdft_fwd_cl(const float *x, float *spec, int B, int C, int C
     if (blocks > 0x7fffffff) return SP3D_ERANGE;
     hipLaunchKernelGGL((sp3d::zdft_fwd_cl_kernel<20, 28, 16>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, x,
                        reinterpret_cast<float2 *>(spec), X, Y, SX, SY, Cout);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? SP3D_OK : (int)e;
+    return sp3d::launch_status();
 }
 
 extern "C" int sp3d_zdft_inv_cl(const float *spec, float *y, const float *shift, int B, int O, int X, int Y, int Z, int SX, int SY,
@@ -391,8 +391,7 @@ extern "C" int sp3d_zdft_inv_cl(const float *spec, float *y, const float *shift,
     if (blocks > 0x7fffffff) return SP3D_ERANGE;
     hipLaunchKernelGGL((sp3d::zdft_inv_cl_kernel<20, 28, 16>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream,
                        reinterpret_cast<const float2 *>(spec), y, shift, X, Y, SX, SY, relu);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? SP3D_OK : (int)e;
+    return sp3d::launch_status();
 }
 
 // dynamic LDS of cfft2d_88_kernel (a plane + the twiddle row: 63 KB, above the default limit: raised once per process)
@@ -422,8 +421,7 @@ extern "C" int sp3d_cfft2d_ex(float *data, int batch, int SX, int SY, int invers
     if (const int ra = f88_lds(&lds)) return ra;
     hipLaunchKernelGGL(sp3d::cfft2d_88_kernel, dim3((unsigned)batch), dim3(sp3d::F88_NT), lds, (hipStream_t)stream,
                        reinterpret_cast<float2 *>(data), inverse, rows_in, rows_out, (const float2 *)nullptr, 0);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? SP3D_OK : (int)e;
+    return sp3d::launch_status();
 }
 
 // forward 88 x 88 plane transforms whose input is the 4 x 4-tiled z-spectrum of sp3d_unproject_fwd_zdft:
@@ -439,6 +437,5 @@ extern "C" int sp3d_cfft2d_88_tiled(const float *tiled, float *planes, int batch
     if (const int ra = f88_lds(&lds)) return ra;
     hipLaunchKernelGGL(sp3d::cfft2d_88_kernel, dim3((unsigned)batch), dim3(sp3d::F88_NT), lds, (hipStream_t)stream,
                        reinterpret_cast<float2 *>(planes), 0, X, sp3d::F88, reinterpret_cast<const float2 *>(tiled), Y / 4);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? SP3D_OK : (int)e;
+    return sp3d::launch_status();
 }

@@ -14,6 +14,7 @@
 #include <stdint.h>
 
 #include "../../include/sp3d.h"
+#include "sp3d_device.h"
 
 namespace sp3d {
 
@@ -181,8 +182,7 @@ extern "C" int sp3d_freq_contract_ty(const float *X, const float *T, const float
     const dim3 grid((unsigned)(((nrb + 7) / 8) * 8 * nog), 1, (unsigned)((B + 3) / 4));
     hipLaunchKernelGGL((freq_contract_ty_kernel<4, SP3D_FT_OG>), grid, dim3(FT_NT), 0, (hipStream_t)stream, reinterpret_cast<const float2 *>(X), T,
                        tw, reinterpret_cast<float2 *>(Y), B, C, O, rows, SY);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? SP3D_OK : (int)e;
+    return launch_status();
 }
 
 extern "C" int sp3d_freq_contract_ex(const float *P, const float *Q, float *Y, int I, int J, int K, int64_t F,
@@ -197,8 +197,7 @@ extern "C" int sp3d_freq_contract_ex(const float *P, const float *Q, float *Y, i
     hipStream_t s = (hipStream_t)stream;
     if (conj_p) { if (conj_q) launch_contract<true, true>(p, q, y, I, J, K, F, sPi, sPk, sQj, sQk, s); else launch_contract<true, false>(p, q, y, I, J, K, F, sPi, sPk, sQj, sQk, s); }
     else { if (conj_q) launch_contract<false, true>(p, q, y, I, J, K, F, sPi, sPk, sQj, sQk, s); else launch_contract<false, false>(p, q, y, I, J, K, F, sPi, sPk, sQj, sQk, s); }
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? SP3D_OK : (int)e;
+    return launch_status();
 }
 
 extern "C" int sp3d_freq_contract(const float *X, const float *W, float *Y, int B, int C, int O, int64_t F, void *stream)

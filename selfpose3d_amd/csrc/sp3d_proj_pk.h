@@ -159,8 +159,9 @@ __device__ __forceinline__ bool project_pk(const float *__restrict__ cm, const G
     return true;
 }
 
-// Tap record of one voxel in one view: the 2x2 block's origin pixel and the four slot weights (see make_record in
-// sp3d_unproject.hip for the clamping rule of blocks that touch the zero padding).
+// Tap record of one voxel in one view: the 2x2 block's origin pixel and the four slot weights (make_record in
+// sp3d_unproject_pipe.h is its scalar form; the head of sp3d_unproject_pipe.hip has the clamping rule of blocks that touch
+// the zero padding).
 struct RecPk {
     int x0, y0;         // origin of the (clamped) 2x2 block
     v2f wt, wb;         // (w00, w10) top row, (w01, w11) bottom row

@@ -9,6 +9,7 @@
 #include <stdint.h>
 
 #include "../../include/sp3d.h"
+#include "sp3d_device.h"
 
 namespace sp3d {
 
@@ -449,8 +450,7 @@ extern "C" int sp3d_soft_argmax(const float *x, const float *grids, float *out, 
     GridSpec gs = {};
     hipLaunchKernelGGL(soft_argmax_kernel<false>, dim3(J, Bv), dim3(SA_THREADS), 0, (hipStream_t)stream, x, grids,
                        (const float *)nullptr, gs, out, J, N, beta);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? SP3D_OK : (int)e;
+    return launch_status();
 }
 
 static GridSpec make_grid_spec(const float *grid_size, int X, int Y, int Z)
@@ -478,8 +478,7 @@ extern "C" int sp3d_soft_argmax_grid_train(const float *x, const float *centers,
     const GridSpec gs = make_grid_spec(grid_size, X, Y, Z);
     hipLaunchKernelGGL(soft_argmax_kernel<true>, dim3(J, Bv), dim3(SA_THREADS), 0, (hipStream_t)stream, x,
                        (const float *)nullptr, centers, gs, out, J, N, beta, stats);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? SP3D_OK : (int)e;
+    return launch_status();
 }
 
 extern "C" int sp3d_soft_argmax_grid(const float *x, const float *centers, const float *grid_size, int X, int Y, int Z,
@@ -501,6 +500,5 @@ extern "C" int sp3d_soft_argmax_grid_bwd(const float *x, const float *centers, c
     if (nb > 256) nb = 256;
     hipLaunchKernelGGL(soft_argmax_grid_bwd_kernel, dim3((unsigned)nb, (unsigned)J, (unsigned)Bv), dim3(256), 0,
                        (hipStream_t)stream, x, centers, gs, out, stats, grad_out, grad_x, J, N, beta);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? SP3D_OK : (int)e;
+    return launch_status();
 }

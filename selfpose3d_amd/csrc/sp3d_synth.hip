@@ -7,6 +7,7 @@
 #include <stdint.h>
 
 #include "../../include/sp3d.h"
+#include "sp3d_device.h"
 
 namespace sp3d {
 
@@ -87,8 +88,7 @@ extern "C" int sp3d_gaussian_target_3d(const float *roots, int B, int R, const f
     if (N > 0x7ffffffe) return SP3D_ERANGE;
     hipLaunchKernelGGL(gaussian_target_kernel, dim3((unsigned)((N + 255) / 256), B), dim3(256), 0, (hipStream_t)stream, roots,
                        R, gx, gy, gz, X, Y, Z, sigma, target);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? SP3D_OK : (int)e;
+    return launch_status();
 }
 
 extern "C" int sp3d_render_root_heatmaps(const float *roots, int B, int R, const float *cam, int V, int h, int w,
@@ -100,8 +100,7 @@ extern "C" int sp3d_render_root_heatmaps(const float *roots, int B, int R, const
     const int blocks = (h * w + 255) / 256 < 64 ? (h * w + 255) / 256 : 64;
     hipLaunchKernelGGL(render_roots_kernel, dim3(blocks, B, V), dim3(256), 0, (hipStream_t)stream, roots, R, cam, B, V, h, w,
                        stride, out);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? SP3D_OK : (int)e;
+    return launch_status();
 }
 
 // ------------------------------------------------------------------------------------------
@@ -209,8 +208,7 @@ extern "C" int sp3d_render_joints_fwd(const float *kps, const int *count, int N,
     const int blocks = (h * w + 255) / 256 < 32 ? (h * w + 255) / 256 : 32;
     hipLaunchKernelGGL(sp3d::render_joints_fwd_kernel, dim3(blocks, J, N), dim3(256), 0, (hipStream_t)stream, kps, count, P, J, h,
                        w, sigma, out);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? SP3D_OK : (int)e;
+    return launch_status();
 }
 
 extern "C" int sp3d_render_joints_bwd(const float *kps, const int *count, const float *grad_out, int N, int P, int J, int h,
@@ -221,6 +219,5 @@ extern "C" int sp3d_render_joints_bwd(const float *kps, const int *count, const 
     if (N > 65535) return SP3D_ERANGE;
     hipLaunchKernelGGL(sp3d::render_joints_bwd_kernel, dim3(J, N), dim3(256), 0, (hipStream_t)stream, kps, count, grad_out, P, J,
                        h, w, sigma, grad_kps);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? SP3D_OK : (int)e;
+    return launch_status();
 }

@@ -7,7 +7,7 @@
 extern "C" {
 #endif
 /* The tuning word `variant` of sp3d_unproject_fwd_variant - this comment is the one place its layout is written down
- * (sp3d_unproject.hip decodes it once, into FwdTuning):
+ * (sp3d_unproject.hip, the host plan, decodes it once, into FwdTuning):
  *   bits 1:0    tile kernel (the first NHWC kernel): voxels in flight per lane - 0: 1, 2: 4, else 2
  *   bit 2       no XCD-aware tile map (tile and pipe kernels)
  *   bit 3       pipe: the per-wave software-pipelined kernel

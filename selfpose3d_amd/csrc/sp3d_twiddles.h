@@ -1,5 +1,5 @@
 // Compile-time DFT twiddle tables, shared by the z-DFT kernels of sp3d_fft.hip and the unprojection kernel that emits the
-// z-spectrum directly (sp3d_unproject.hip, unproject_brick_kernel<..., ZD>): ONE table, so both produce the same bits.
+// z-spectrum directly (sp3d_unproject_brick.hip, unproject_brick_kernel<..., ZD>): ONE table, so both produce the same bits.
 #pragma once
 
 namespace sp3d {

@@ -1,0 +1,289 @@
+// sp3d_unproject_one.hip - the one-channel path (SP3D_HM_ONE_CHANNEL): unproject_one_kernel with its kernel table, and the
+// backward of that channel, unproject_one_bwd_kernel behind sp3d_unproject_one_bwd[_det].  The forward entries are in
+// sp3d_unproject.hip (resolve_one).
+#include <type_traits>
+
+#include "sp3d_unproject_pipe.h"
+
+namespace sp3d {
+
+// ------------------------------------------------------------------------------------------
+// one-channel forward (SP3D_HM_ONE_CHANNEL): ONE channel of a wider heat-map tensor, read where it lies - the root
+// joint's map of the ROOTNET_ROOTHM root nets (cuboid_proposal_net.py:103-108 of the reference, V2VNet(1, 1)).
+//
+// Lane = voxel in every phase (projection, gather, view fusion, store): no LDS, no barrier.  A wave owns 64 consecutive
+// voxels.  hm.p[c] points at the wanted channel's element (sample 0, row 0, pixel 0) of view c; a tap is one
+// global_load_dword at  sample * s_sample + y * s_row + x * s_px  elements from it, so the same kernel reads a channel
+// plane of a planar (B,Jt,h,w) tensor (Jt*h*w, w, 1) and a channel of a channels-last (B,h,w,PS) buffer
+// (h*w*PS, w*PS, PS).  Projection and tap records are project_pk / make_record_pk (zero weights on clamped in-range
+// addresses: a branch-free gather); interpolation and view fusion are pipe_views' / pipe_tile's, operation for
+// operation, so the result has the bits of the packed path's channel.
+//
+// Latency (at B = 1 the root grid is 2 000 waves on 1 024 SIMDs): the views are taken in chunks of CS; a chunk's
+// records stay in registers, all of its tap loads are issued back to back, and the next chunk is projected while
+// they are in flight.  The FMAs run last, in view order.  VT >= V is the number of view slots the kernel is unrolled
+// for (resolve_one: V itself up to 6, then 8, 10, 12, 16), CS = 4 up to 8 views and 8 above.
+//
+// Result: planar with g.J = 1 or 4 channels (dense or strided; channels 1-3 zeros), or channels-last (B,X,Y,Z,4) as
+// one 16-byte store {v, 0, 0, 0} per lane.
+//
+// MASK (sp3d_unproject_one_fwd_train): the lane also writes its voxel's word of g.pass_mask - bit 0 by the predicate of
+// pipe_tile / unproject_brick_kernel on the same fuse_pre value, so the words are the packed training forward's at J = 1
+// (an unseen voxel passes, a NaN-zeroed one does not, a cube that `valid` skips gets zeros).  One 2-byte store per lane,
+// 128 contiguous bytes per wave.  The MASK = false instantiations are the kernels of the inference path, unchanged.
+// ------------------------------------------------------------------------------------------
+template <int VT, int CS, bool OUTCL, bool MASK = false>
+__global__ __launch_bounds__(64) void unproject_one_kernel(Views hm, const float *__restrict__ cam,
+                                                           const float *__restrict__ centers,
+                                                           const uint8_t *__restrict__ valid, float *__restrict__ cubes,
+                                                           float *__restrict__ grids, Geom g, long long s_sample,
+                                                           int s_row, int s_px)
+{
+    constexpr int NCH = (VT + CS - 1) / CS;
+    int b, tile;
+    if (!xcd_map_fast(blockIdx.x, g, b, tile)) return;
+    const int bs = g.sample_of ? g.sample_of[b] : b;
+    const int lane = threadIdx.x;
+    const int n0 = tile * 64;
+    if (n0 >= g.N) return;
+    const int nvox = min(64, g.N - n0);
+    const bool inb = lane < nvox;
+    const int n = n0 + (inb ? lane : 0);
+    int vx, rem, vy, vz;
+    udiv_magic((uint32_t)n, (uint32_t)g.YZ, g.magicYZ, vx, rem);
+    udiv_magic((uint32_t)rem, (uint32_t)g.Z, g.magicZ, vy, vz);
+    // where this lane's voxel goes: channel plane j of a planar result starts j * sJ further
+    float *dst = OUTCL ? cubes + ((size_t)b * g.N + n) * 4
+                       : cubes + (size_t)b * g.sB + (g.dense ? (size_t)n : (size_t)vx * g.sX + (size_t)vy * g.sY + vz);
+    float out = 0.0f;
+    uint16_t word = 0;                              // MASK: this voxel's pass-mask word
+    if (valid[b]) {
+        const float x = linspace_step(g.Lx, g.stepx, g.X, vx) + centers[3 * b + 0];
+        const float y = linspace_step(g.Ly, g.stepy, g.Y, vy) + centers[3 * b + 1];
+        const float z = linspace_step(g.Lz, g.stepz, g.Z, vz) + centers[3 * b + 2];
+        if (grids && inb) {
+            float *gp = grids + ((size_t)b * g.N + n) * 3;
+            gp[0] = x; gp[1] = y; gp[2] = z;
+        }
+        const unsigned long long inbm = __builtin_amdgcn_ballot_w64(inb);
+        uint32_t mymask = 0;                        // views that see MY voxel (+ bit 31: NaN position)
+        uint32_t have = 0;                          // wave-uniform: views with a record (some voxel of the wave sees them)
+        uint32_t off[VT];                           // byte offset of the 2x2 block inside the sample's image
+        float w00[VT], w10[VT], w01[VT], w11[VT];
+        float t00[VT], t10[VT], t01[VT], t11[VT];
+        const size_t pxb = (size_t)s_px * sizeof(float), rowb = (size_t)s_row * sizeof(float);
+#pragma unroll
+        for (int ch = 0; ch < NCH; ++ch) {
+#pragma unroll
+            for (int c = ch * CS; c < (ch + 1) * CS && c < VT; ++c) {
+                off[c] = 0u;
+                w00[c] = w10[c] = w01[c] = w11[c] = 0.0f;
+                if (c < g.V) {
+                    const float *cm = cam + ((size_t)bs * g.V + c) * SP3D_CAM_STRIDE;
+                    P1State st;
+                    const bool go = project_pk(cm, g, x, y, z, inbm, st);
+                    add_mask(mymask, st.bm);
+                    if (st.nm != 0ull && lane_of(st.nm)) mymask |= 0x80000000u;
+                    const unsigned long long um = st.bm & ~st.nm;
+                    if (go && um != 0ull) {         // else: no voxel of this wave sees camera c
+                        const RecPk r = make_record_pk(lane_of(um), st.i, g.w, g.h);
+                        off[c] = (__umul24((unsigned)r.y0, (unsigned)s_row) + __umul24((unsigned)r.x0, (unsigned)s_px)) << 2;
+                        w00[c] = r.wt.x; w10[c] = r.wt.y; w01[c] = r.wb.x; w11[c] = r.wb.y;
+                        have |= 1u << c;
+                    }
+                }
+            }
+            __builtin_amdgcn_sched_barrier(0);
+            // The chunk's taps: four wave-uniform bases (scalar register pairs) + one 32-bit byte offset per lane, no
+            // branch between the loads.  A view without a record (and a slot past V, which reads view 0) loads its
+            // first 2x2 block with zero weights and is left out of the sum below.  Issued in the reverse of the order
+            // the interpolation consumes them (loads return in order).
+#pragma unroll
+            for (int c = min((ch + 1) * CS, VT) - 1; c >= ch * CS; --c) {
+                const char *vb = reinterpret_cast<const char *>((c < g.V ? hm.p[c] : hm.p[0]) + (ptrdiff_t)bs * s_sample);
+                const char *vb2 = vb + rowb;
+                t11[c] = *reinterpret_cast<const float *>(vb2 + pxb + off[c]);
+                t01[c] = *reinterpret_cast<const float *>(vb2 + off[c]);
+                t10[c] = *reinterpret_cast<const float *>(vb + pxb + off[c]);
+                t00[c] = *reinterpret_cast<const float *>(vb + off[c]);
+            }
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        float acc = 0.0f;
+#pragma unroll
+        for (int c = 0; c < VT; ++c) {
+            // ATen's bilinear chain: fma(se, wse, fma(sw, wsw, fma(ne, wne, nw * wnw)))
+            float v = t00[c] * w00[c];
+            v = fmaf(t10[c], w10[c], v);
+            v = fmaf(t01[c], w01[c], v);
+            v = fmaf(t11[c], w11[c], v);
+            const float a = acc + v;
+            acc = ((have >> c) & 1u) ? a : acc;     // wave-uniform, as the pipelined kernels skip such a view
+        }
+        // view fusion (project_layer.py:96-99): den = #views seeing the voxel + 1e-6; NaN sample position -> 0
+        const float den = (float)(mymask & 0x7fffffffu) + 1e-6f;
+        const float rden = (mymask & 0x80000000u) ? 0.0f : 1.0f / den;
+        out = fuse_rcp(acc, den, rden);
+        if constexpr (MASK) {
+            // gradient pass mask (torch.clamp backward: 0 <= pre <= 1; a NaN-zeroed voxel, rden == 0, blocks it)
+            const float pre = fuse_pre(acc, den, rden);
+            word = (rden != 0.0f && pre >= 0.0f && pre <= 1.0f) ? 1 : 0;
+        }
+    } else if (grids && inb) {                      // skipped sample: zeros (project_layer.py:48,51,54)
+        float *gp = grids + ((size_t)b * g.N + n) * 3;
+        gp[0] = 0.0f; gp[1] = 0.0f; gp[2] = 0.0f;
+    }
+    if (!inb) return;
+    if constexpr (MASK) g.pass_mask[(size_t)b * g.N + n] = word;
+    if (OUTCL) {
+        Store4<float>::store_nt(dst, make_float4(out, 0.0f, 0.0f, 0.0f));
+    } else {
+        dst[0] = out;
+        for (int j = 1; j < g.J; ++j) dst[(size_t)j * g.sJ] = 0.0f;
+    }
+}
+
+// ------------------------------------------------------------------------------------------
+// one-channel backward (sp3d_unproject_one_bwd[_det]): the scatter of bwd2 for ONE gradient channel, into dense (V,B,h,w)
+// planes instead of channel 0 of 16-byte pixels.  bwd2<4> runs this case on 16 of its 64 lanes and three of every four
+// atomics it issues add the zero gradient of a pad channel; here lane = voxel throughout and every atomic carries a value.
+//   pass 1   lane = voxel: sample_pos_fast per view -> view bits (+ bit 31: NaN position), den = popc + 1e-6
+//            g = (bit 0 of the pass-mask word && !dead) ? grad / den : 0; a wave without any g != 0 ends here
+//   pass 2   per view (wave-uniform loop, camera record in scalar registers): sample_pos_fast + make_record again - the
+//            calls of bwd2's phase P1, so offset and weights are bwd2's - then up to four atomics g * w on the lanes that see
+//            the view, each predicated on its weight.  Same fp32 products (grad / den) * w as bwd2: with DET the integers
+//            added are the same, so the result equals channel 0 of sp3d_unproject_bwd_packed_det bit for bit.
+// No LDS, no barrier: the record of a view lives in registers while its taps are issued.  grad_cubes: channel 0 of cube p is
+// N contiguous floats at p * grad_stride (N for a (P,1,..) gradient, 4N for a planar (P,4,..) one).
+// ------------------------------------------------------------------------------------------
+template <bool DET>
+__global__ __launch_bounds__(64) void unproject_one_bwd_kernel(const float *__restrict__ cam,
+                                                              const float *__restrict__ centers,
+                                                              const uint8_t *__restrict__ valid,
+                                                              const float *__restrict__ grad_cubes, long long grad_stride,
+                                                              const uint16_t *__restrict__ pass_mask,
+                                                              void *__restrict__ grad_hm_, size_t view_stride, Geom g,
+                                                              int tiles_per_sample, const float *__restrict__ scale_p)
+{
+    using ACC = typename std::conditional<DET, unsigned long long, float>::type;
+    ACC *grad_hm = reinterpret_cast<ACC *>(grad_hm_);
+    const double scale = DET ? (double)*scale_p : 1.0;
+    auto add = [&](ACC *p, float val) {
+        if constexpr (DET) atomicAdd(p, (unsigned long long)__double2ll_rn((double)val * scale));
+        else unsafeAtomicAdd(p, val);
+    };
+    int b, tile;
+    if (!xcd_map(blockIdx.x, g.B, tiles_per_sample, g.xcd_chunk, b, tile)) return;
+    const int n0 = tile * 64;
+    if (n0 >= g.N || !valid[b]) return;
+    const int bs = g.sample_of ? g.sample_of[b] : b;
+    const int lane = threadIdx.x;
+    const int nvox = min(64, g.N - n0);
+    const bool inb = lane < nvox;
+    const int n = n0 + (inb ? lane : 0);
+    int vx, rem, vy, vz;
+    udiv_magic((uint32_t)n, (uint32_t)g.YZ, g.magicYZ, vx, rem);
+    udiv_magic((uint32_t)rem, (uint32_t)g.Z, g.magicZ, vy, vz);
+    const float x = linspace_step(g.Lx, g.stepx, g.X, vx) + centers[3 * b + 0];
+    const float y = linspace_step(g.Ly, g.stepy, g.Y, vy) + centers[3 * b + 1];
+    const float z = linspace_step(g.Lz, g.stepz, g.Z, vz) + centers[3 * b + 2];
+    // the two loads of a voxel in flight while the views are projected (n is a valid voxel for every lane)
+    const uint32_t pm = (uint32_t)pass_mask[(size_t)b * g.N + n];
+    const float gl = grad_cubes[(size_t)b * (size_t)grad_stride + n];
+    uint32_t mymask = 0;
+    for (int c = 0; c < g.V; ++c) {
+        const float *cm = cam + ((size_t)bs * g.V + c) * SP3D_CAM_STRIDE;
+        float ix, iy;
+        bool isnan;
+        const bool bound = sample_pos_fast(cm, x, y, z, g, ix, iy, isnan) && inb;
+        if (bound) mymask |= (1u << c);
+        if (isnan && inb) mymask |= 0x80000000u;
+    }
+    // g = pass ? grad / den : 0     (autograd of project_layer.py:96-99)
+    const float den = (float)__popc(mymask & 0x7fffffffu) + 1e-6f;
+    const bool dead = (mymask & 0x80000000u) != 0 || (mymask & 0x7fffffffu) == 0;
+    float gv = 0.0f;
+    if (inb && !dead && (pm & 1u)) gv = gl / den;
+    const uint32_t views = gv != 0.0f ? (mymask & 0x7fffffffu) : 0u;      // voxels without gradient scatter nothing
+    if (__builtin_amdgcn_ballot_w64(views != 0u) == 0ull) return;
+    ACC *gbase = grad_hm + (size_t)bs * g.h * g.w;
+#pragma unroll 1
+    for (int c = 0; c < g.V; ++c) {
+        const float *cm = cam + ((size_t)bs * g.V + c) * SP3D_CAM_STRIDE;
+        float ix, iy;
+        bool isnan;
+        const bool bound = sample_pos_fast(cm, x, y, z, g, ix, iy, isnan) && inb;
+        const Rec r = make_record<1>(bound && !isnan, isnan ? 0.0f : ix, isnan ? 0.0f : iy, g.w, g.h);
+        if ((views >> c) & 1u) {
+            ACC *p = gbase + (size_t)c * view_stride + r.off;
+            if (r.w00 != 0.0f) add(p, gv * r.w00);
+            if (r.w10 != 0.0f) add(p + 1, gv * r.w10);
+            if (r.w01 != 0.0f) add(p + g.w, gv * r.w01);
+            if (r.w11 != 0.0f) add(p + g.w + 1, gv * r.w11);
+        }
+    }
+}
+
+// one-channel kernel: VT view slots gathered in chunks of CS
+#define SP3D_ONE(VT_, CS_) SP3D_ROW(OneFn, (KernelKey{1, 1, VT_, CS_, false, 0}), unproject_one_kernel, VT_, CS_, false) \
+    SP3D_ROW(OneFn, (KernelKey{1, 1, VT_, CS_, true, 0}), unproject_one_kernel, VT_, CS_, true) \
+    SP3D_ROW(OneFn, (KernelKey{1, 1, VT_, CS_, false, 4}), unproject_one_kernel, VT_, CS_, false, true) \
+    SP3D_ROW(OneFn, (KernelKey{1, 1, VT_, CS_, true, 4}), unproject_one_kernel, VT_, CS_, true, true)
+int find_one_kernel(const KernelKey &key, const void *&fn, const char *&name)
+{
+    SP3D_ONE(1, 4) SP3D_ONE(2, 4) SP3D_ONE(3, 4) SP3D_ONE(4, 4) SP3D_ONE(5, 4) SP3D_ONE(6, 4) SP3D_ONE(8, 4) SP3D_ONE(10, 8)
+    SP3D_ONE(12, 8) SP3D_ONE(16, 8)
+    return SP3D_EUNSUPPORTED;
+}
+
+} // namespace sp3d
+
+using namespace sp3d;
+
+// scale == nullptr: fp32 atomics into (V,B,h,w) float; else 64-bit fixed point into (V,B,h,w) int64
+static int one_bwd_impl(const float *cam, const int32_t *sample_of, const float *centers, const uint8_t *valid,
+                        const float *grad_cubes, int64_t grad_cube_stride, const uint16_t *pass_mask, void *grad_acc,
+                        const float *scale, int B, int P, int V, int h, int w, int X, int Y, int Z, const float *grid_size,
+                        int W_in, int H_in, void *stream)
+{
+    Geom g;
+    const int rc = make_geom(g, P, V, 1, h, w, X, Y, Z, grid_size, W_in, H_in);
+    if (rc) return rc;
+    if (B <= 0 || grad_cube_stride < (int64_t)g.N) return SP3D_EINVAL;
+    if (!cam || !centers || !valid || !grad_cubes || !pass_mask || !grad_acc) return SP3D_ENULL;
+    // a clamped 2x2 tap block needs a 2x2 image; its offset inside a plane is a 32-bit int of at most 2^24 pixels
+    if (w < 2 || h < 2 || (int64_t)h * w > (1 << 24)) return SP3D_EUNSUPPORTED;
+    g.sample_of = sample_of;
+    const int tiles = (g.N + 63) / 64;
+    const size_t view_stride = (size_t)B * h * w;
+    const long long gstride = (long long)grad_cube_stride;
+    dim3 grid(xcd_grid_blocks(P, tiles, g.xcd_chunk)), block(64);
+    hipStream_t s = (hipStream_t)stream;
+    if (scale)
+        hipLaunchKernelGGL(unproject_one_bwd_kernel<true>, grid, block, 0, s, cam, centers, valid, grad_cubes, gstride, pass_mask,
+                           grad_acc, view_stride, g, tiles, scale);
+    else
+        hipLaunchKernelGGL(unproject_one_bwd_kernel<false>, grid, block, 0, s, cam, centers, valid, grad_cubes, gstride, pass_mask,
+                           grad_acc, view_stride, g, tiles, scale);
+    return launch_status();
+}
+
+extern "C" int sp3d_unproject_one_bwd(const float *cam, const int32_t *sample_of, const float *centers, const uint8_t *valid,
+                                      const float *grad_cubes, int64_t grad_cube_stride, const uint16_t *pass_mask,
+                                      float *grad_hm, int B, int P, int V, int h, int w, int X, int Y, int Z,
+                                      const float *grid_size, int W_in, int H_in, void *stream)
+{
+    return one_bwd_impl(cam, sample_of, centers, valid, grad_cubes, grad_cube_stride, pass_mask, grad_hm, nullptr, B, P, V, h,
+                        w, X, Y, Z, grid_size, W_in, H_in, stream);
+}
+
+extern "C" int sp3d_unproject_one_bwd_det(const float *cam, const int32_t *sample_of, const float *centers,
+                                          const uint8_t *valid, const float *grad_cubes, int64_t grad_cube_stride,
+                                          const uint16_t *pass_mask, int64_t *grad_fixed, const float *scale, int B, int P,
+                                          int V, int h, int w, int X, int Y, int Z, const float *grid_size, int W_in, int H_in,
+                                          void *stream)
+{
+    if (!scale) return SP3D_ENULL;
+    return one_bwd_impl(cam, sample_of, centers, valid, grad_cubes, grad_cube_stride, pass_mask, grad_fixed, scale, B, P, V, h,
+                        w, X, Y, Z, grid_size, W_in, H_in, stream);
+}

@@ -23,6 +23,7 @@
 #include <stdint.h>
 
 #include "../../include/sp3d.h"
+#include "sp3d_device.h"
 #include "sp3d_split.h"
 
 namespace sp3d {
@@ -237,6 +238,5 @@ extern "C" int sp3d_upconv2x_fused(const float *x, const void *w_split, const fl
         const auto kern = ny < 8 ? upconv2x_fused_kernel<128, 64, false, true> : upconv2x_fused_kernel<128, 64, false, false>;
         hipLaunchKernelGGL(kern, grid, block, lds, s, x, w, shift, skip, w_out, b_out, out, (int)n_in, X, Y, Z, 0, ny, 8 / ny);
     }
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? SP3D_OK : (int)e;
+    return sp3d::launch_status();
 }

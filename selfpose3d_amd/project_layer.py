@@ -129,7 +129,7 @@ def one_channel_source(hms: Sequence[torch.Tensor]):
         else:
             if B > 1 and sB != h * w * sW:
                 return None
-            # the limits resolve_one (csrc/sp3d_unproject.hip) answers SP3D_EUNSUPPORTED for - 32-bit byte offsets, 24-bit
+            # the limits resolve_one (csrc/sp3d_unproject.hip, the host plan) answers SP3D_EUNSUPPORTED for - 32-bit byte offsets, 24-bit
             # multiplies - so that such a buffer keeps the packed path instead of raising
             if h * w * sW * 4 > 0x7fffffff or w * sW >= (1 << 24):
                 return None

@@ -55,7 +55,7 @@ def plan_of(r):
 
 def static_lds(name):
     """LDS a kernel declares itself, which a trace adds to the launch's dynamic bytes: only the pipe kernel has any -
-    NW * max(JP * WOSTR, WREC) floats (sp3d_unproject.hip: WOSTR = 68, WREC = 640)"""
+    NW * max(JP * WOSTR, WREC) floats (sp3d_unproject_host.h: WOSTR = 68, WREC = 640)"""
     m = re.match(r"unproject_pipe_kernel<(\d+), (?:true|false), (\d+),", name)
     return int(m.group(2)) * max(int(m.group(1)) * 68, 640) * 4 if m else 0
 

@@ -243,6 +243,66 @@ def test_conv3_entries_refuse_in_the_documented_order(lib):
     assert wo(d, d, d, None, 2, 1 << 20, 1024, 1024, 1024, 32, None) == ENULL
 
 
+def test_unprojection_backward_entries_refuse_in_the_documented_order(lib):
+    """the C entries of the unprojection backward (csrc/sp3d_unproject_bwd.hip, sp3d_unproject_one.hip): the geometry
+    (SP3D_EINVAL; its own SP3D_ENULL for grid_size and SP3D_ERANGE follow it), then B <= 0 (SP3D_EINVAL), then the packed
+    entries' `scatter` (SP3D_EINVAL), then the pointers (SP3D_ENULL), then what the kernels are not built for
+    (SP3D_EUNSUPPORTED); the deterministic entries answer SP3D_ENULL for scale == NULL before anything else.  All of it
+    before the first HIP call: EVERY call below breaks at least one rule and the dummy pointers are never dereferenced."""
+    hdr = open(os.path.join(ROOT, "include", "sp3d.h")).read()
+    EINVAL, ENULL, ERANGE, EUNSUPPORTED = (int(re.search(name + r"\s*=\s*(-?\d+)", hdr).group(1))
+                                           for name in ("SP3D_EINVAL", "SP3D_ENULL", "SP3D_ERANGE", "SP3D_EUNSUPPORTED"))
+    assert len({0, EINVAL, ENULL, ERANGE, EUNSUPPORTED}) == 5
+    gs = (C.c_float * 3)(2000, 2000, 2000)
+    d = C.c_void_p(0x1000)
+    huge = dict(X=2048, Y=2048, Z=2048)
+
+    def packed(det):     # (cam, sample_of, centers, valid, grad_cubes, pass_mask, grad, [scale,] B, P, V, J, Jp, h, w, X, Y, Z, ...)
+        f = lib.sp3d_unproject_bwd_packed_det if det else lib.sp3d_unproject_bwd_packed
+
+        def call(cam=d, scale=d, B=1, V=2, Jp=16, w=8, X=4, Y=4, Z=4, grid=gs, scatter=_lib.SCATTER_AUTO):
+            return f(cam, None, d, d, d, d, d, *((scale,) if det else ()), B, 1, V, 15, Jp, 8, w, X, Y, Z, grid, 96, 72, scatter, None)
+        return call
+
+    def one(det):        # (cam, sample_of, centers, valid, grad_cubes, grad_cube_stride, pass_mask, grad, [scale,] B, P, V, h, w, ...)
+        f = lib.sp3d_unproject_one_bwd_det if det else lib.sp3d_unproject_one_bwd
+
+        def call(cam=d, scale=d, B=1, V=2, w=8, X=4, Y=4, Z=4, grid=gs, stride=64):
+            return f(cam, None, d, d, d, stride, d, d, *((scale,) if det else ()), B, 1, V, 8, w, X, Y, Z, grid, 96, 72, None)
+        return call
+
+    for f in (packed(False), packed(True), one(False), one(True)):
+        assert f(V=0) == EINVAL and f(V=17) == EINVAL and f(X=0) == EINVAL       # the geometry
+        assert f(B=0) == EINVAL
+        assert f(cam=None) == ENULL
+        assert f(w=1) == EUNSUPPORTED
+        # the order: the earlier rule answers for a call that breaks several
+        assert f(V=0, grid=None, **{k: v for k, v in huge.items() if k != "X"}) == EINVAL
+        assert f(grid=None, B=0, cam=None, w=1, **huge) == ENULL               # the geometry's own: grid_size, then the range
+        assert f(B=0, cam=None, w=1, **huge) == ERANGE
+        assert f(V=17, B=0, cam=None, w=1) == EINVAL
+        assert f(B=0, cam=None, w=1) == EINVAL
+        assert f(cam=None, w=1) == ENULL
+    for f in (packed(False), packed(True)):
+        assert f(scatter=1) == EINVAL and f(scatter=4) == EINVAL and f(scatter=-1) == EINVAL
+        assert f(scatter=1, cam=None, Jp=12) == EINVAL                          # scatter before the pointers ...
+        assert f(X=0, scatter=1) == EINVAL and f(scatter=1, **huge) == ERANGE    # ... and after the geometry
+        assert f(Jp=12) == EUNSUPPORTED and f(Jp=18) == EUNSUPPORTED and f(Jp=20) == EUNSUPPORTED      # Jp < J, Jp % 4, Jp > 16
+        assert f(cam=None, Jp=12) == ENULL
+    for f in (one(False), one(True)):
+        assert f(stride=63) == EINVAL and f(stride=63, cam=None, w=1) == EINVAL     # a gradient cube shorter than the grid
+        assert f(X=0, stride=0) == EINVAL
+    for f in (packed(True), one(True)):                                             # scale == NULL: before anything else
+        assert f(scale=None) == ENULL
+        assert f(scale=None, V=0) == ENULL and f(scale=None, B=0) == ENULL and f(scale=None, w=1, **huge) == ENULL
+    assert packed(True)(scale=None, scatter=1) == ENULL
+    # sp3d_fixed_to_float(acc, out, scale, n, stream): n, then the pointers, then the grid range
+    ff = lib.sp3d_fixed_to_float
+    assert ff(d, d, d, 0, None) == EINVAL and ff(d, d, d, -5, None) == EINVAL and ff(None, None, None, 0, None) == EINVAL
+    assert ff(None, d, d, 10, None) == ENULL and ff(d, None, d, 10, None) == ENULL and ff(d, d, None, 10, None) == ENULL
+    assert ff(d, d, d, 1 << 40, None) == ERANGE and ff(d, None, d, 1 << 40, None) == ENULL
+
+
 def test_missing_library_fails_loudly(monkeypatch, tmp_path):
     monkeypatch.setattr(_lib, "_lib", None)
     monkeypatch.setattr(_lib, "LIB_PATH", str(tmp_path / "nope.so"))

@@ -1,6 +1,6 @@
 """The brick unprojection's workgroup -> (sample, brick stack) maps, emulated on the host: every (sample, tile) exactly once.
 
-The brick kernels (selfpose3d_amd/csrc/sp3d_unproject.hip, resolve_group) decode blockIdx.x through xcd_map_fast() with
+The brick kernels (selfpose3d_amd/csrc/sp3d_unproject_brick.hip; launched by resolve_group, sp3d_unproject.hip) decode blockIdx.x through xcd_map_fast() with
 fields the host fills in set_xcd_fields(), set_block_fields() and set_brick_fields() (selfpose3d_amd/csrc/sp3d_device.h:396-504);
 udiv_magic() is sp3d_device.h:80-86.  Since round 6 the default for B in {1, 2, 4} is the block map: octants of the (x, y)
 plane of brick columns at B = 1 on a square grid with an even side >= 4 (xm_mode 4, with a float square root and two
@@ -168,7 +168,7 @@ def check_bijection(B, nbx, nby, nzc, chunks=False):
     key = b[ok] * wgs + tile[ok]
     hits = np.bincount(key, minlength=B * wgs)
     assert hits.size == B * wgs and (hits == 1).all(), (where, int((hits == 0).sum()), int((hits > 1).sum()))
-    # the brick kernels' decode of the tile (sp3d_unproject.hip: udiv_magic by bk_nxy, then by bk_nby) lands in the grid
+    # the brick kernels' decode of the tile (sp3d_unproject_brick.hip: udiv_magic by bk_nxy, then by bk_nby) lands in the grid
     zc, t = udiv_magic(tile[ok], g["bk_nxy"], g["bk_magic_nxy"])
     bx, by = udiv_magic(t, g["bk_nby"], g["bk_magic_nby"])
     assert ((zc < nzc) & (bx < nbx) & (by < nby)).all(), where

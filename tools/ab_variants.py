@@ -74,7 +74,7 @@ def main():
         fns = {"planar": lambda: _lib.unproject_fwd(hms, _lib.LAYOUT_PLANAR, 0, cam, centers, valid, B, J, h, w, cube,
                                                     gs, img, False),
                "pack": lambda: _lib.pack_heatmaps(hms, jp=16, out=packed)}
-        # library defaults (selfpose3d_amd/csrc/sp3d_unproject.hip: default_tuning)
+        # library defaults (selfpose3d_amd/csrc/sp3d_unproject.hip, the host plan: default_tuning)
         fns["nhwc_default"] = lambda: _lib.unproject_fwd(views, _lib.LAYOUT_NHWC, 16, cam, centers, valid, B, J, h, w, cube,
                                                          gs, img, False)
         fns["nhwc_default_cl"] = lambda: _lib.unproject_fwd(views, _lib.LAYOUT_NHWC, 16, cam, centers, valid, B, 16, h, w,
