@@ -104,7 +104,17 @@ enum {
      * are sp3d_unproject_one_fwd_train / sp3d_unproject_one_bwd[_det] below), for heat-maps narrower or lower
      * than 2 pixels or of more than 2^24 pixels, and for a sample of more than 2^31 bytes; SP3D_EINVAL for Jp < 1 and for a
      * layout byte that is neither SP3D_LAYOUT_PLANAR nor SP3D_LAYOUT_NHWC. */
-    SP3D_HM_ONE_CHANNEL = 0x800
+    SP3D_HM_ONE_CHANNEL = 0x800,
+    /* OR-ed into hm_layout of sp3d_unproject_fwd_train ONLY: the training forward at Jp = 32 (17..32 joints), whose pass mask
+     * then has TWO planes, pass_mask (2, P, X*Y*Z) uint16 - plane 0: channels 0-15, plane 1: channels 16..J-1, bit (j mod 16)
+     * under the rule stated at sp3d_unproject_fwd_train.  Bits at or above J - 16 of plane 1 are zero, both planes of a cube
+     * that `valid` skips are zero, and for J <= 16 plane 1 is written as zeros.  Takes SP3D_LAYOUT_NHWC, Jp == 32,
+     * 1 <= J <= 32, fp32 maps, a planar result, with or without sample_of and grids; the cubes are those of the inference
+     * forward at Jp = 32 (two launches, one per channel group, each writing its plane).  SP3D_EUNSUPPORTED, before any
+     * launch, for Jp != 32, for SP3D_OUT_CHANNELS_LAST, for either bf16 flag, for SP3D_HM_ONE_CHANNEL, for heat-maps below
+     * 2x2 or above 2^24 pixels, and for the flag on any other forward entry (_fwd, _fwd_indexed, _fwd_strided,
+     * sp3d_unproject_one_fwd_train).  Read back by sp3d_unproject_bwd_packed[_det] with SP3D_SCATTER_WIDE. */
+    SP3D_HM_WIDE_MASK = 0x1000
 };
 
 int sp3d_abi_version(void);
@@ -131,9 +141,12 @@ int sp3d_pack_heatmaps_ex(const void *const *hm_views, void *packed, int in_bf16
  * configurations).  A 32-float pixel is one 128-byte line, gathered as two channel groups (channels 0-15, 16..J-1) by
  * one launch each of the 16-channel kernels; each group is bit-identical to the oracle.  At Jp = 32 the NHWC forward
  * entries (_fwd, _fwd_indexed, _fwd_strided) take fp32 or bf16 maps and cubes, with or without sample_of and grids, for
- * heat-maps of at least 2x2 pixels; SP3D_EUNSUPPORTED for a channels-last result, for sp3d_unproject_fwd_train (the pass
- * mask holds 16 bits per voxel), for sp3d_unproject_fwd_zdft and for both sp3d_unproject_bwd_packed entries.  Any other
- * Jp, or J > Jp: SP3D_EUNSUPPORTED, before any launch.
+ * heat-maps of at least 2x2 pixels; SP3D_EUNSUPPORTED for a channels-last result and for sp3d_unproject_fwd_zdft.  The
+ * training pair takes Jp = 32 by request only: the pass mask of sp3d_unproject_fwd_train holds 16 bits per voxel, so that
+ * entry and both sp3d_unproject_bwd_packed entries answer SP3D_EUNSUPPORTED at Jp = 32 as they are called for Jp <= 16;
+ * with SP3D_HM_WIDE_MASK the forward writes one 16-bit mask plane per channel group, and with SP3D_SCATTER_WIDE the two
+ * scatters read them back and accumulate into 32-element pixels (both below).  Any other Jp, or J > Jp:
+ * SP3D_EUNSUPPORTED, before any launch.
  */
 
 /*
@@ -212,11 +225,21 @@ int sp3d_unproject_fwd_train(const float *const *hm_views, int hm_layout, int Jp
  * 2x2 tap and 64-byte pixel), and block merge (an 8x8x4 block of voxels first adds its taps in an LDS patch, 64-bit fixed
  * point, and every touched pixel leaves once - 3x faster where voxels lie closer than ~2 pixels, the 64^3 person cubes).
  * `scatter` picks per CALL (the library keeps no selector state); any other value: SP3D_EINVAL.
+ *
+ * SP3D_SCATTER_WIDE, OR-ed into `scatter` of both entries: 17..32 joints at a pixel of 32 elements.  The low byte keeps its
+ * meaning (AUTO, PER_TAP or MERGE; anything else, or any bit above 0x100: SP3D_EINVAL).  With the flag Jp must be 32 and
+ * 1 <= J <= 32; pass_mask is the two-plane mask of SP3D_HM_WIDE_MASK; grad_cubes is (P,J,X,Y,Z); grad_packed / grad_fixed
+ * is (V,B,h,w,32), zero-filled by the caller; channels J..31 are left untouched (they stay zero).  The call is two
+ * launches of the same scatter kernel, one per channel group (AUTO decides once for both), sequential in `stream`.
+ * SP3D_EUNSUPPORTED for the flag with Jp != 32, and for w or h below 2.  The refusals come in the order of the plain call:
+ * geometry, B, scatter, pointers (SP3D_ENULL; scale == NULL of the _det entry first of all), then unsupported.  Without
+ * the flag Jp = 32 keeps answering SP3D_EUNSUPPORTED.
  */
 enum {
     SP3D_SCATTER_AUTO = 0,    /* by voxel pitch: <= 50 mm on every axis -> merge, else per tap */
     SP3D_SCATTER_PER_TAP = 2,
-    SP3D_SCATTER_MERGE = 3
+    SP3D_SCATTER_MERGE = 3,
+    SP3D_SCATTER_WIDE = 0x100 /* flag bit, see above */
 };
 int sp3d_unproject_bwd_packed(const float *cam, const int32_t *sample_of, const float *centers, const uint8_t *valid,
                               const float *grad_cubes, const uint16_t *pass_mask, float *grad_packed, int B, int P,

@@ -24,7 +24,9 @@ OUT_CHANNELS_LAST = 0x100
 HM_BF16 = 0x200
 OUT_BF16 = 0x400
 HM_ONE_CHANNEL = 0x800      # one channel of a wider tensor, read in place (include/sp3d.h)
+HM_WIDE_MASK = 0x1000       # sp3d_unproject_fwd_train at Jp = 32: a (2, P, N) pass mask, one plane per channel group
 SCATTER_AUTO, SCATTER_PER_TAP, SCATTER_MERGE = 0, 2, 3      # include/sp3d.h: per-call scatter choice of unproject_bwd_packed
+SCATTER_WIDE = 0x100        # OR-ed into that choice: 17..32 joints, 32-element pixels, the two-plane mask
 MAX_VIEWS = 16
 MAX_TOPK = 32
 ABI_VERSION = 3
@@ -246,7 +248,8 @@ def unproject_fwd(views: Sequence[torch.Tensor], layout: int, jp: int, cam: torc
                   valid: torch.Tensor, B: int, J: int, h: int, w: int, cube_size, grid_size, img_size,
                   want_grids: bool = True, variant: Optional[int] = None, channels_last: bool = False,
                   sample_of: Optional[torch.Tensor] = None, out_dtype: torch.dtype = torch.float32,
-                  pass_mask: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None, one_channel: bool = False):
+                  pass_mask: Optional[torch.Tensor] = None, wide_mask: bool = False, out: Optional[torch.Tensor] = None,
+                  one_channel: bool = False):
     """-> (cubes (B,J,X,Y,Z), grids (B,N,3) | None).  With ``channels_last`` the cubes tensor has
     torch.channels_last_3d strides (memory (B,X,Y,Z,J), J % 4 == 0, NHWC input only).
     ``sample_of`` (int32, (B,)): output cube p reads heat-map/camera row sample_of[p] (B = #cubes).
@@ -255,7 +258,9 @@ def unproject_fwd(views: Sequence[torch.Tensor], layout: int, jp: int, cam: torc
     ``one_channel`` (SP3D_HM_ONE_CHANNEL): ``views[c]`` is any fp32 tensor whose ``data_ptr()`` is the wanted channel's first
     element of view c - a (B,1,h,w) slice of a planar (B,jp,h,w) tensor (``LAYOUT_PLANAR``, ``jp`` = its channel count) or
     of a channels-last (B,h,w,jp) buffer (``LAYOUT_NHWC``, ``jp`` = its pixel stride) - read in place; ``J`` = channels
-    written, 1 or 4 (value + three zero channels; channels-last results: 4)."""
+    written, 1 or 4 (value + three zero channels; channels-last results: 4).
+    ``wide_mask`` (SP3D_HM_WIDE_MASK, with ``pass_mask`` at ``jp`` = 32 only): ``pass_mask`` is a contiguous (2, B, X*Y*Z)
+    int16 tensor, plane 0 for channels 0-15 and plane 1 for channels 16..J-1."""
     lib = load()
     dev = cam.device
     _require_cam(cam)
@@ -283,6 +288,11 @@ def unproject_fwd(views: Sequence[torch.Tensor], layout: int, jp: int, cam: torc
         (OUT_BF16 if out_dtype == torch.bfloat16 else 0) | one
     grids = torch.empty((B, X * Y * Z, 3), dtype=torch.float32, device=dev) if want_grids else None
     gs = _f3(grid_size)
+    if wide_mask:
+        if pass_mask is None or pass_mask.dtype != torch.int16 or not pass_mask.is_contiguous() or \
+                pass_mask.numel() != 2 * B * X * Y * Z:
+            raise Sp3dError("unproject_fwd(wide_mask=True): pass_mask must be a contiguous int16 (2, B, X*Y*Z) tensor")
+        flags |= HM_WIDE_MASK
     if pass_mask is not None:
         rc = lib.sp3d_unproject_fwd_train(_ptr_array(views), layout | flags, jp, cam.data_ptr(), _opt(sample_of),
                                           centers.data_ptr(), valid.data_ptr(), cubes.data_ptr(), _opt(grids),
@@ -632,16 +642,22 @@ def channel_shift_act_(y: torch.Tensor, shift: torch.Tensor, mode: int, residual
 def unproject_bwd_packed(cam, centers, valid, grad_cubes: torch.Tensor, pass_mask: torch.Tensor, batch: int,
                          num_views: int, J: int, jp: int, h: int, w: int, cube_size, grid_size, img_size,
                          sample_of: Optional[torch.Tensor] = None, deterministic: bool = False, return_packed: bool = False,
-                         scatter: int = SCATTER_AUTO):
+                         scatter: int = SCATTER_AUTO, wide: bool = False):
     """line-coalesced scatter: -> list[V] of (B,J,h,w) gradient views into one (V,B,h,w,jp) channels-last buffer
     (``return_packed``: that buffer itself, pad channels zero).
     ``deterministic``: accumulate in 64-bit fixed point (integer atomics): bit-identical run to run.
-    ``scatter``: SCATTER_AUTO (by voxel pitch) / SCATTER_PER_TAP / SCATTER_MERGE - a per-call choice (include/sp3d.h)."""
+    ``scatter``: SCATTER_AUTO (by voxel pitch) / SCATTER_PER_TAP / SCATTER_MERGE - a per-call choice (include/sp3d.h).
+    ``wide`` (SP3D_SCATTER_WIDE): 17..32 joints; ``jp`` must be 32, ``pass_mask`` the (2, P, X*Y*Z) mask of
+    ``unproject_fwd(wide_mask=True)``; the buffer is (V,B,h,w,32)."""
     lib = load()
     dev = cam.device
     _require_cam(cam)
     P = int(grad_cubes.shape[0])
     X, Y, Z = (int(c) for c in cube_size)
+    if wide:
+        if pass_mask.numel() != 2 * P * X * Y * Z:
+            raise Sp3dError("unproject_bwd_packed(wide=True): pass_mask must hold (2, P, X*Y*Z) words")
+        scatter = int(scatter) | SCATTER_WIDE
     gc = grad_cubes[:, :J].float().contiguous()
     if deterministic:
         # scale = 2^(40 - ceil(log2 max|g|)): computed on the device, no host synchronisation

@@ -86,6 +86,7 @@ struct FwdRequest {
     int io;              // bit 0 = the heat-maps are bf16, bit 1 = the cubes are bf16
     bool one, out_cl, zd, out_aligned;   // one-channel read; channels-last result; z-spectrum result; result 16-byte aligned
     bool one_train;      // one-channel read that also writes the pass mask (sp3d_unproject_one_fwd_train)
+    bool wide_mask;      // SP3D_HM_WIDE_MASK: the pass mask has two planes of P * N words, one per channel group of Jp = 32
     Geom g;
 };
 
@@ -196,8 +197,9 @@ static int resolve_one(const FwdRequest &rq, Launch &L)
 //             no VGPR does), its result pointer 16 channel planes further, and its Geom has J - 16 channels.
 // The per-channel arithmetic is the 16-channel kernels', so each group is bit-identical to the oracle by construction.  Only
 // group 0 writes grids; a sample that `valid` skips gets zeros in each group.  Planar results only (dense or strided: the
-// strided path already carries full-volume strides), the two planar defaults only (pipe / brick stacks), no pass mask.
-constexpr int WIDE_PS = 32;
+// strided path already carries full-volume strides), the two planar defaults only (pipe / brick stacks).  A pass mask only
+// with SP3D_HM_WIDE_MASK (sp3d_unproject_fwd_train): each group writes the 16-bit words of its own channels into its own
+// plane of P * N words - group 1's mask pointer lies P * N words further, bit j of its words being channel 16 + j.
 
 // The one place a forward request becomes launches: every downgrade and refusal, in this order.  Pure host arithmetic.
 static int resolve_fwd(const FwdRequest &rq, FwdTuning t, Launch (&plan)[SP3D_PLAN_RECORDS], int &n)
@@ -206,6 +208,9 @@ static int resolve_fwd(const FwdRequest &rq, FwdTuning t, Launch (&plan)[SP3D_PL
     Launch &L = plan[0];
     L = Launch{};
     L.g = rq.g; L.grid_y = 1; L.grids = true;
+    // the two-plane mask belongs to the Jp = 32 training forward with a planar fp32 result, and to nothing else
+    if (rq.wide_mask && (rq.one || !rq.g.pass_mask || rq.layout != SP3D_LAYOUT_NHWC || rq.Jp != WIDE_PS || rq.out_cl || rq.io))
+        return SP3D_EUNSUPPORTED;
     if (rq.one) return resolve_one(rq, L);
     if (rq.layout == SP3D_LAYOUT_PLANAR) {
         if (rq.out_cl || rq.io) return SP3D_EUNSUPPORTED;
@@ -225,7 +230,7 @@ static int resolve_fwd(const FwdRequest &rq, FwdTuning t, Launch (&plan)[SP3D_PL
     if (t.brick) t.pipe = 1;
     if (rq.io) t.one_wave = 1;                 // bf16 storage: one wave per workgroup only
     if (rq.Jp == WIDE_PS) {
-        if (g.J > WIDE_PS || rq.out_cl || g.pass_mask || rq.zd || tile_only) return SP3D_EUNSUPPORTED;
+        if (g.J > WIDE_PS || rq.out_cl || (g.pass_mask && !rq.wide_mask) || rq.zd || tile_only) return SP3D_EUNSUPPORTED;
         if (memcmp(&asked, &pipe, sizeof(t)) && memcmp(&asked, &stacks, sizeof(t))) return SP3D_EUNSUPPORTED;
         Geom gg = g;
         gg.J = g.J < 16 ? g.J : 16;
@@ -234,6 +239,7 @@ static int resolve_fwd(const FwdRequest &rq, FwdTuning t, Launch (&plan)[SP3D_PL
         Launch &L1 = plan[n++];
         L1 = L;
         gg.J = g.J - 16;
+        if (g.pass_mask) gg.pass_mask = g.pass_mask + (size_t)g.B * g.N;
         L1.view_off = 16 * ((rq.io & 1) ? 2 : 4);
         L1.out_off = (size_t)16 * g.sJ * ((rq.io & 2) ? 2 : 4);
         L1.grids = false;
@@ -275,6 +281,7 @@ static int fwd_request(FwdRequest &rq, int hm_layout, int Jp, bool ptrs, int B, 
     rq.io = ((hm_layout & SP3D_HM_BF16) ? 1 : 0) | ((hm_layout & SP3D_OUT_BF16) ? 2 : 0);
     rq.one = (hm_layout & SP3D_HM_ONE_CHANNEL) != 0;
     rq.out_cl = (hm_layout & SP3D_OUT_CHANNELS_LAST) != 0;
+    rq.wide_mask = (hm_layout & SP3D_HM_WIDE_MASK) != 0;
     rq.zd = false; rq.out_aligned = true; rq.one_train = false;
     return SP3D_OK;
 }
@@ -289,6 +296,9 @@ static int run_fwd(const FwdRequest &rq, const FwdTuning &t, const float *const 
     Launch plan[SP3D_PLAN_RECORDS];
     int n;
     rc = resolve_fwd(rq, t, plan, n);
+    // SP3D_HM_WIDE_MASK at J <= 16: no second group, so nobody writes plane 1 - it is zeros
+    if (!rc && rq.wide_mask && n == 1)
+        rc = (int)hipMemsetAsync(rq.g.pass_mask + (size_t)rq.g.B * rq.g.N, 0, (size_t)rq.g.B * rq.g.N * sizeof(uint16_t), (hipStream_t)stream);
     for (int i = 0; !rc && i < n; ++i) rc = launch_fwd(plan[i], v, cam, centers, valid, cubes, grids, (hipStream_t)stream);
     return rc;
 }
@@ -434,7 +444,7 @@ extern "C" int sp3d_unproject_fwd_plan(int entry, int hm_layout, int Jp, const i
     if (!names || !fields || !tuning || !records) return SP3D_ENULL;
     if (entry < SP3D_PLAN_INDEXED || entry > SP3D_PLAN_ONE_TRAIN) return SP3D_EINVAL;
     const float grid_size[3] = {1.0f, 1.0f, 1.0f};
-    if (entry == SP3D_PLAN_ZDFT) hm_layout = SP3D_LAYOUT_NHWC;
+    if (entry == SP3D_PLAN_ZDFT) hm_layout = SP3D_LAYOUT_NHWC | (hm_layout & SP3D_HM_WIDE_MASK);     // the entry has no layout word; the flag is kept to be refused
     if (entry == SP3D_PLAN_TUNING) hm_layout = SP3D_LAYOUT_NHWC | ((variant & SP3D_TUNING_CHANNELS_LAST) ? SP3D_OUT_CHANNELS_LAST : 0);
     if (entry == SP3D_PLAN_ONE_TRAIN) hm_layout |= SP3D_HM_ONE_CHANNEL;
     FwdRequest rq;

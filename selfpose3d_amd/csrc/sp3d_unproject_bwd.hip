@@ -119,7 +119,11 @@ __global__ __launch_bounds__(TILE) void unproject_bwd_kernel(Views hm, const flo
 // associative, so the result does not depend on the order in which the hardware retires the atomics: bit-identical
 // run to run (what SURVEY.md §5 asks for, since the reference's grid_sampler_2d_backward is order-dependent too);
 // sp3d_fixed_to_float converts back.  *scale = 2^k chosen by the caller from max|grad| so that 2^40 steps span it.
-template <int JP, bool XCD, bool DET = false>
+// PS: pixel stride of the gradient buffer in elements.  PS = JP is the packed form above.  PS = 32 > JP is one channel group of
+// SP3D_SCATTER_WIDE (17..32 joints, a pixel is 32 elements): the launch scatters g.J <= JP channels of a (P, J, X, Y, Z)
+// gradient whose cube stride is g.sB, into the JP channels that start at the base pointer it is given; everything indexed
+// by channel (loops, LDS tile) keeps JP, everything that steps between pixels takes PS.
+template <int JP, bool XCD, bool DET = false, int PS = JP>
 __global__ __launch_bounds__(64) void unproject_bwd2_kernel(const float *__restrict__ cam,
                                                            const float *__restrict__ centers,
                                                            const uint8_t *__restrict__ valid,
@@ -168,7 +172,7 @@ __global__ __launch_bounds__(64) void unproject_bwd2_kernel(const float *__restr
         const bool bound = sample_pos_fast(cm, x, y, z, g, ix, iy, isnan) && inb;
         if (bound) mymask |= (1u << c);
         if (isnan && inb) mymask |= 0x80000000u;
-        const Rec r = make_record<JP>(bound && !isnan, isnan ? 0.0f : ix, isnan ? 0.0f : iy, g.w, g.h);
+        const Rec r = make_record<PS>(bound && !isnan, isnan ? 0.0f : ix, isnan ? 0.0f : iy, g.w, g.h);
         const int base = c * 320 + lane;
         reci[base] = r.off;
         rec[base + 64] = r.w00; rec[base + 128] = r.w10; rec[base + 192] = r.w01; rec[base + 256] = r.w11;
@@ -177,7 +181,7 @@ __global__ __launch_bounds__(64) void unproject_bwd2_kernel(const float *__restr
     const uint32_t pm = inb ? (uint32_t)pass_mask[(size_t)b * g.N + n] : 0u;
     const float den = (float)__popc(mymask & 0x7fffffffu) + 1e-6f;
     const bool dead = (mymask & 0x80000000u) != 0 || (mymask & 0x7fffffffu) == 0;
-    const float *gc = grad_cubes + (size_t)b * g.J * g.N + n;
+    const float *gc = grad_cubes + (PS == JP ? (size_t)b * g.J * g.N : (size_t)b * g.sB) + n;
     bool any = false;
     // the J gradient loads of a voxel in flight together (n is a valid voxel for every lane): inside the per-channel condition
     // they were JP dependent round trips per wave
@@ -199,7 +203,7 @@ __global__ __launch_bounds__(64) void unproject_bwd2_kernel(const float *__restr
     // scatter: lane = (v4, ch)
     const int v4 = lane >> 4, ch = lane & 15;
     if (ch >= JP) return;
-    const size_t rowf = (size_t)g.w * JP;
+    const size_t rowf = (size_t)g.w * PS;
     ACC *gbase = grad_packed + (size_t)bs * g.h * rowf + ch;
 #pragma unroll 1
     for (int m = 0; m < 16; ++m) {
@@ -213,9 +217,9 @@ __global__ __launch_bounds__(64) void unproject_bwd2_kernel(const float *__restr
             ACC *p = gbase + (size_t)c * view_stride + reci[rb];
             const float w00 = rec[rb + 64], w10 = rec[rb + 128], w01 = rec[rb + 192], w11 = rec[rb + 256];
             if (w00 != 0.0f) add(p, gv * w00);
-            if (w10 != 0.0f) add(p + JP, gv * w10);
+            if (w10 != 0.0f) add(p + PS, gv * w10);
             if (w01 != 0.0f) add(p + rowf, gv * w01);
-            if (w11 != 0.0f) add(p + rowf + JP, gv * w11);
+            if (w11 != 0.0f) add(p + rowf + PS, gv * w11);
         }
     }
 }
@@ -253,7 +257,8 @@ constexpr int B3_PXS = B3_PX + 4;    // plane stride (int64 words): == 4 mod 32,
                                  // 32 no pass-1 projection, 64 no patch clear, 128 no divisions
 #endif
 
-template <int JP, bool DET>
+// PS: pixel stride of the gradient buffer, as in unproject_bwd2_kernel (the patch and its flush lanes keep JP channels)
+template <int JP, bool DET, int PS = JP>
 __global__ __launch_bounds__(256, 4) void unproject_bwd3_kernel(const float *__restrict__ cam, const float *__restrict__ centers,
                                                             const uint8_t *__restrict__ valid,
                                                             const float *__restrict__ grad_cubes,
@@ -278,7 +283,7 @@ __global__ __launch_bounds__(256, 4) void unproject_bwd3_kernel(const float *__r
     const bool inb = vx < g.X && vy < g.Y && vz < g.Z;
     const int n = (min(vx, g.X - 1) * g.Y + min(vy, g.Y - 1)) * g.Z + min(vz, g.Z - 1);
     // gradient of this voxel, all channels: issued first, consumed after pass 1
-    const float *gc = grad_cubes + (size_t)b * g.J * g.N + n;
+    const float *gc = grad_cubes + (PS == JP ? (size_t)b * g.J * g.N : (size_t)b * g.sB) + n;
     float gq[JP];
 #pragma unroll
     for (int j = 0; j < JP; ++j) gq[j] = (SP3D_B3_ABL & 16) ? (float)(j + tid) : gc[(size_t)min(j, g.J - 1) * g.N];
@@ -349,7 +354,7 @@ __global__ __launch_bounds__(256, 4) void unproject_bwd3_kernel(const float *__r
     }
     if (SP3D_B3_ABL & 8) return;
 
-    const size_t rowf = (size_t)g.w * JP;
+    const size_t rowf = (size_t)g.w * PS;
 #pragma unroll 1
     for (int c = 0; c < g.V; ++c) {
         const int rx0 = rect[4 * c + 0], ry0 = rect[4 * c + 1], rx1 = rect[4 * c + 2], ry1 = rect[4 * c + 3];
@@ -368,13 +373,13 @@ __global__ __launch_bounds__(256, 4) void unproject_bwd3_kernel(const float *__r
             // non-finite value reaches exactly the pixels its voxel touches)
             if constexpr (!DET) {
                 if (act) {
-                    ACC *p0 = gview + ((size_t)r.y0 * g.w + r.x0) * JP;
+                    ACC *p0 = gview + ((size_t)r.y0 * g.w + r.x0) * PS;
 #pragma unroll
                     for (int j = 0; j < JP; ++j) {
                         if (j >= g.J) break;
 #pragma unroll
                         for (int t = 0; t < 4; ++t)
-                            if (wts[t] != 0.0f) unsafeAtomicAdd(p0 + (size_t)(t >> 1) * rowf + (t & 1) * JP + j, gq[j] * wts[t]);
+                            if (wts[t] != 0.0f) unsafeAtomicAdd(p0 + (size_t)(t >> 1) * rowf + (t & 1) * PS + j, gq[j] * wts[t]);
                     }
                 }
             }
@@ -417,7 +422,7 @@ __global__ __launch_bounds__(256, 4) void unproject_bwd3_kernel(const float *__r
                     patch[ch * B3_PXS + px] = 0ull;
                     const int ty = (int)(((float)px + 0.5f) * rww), tx = px - ty * ww;
                     if (tx >= nwx || (SP3D_B3_ABL & 1)) continue;
-                    ACC *dst = gview + ((size_t)(wy0 + ty) * g.w + (wx0 + tx)) * JP + ch;
+                    ACC *dst = gview + ((size_t)(wy0 + ty) * g.w + (wx0 + tx)) * PS + ch;
                     if constexpr (DET) atomicAdd(dst, (unsigned long long)val);
                     else unsafeAtomicAdd(dst, (float)((double)val * inv_scale));
                 }
@@ -490,6 +495,11 @@ extern "C" int sp3d_unproject_bwd(const float *const *hm_views, const float *cam
 
 // scatter: which kernel sp3d_unproject_bwd_packed[_det] launches - SP3D_SCATTER_AUTO (by voxel pitch), _PER_TAP (bwd2),
 // _MERGE (bwd3).  A per-call argument: the library keeps no selector state (include/sp3d.h "no global state").
+// | SP3D_SCATTER_WIDE: 17..32 joints in a 32-element pixel, as two channel groups - one launch each, like the forward
+// (sp3d_unproject.hip, WIDE_PS).  Group 0 scatters channels 0-15 under mask plane 0 through the JP = 16 kernel; group 1
+// scatters channels 16..J-1 under plane 1 through the kernel of width ceil4(J - 16): its gradient base lies 16 elements
+// into the pixel, its grad_cubes 16 channel volumes further, its Geom has J - 16 channels.  Both read cubes at the stride
+// of all J channels (Geom::sB) and step pixels by 32.  One scatter choice for both, so AUTO decides once.
 static int bwd_packed_impl(const float *cam, const int32_t *sample_of, const float *centers, const uint8_t *valid,
                            const float *grad_cubes, const uint16_t *pass_mask, void *grad_acc, const float *scale, int B,
                            int P, int V, int J, int Jp, int h, int w, int X, int Y, int Z, const float *grid_size,
@@ -499,9 +509,14 @@ static int bwd_packed_impl(const float *cam, const int32_t *sample_of, const flo
     int rc = make_geom(g, P, V, J, h, w, X, Y, Z, grid_size, W_in, H_in);
     if (rc) return rc;
     if (B <= 0) return SP3D_EINVAL;
-    if (scatter != SP3D_SCATTER_AUTO && scatter != SP3D_SCATTER_PER_TAP && scatter != SP3D_SCATTER_MERGE) return SP3D_EINVAL;
+    const bool wide = (scatter & SP3D_SCATTER_WIDE) != 0;
+    const int choice = scatter & 0xff;
+    if ((scatter & ~(0xff | SP3D_SCATTER_WIDE)) != 0) return SP3D_EINVAL;
+    if (choice != SP3D_SCATTER_AUTO && choice != SP3D_SCATTER_PER_TAP && choice != SP3D_SCATTER_MERGE) return SP3D_EINVAL;
     if (!cam || !centers || !valid || !grad_cubes || !pass_mask || !grad_acc) return SP3D_ENULL;
-    if (Jp < J || (Jp & 3) || Jp > 16 || w < 2 || h < 2) return SP3D_EUNSUPPORTED;
+    if (w < 2 || h < 2) return SP3D_EUNSUPPORTED;
+    // wide: the tap offset (y0 * w + x0) * 32 is a 32-bit int; the bound is the forward's (24-bit pixel indices)
+    if (wide ? (Jp != WIDE_PS || J > WIDE_PS || (int64_t)h * w > (1 << 24)) : (Jp < J || (Jp & 3) || Jp > 16)) return SP3D_EUNSUPPORTED;
     g.sample_of = sample_of;
     const int tiles = (g.N + 63) / 64;
     const size_t view_stride = (size_t)B * h * w * Jp;
@@ -509,30 +524,45 @@ static int bwd_packed_impl(const float *cam, const int32_t *sample_of, const flo
     // The pixel pitch depends on the cameras (device data); what the host knows is the voxel pitch in mm: <= 50 mm.
     const bool dense = X >= 2 && Y >= 2 && Z >= 2 && (double)grid_size[0] / (X - 1) <= 50.0 &&
                        (double)grid_size[1] / (Y - 1) <= 50.0 && (double)grid_size[2] / (Z - 1) <= 50.0;
-    const bool merge = scatter == SP3D_SCATTER_MERGE || (scatter == SP3D_SCATTER_AUTO && dense);
+    const bool merge = choice == SP3D_SCATTER_MERGE || (choice == SP3D_SCATTER_AUTO && dense);
     const int nbx = (X + B3_BX - 1) / B3_BX, nby = (Y + B3_BY - 1) / B3_BY, nbz = (Z + B3_BZ - 1) / B3_BZ;
     // bwd3: the 16-byte z runs a block reads of the gradient volume share their 256-byte rows with the blocks above and
     // below: keep a whole z column of blocks on one XCD, back to back in dispatch order (chunk = nbz when a power of two)
     if (merge && (nbz & (nbz - 1)) == 0) g.xcd_chunk = nbz;
     const dim3 grid(xcd_grid_blocks(P, merge ? nbx * nby * nbz : tiles, g.xcd_chunk)), block(merge ? 256 : 64);
-    const size_t lds = merge ? (size_t)Jp * B3_PXS * sizeof(unsigned long long) + (4 * SP3D_MAX_VIEWS + 4) * sizeof(int)
-                             : (size_t)(V * 320 + Jp * 64 + 64) * sizeof(float);
     hipStream_t s = (hipStream_t)stream;
-    auto launch = [&](auto jp, auto det) {
-        constexpr int JP = decltype(jp)::value;
+    // one launch: `jp` channels (the kernel's width) starting at channel ch0 of the pixel and of the cubes, under mask plane pm
+    auto launch = [&](auto jp, auto wd, auto det, const Geom &gg, int ch0, const uint16_t *pm) {
+        constexpr int JP = decltype(jp)::value, PS = decltype(wd)::value ? WIDE_PS : JP;
         constexpr bool DET = decltype(det)::value;
+        const size_t lds = merge ? (size_t)JP * B3_PXS * sizeof(unsigned long long) + (4 * SP3D_MAX_VIEWS + 4) * sizeof(int)
+                                 : (size_t)(V * 320 + JP * 64 + 64) * sizeof(float);
+        const float *gc = grad_cubes + (size_t)ch0 * g.N;
+        void *acc = static_cast<char *>(grad_acc) + (size_t)ch0 * (DET ? sizeof(unsigned long long) : sizeof(float));
         if (merge)
-            hipLaunchKernelGGL((unproject_bwd3_kernel<JP, DET>), grid, block, lds, s, cam, centers, valid, grad_cubes, pass_mask,
-                               grad_acc, view_stride, g, nbx, nby, nbz, scale);
+            hipLaunchKernelGGL((unproject_bwd3_kernel<JP, DET, PS>), grid, block, lds, s, cam, centers, valid, gc, pm,
+                               acc, view_stride, gg, nbx, nby, nbz, scale);
         else
-            hipLaunchKernelGGL((unproject_bwd2_kernel<JP, true, DET>), grid, block, lds, s, cam, centers, valid, grad_cubes,
-                               pass_mask, grad_acc, view_stride, g, tiles, scale);
+            hipLaunchKernelGGL((unproject_bwd2_kernel<JP, true, DET, PS>), grid, block, lds, s, cam, centers, valid, gc,
+                               pm, acc, view_stride, gg, tiles, scale);
     };
-    with_jp(Jp, [&](auto jp) {
-        if (scale) launch(jp, std::true_type{});
-        else launch(jp, std::false_type{});
-    });
-    return launch_status();
+    const int groups = (wide && J > 16) ? 2 : 1;
+    for (int k = 0; k < groups && !rc; ++k) {
+        Geom gg = g;                                   // gg.sB stays J * N: the cube stride of grad_cubes
+        if (wide) gg.J = k ? J - 16 : (J < 16 ? J : 16);
+        const int width = wide ? (k ? (gg.J + 3) / 4 * 4 : 16) : Jp;
+        const uint16_t *pm = pass_mask + (size_t)k * P * g.N;
+        with_jp(width, [&](auto jp) {
+            auto go = [&](auto wd) {
+                if (scale) launch(jp, wd, std::true_type{}, gg, 16 * k, pm);
+                else launch(jp, wd, std::false_type{}, gg, 16 * k, pm);
+            };
+            if (wide) go(std::true_type{});
+            else go(std::false_type{});
+        });
+        rc = launch_status();
+    }
+    return rc;
 }
 
 extern "C" int sp3d_unproject_bwd_packed(const float *cam, const int32_t *sample_of, const float *centers,

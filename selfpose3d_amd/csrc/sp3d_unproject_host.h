@@ -26,6 +26,7 @@ constexpr int WOFF = 2 * 4 * 64;           // first offset word
 constexpr int WOSTR = 68;                  // sOut row stride (floats), rows 16-B aligned
 constexpr int BR = 4;                      // brick kernels: a wave owns BR x BR x BR voxels
 constexpr int ZDZ = 20, ZDSZ = 28;         // brick kernel, z-spectrum result: z extent of the grid, length of the z transform
+constexpr int WIDE_PS = 32;                // 17..32 joints: elements of a packed pixel, gathered and scattered as two channel groups
 
 inline int make_geom(Geom &g, int B, int V, int J, int h, int w, int X, int Y, int Z, const float *grid_size,
                      int W_in, int H_in)

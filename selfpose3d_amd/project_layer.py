@@ -141,6 +141,22 @@ def one_channel_source(hms: Sequence[torch.Tensor]):
     return first
 
 
+def unproject_path(J: int, grad_hm: bool, h: int, w: int, mode: str, wide_grad: bool) -> str:
+    """Which kernels a ``get_voxel`` call takes: ``"nhwc"`` or ``"planar"``, or a raise for a ``mode="nhwc"`` request the
+    NHWC path cannot differentiate.  Pure (no tensors): ``J`` joints, ``grad_hm`` = a heat-map gradient is wanted, an
+    ``h`` x ``w`` map, the layer's ``mode`` and its ``wide_grad`` switch (already False for bf16 storage).
+    17..32 joints (Jp = 32) run NHWC without a gradient; with one they keep the planar kernels - the pass mask of the
+    packed backward holds 16 bits per voxel - unless ``wide_grad`` asks for the two-plane mask and the wide scatter."""
+    wide = 16 < J <= 32
+    wide_ok = wide and (not grad_hm or (wide_grad and w >= 2 and h >= 2))
+    if mode == "auto":
+        return "nhwc" if ((J <= 16 or wide_ok) and w >= 2 and h >= 2) else "planar"
+    if mode == "nhwc" and J > 16 and grad_hm and not wide_ok:
+        raise _lib.Sp3dError(f"ProjectLayer(mode='nhwc'): {J} joints with a heat-map gradient - the NHWC path "
+                             "differentiates at most 16 joints (use mode='planar' or 'auto')")
+    return mode
+
+
 class _UnprojectFn(torch.autograd.Function):
     """autograd seam: gradient flows to the heat-maps only."""
 
@@ -202,16 +218,20 @@ class _UnprojectFn(torch.autograd.Function):
             views = [packed[c] for c in range(len(hms))]
             # when a gradient will be asked for, let the kernel also emit the clamp pass mask: the backward
             # then runs the line-coalesced scatter without re-reading any heat-map
-            need_grad = io == torch.float32 and any(ctx.needs_input_grad[12:]) and w >= 2 and h >= 2 and jp <= 16
+            need_grad = io == torch.float32 and any(ctx.needs_input_grad[12:]) and w >= 2 and h >= 2 and \
+                (jp <= 16 or (jp == 32 and layer.wide_grad))
+            # 17..32 joints under ``wide_grad``: one 16-bit mask plane per channel group, read back by the wide scatter
+            two_planes = need_grad and jp == 32
             X, Y, Z = cube_size
-            mask = torch.empty((B, X * Y * Z), dtype=torch.int16, device=cam.device) if need_grad else None
+            mask = torch.empty(((2,) if two_planes else ()) + (B, X * Y * Z), dtype=torch.int16, device=cam.device) if need_grad else None
             # pad_channels: run the kernel over all jp channels - the padded ones are zero in `packed`,
             # so the extra output channels are exact zeros at no extra cost
             cubes, grids = _lib.unproject_fwd(views, _lib.LAYOUT_NHWC, jp, cam, centers, valid, B,
                                               jp if pad_channels else J, h, w, cube_size, grid_size, layer.img_size,
                                               want_grids, channels_last=channels_last, sample_of=sample_of,
-                                              out_dtype=io, pass_mask=mask, out=None if need_grad else out)
+                                              out_dtype=io, pass_mask=mask, out=None if need_grad else out, wide_mask=two_planes)
             ctx.packed_bwd = (mask, jp, int(heatmaps[0].shape[0]), len(hms), J, h, w) if need_grad else None
+            ctx.two_planes = two_planes
         else:
             ctx.packed_bwd = None
             cubes, grids = _lib.unproject_fwd(hms, _lib.LAYOUT_PLANAR, 0, cam, centers, valid, B, J, h, w, cube_size,
@@ -253,7 +273,7 @@ class _UnprojectFn(torch.autograd.Function):
             mask, jp, batch, nv, J, h, w = ctx.packed_bwd
             grads = _lib.unproject_bwd_packed(cam, centers, valid, grad_cubes, mask, batch, nv, J, jp, h, w, cube_size,
                                               grid_size, ctx.layer.img_size, sample_of=ctx.sample_of,
-                                              deterministic=ctx.layer.deterministic_backward)
+                                              deterministic=ctx.layer.deterministic_backward, wide=ctx.two_planes)
             return (None,) * 12 + wide(grads)
         grads = _lib.unproject_bwd(hms, cam, centers, valid, grad_cubes, cube_size, grid_size, ctx.layer.img_size,
                                    sample_of=ctx.sample_of)
@@ -262,7 +282,8 @@ class _UnprojectFn(torch.autograd.Function):
 
 class ProjectLayer(nn.Module):
     """See module docstring.  ``mode``: "nhwc" (re-tile + fast kernel: J <= 16, and J <= 32 without a heat-map
-    gradient), "planar" (direct kernel on the reference layout) or "auto" (nhwc wherever it applies)."""
+    gradient - with one under ``wide_grad``), "planar" (direct kernel on the reference layout) or "auto" (nhwc wherever it
+    applies)."""
 
     def __init__(self, cfg, mode: str = "auto", io_dtype: torch.dtype = torch.float32):
         super().__init__()
@@ -287,6 +308,11 @@ class ProjectLayer(nn.Module):
         # instead of slice copy + re-tile + packed training forward + 4-channel scatter.  Same cubes, same deterministic
         # gradient bits; off until tools/bench_roothm_grad.py has recorded that it is faster
         self.one_channel_grad = os.environ.get("SP3D_ONE_CHANNEL_GRAD", "0") not in ("", "0")
+        # opt-in (SP3D_WIDE_GRAD=1 / ``wide_grad = True``): 17..32 joints (fp32 storage) WITH a heat-map gradient train through
+        # the channels-last pair - training forward with a two-plane pass mask, wide packed scatter (fp32 or deterministic) -
+        # instead of planar forward + planar backward.  Same cubes as the no-grad forward; off until tools/bench_wide_grad.py
+        # has recorded that it is faster in every leg
+        self.wide_grad = os.environ.get("SP3D_WIDE_GRAD", "0") not in ("", "0")
 
     @contextlib.contextmanager
     def static_camera_table(self, table: torch.Tensor):
@@ -401,16 +427,8 @@ class ProjectLayer(nn.Module):
             cube_size = [cube_size] * 3
         if isinstance(grid_size, (int, float)):
             grid_size = [grid_size] * 3
-        mode = self.mode
-        # 17..32 joints (Jp = 32): forward only - the pass mask of the packed backward holds 16 bits per voxel, so a
-        # heat-map gradient keeps the planar kernels there
-        wide = 16 < J <= 32
         grad_hm = torch.is_grad_enabled() and any(x.requires_grad for x in heatmaps)
-        if mode == "auto":
-            mode = "nhwc" if ((J <= 16 or (wide and not grad_hm)) and w >= 2 and h >= 2) else "planar"
-        elif mode == "nhwc" and J > 16 and grad_hm:
-            raise _lib.Sp3dError(f"ProjectLayer(mode='nhwc'): {J} joints with a heat-map gradient - the NHWC path "
-                                 "differentiates at most 16 joints (use mode='planar' or 'auto')")
+        mode = unproject_path(J, grad_hm, h, w, self.mode, self.wide_grad and self.io_dtype == torch.float32)
         if self.io_dtype != torch.float32 and (mode != "nhwc" or self.jp_for(J) not in (16, 32) or J > 32):
             raise _lib.Sp3dError("bf16 storage needs the NHWC path with 13..32 joints")
         if mode != "nhwc" or J > 16:
