@@ -510,7 +510,13 @@ int sp3d_wino_fused_split64(const float *x, const void *U3, float *y, const floa
  * sp3d_channel_shift_act, as an implicit GEMM on v_mfma_f32_32x32x16_bf16 with exact three-piece bf16 splits of both
  * operands (fp32 accuracy, fp32 accumulation; no Winograd transforms).  x, y channels-last (B,X,Y,Z,C) / (B,X,Y,Z,O);
  * W3: 48-byte records of bf16 = the three B operands {hi,lo} {hi,hi} {mid,mid} (4 channels each) at index
- * ((tap*(C/8) + chunk)*2 + half)*O + o, tap = kz*9 + ky*3 + kx of w[o][c][kx][ky][kz] (_lib.conv_weights_split), 16-byte aligned.  (C,O) in {(16,32),(32,32)}. */
+ * ((tap*(C/8) + chunk)*2 + half)*O + o, tap = kz*9 + ky*3 + kx of w[o][c][kx][ky][kz] (_lib.conv_weights_split), 16-byte aligned.  (C,O) in {(16,32),(32,32)}.
+ * (C,O) in {(64,128),(128,128)}, the quarter-resolution layers, run another kernel: one workgroup per block of 5x5x5 output
+ * voxels x 32 outputs, K (27 taps x C) divided over its four matrix waves, whose partial sums are added in a fixed order
+ * (deterministic).  W3 is then, per (tap, chunk, 32 outputs), 1536 contiguous bytes of bf16 at index
+ * (tap*(C/8) + chunk)*(O/32) + o/32: [half][o%32] x {hi,lo} of 4 channels (16 bytes each), then [half][o%32] x {mid} (8 bytes
+ * each) (_lib.conv_weights_split24); x, W3, y, shift and residual 16-byte aligned (SP3D_EUNSUPPORTED); ReLU is fmaxf, as
+ * sp3d_wino_output.  Any other (C,O): SP3D_EUNSUPPORTED. */
 int sp3d_conv3_split(const float *x, const void *W3, float *y, const float *shift, const float *residual, int mode, int B,
                      int X, int Y, int Z, int C, int O, void *stream);
 

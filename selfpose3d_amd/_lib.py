@@ -880,6 +880,19 @@ def conv_weights_split(w: torch.Tensor) -> torch.Tensor:
     return torch.stack([hi, lo, hi, hi, mid, mid], -2).contiguous()        # the B operands {bh,bl} {bh,bh} {bm,bm}
 
 
+def conv_weights_split24(w: torch.Tensor) -> torch.Tensor:
+    """(O,C,3,3,3) conv weights, O % 32 == 0 -> what sp3d_conv3_split reads for O = 128: (27, C/8, O/32, 768) bfloat16, per (tap, chunk,
+    32 outputs) one block of 1 536 contiguous bytes = [half 2][output 32] x {hi,lo} of 4 channels (16 bytes) followed by
+    [half 2][output 32] x {mid} of 4 channels (8 bytes); tap = kz*9 + ky*3 + kx, channel = 8*chunk + 4*half + q.  The three
+    pieces once each (24 bytes per output and 4 channels): the kernel assembles {hi,hi} and {mid,mid} in registers."""
+    O, Cc = int(w.shape[0]), int(w.shape[1])
+    pc = wino_weights_split(w.float().permute(4, 3, 2, 1, 0).reshape(27, Cc, O).contiguous(), 8)   # [tap, chunk, half, o, piece (mid,hi,lo), 4]
+    pc = pc.reshape(27, Cc // 8, 2, O // 32, 32, 3, 4).permute(0, 1, 3, 2, 4, 5, 6)                # [tap, chunk, og, half, t, piece, 4]
+    hl = torch.stack([pc[..., 1, :], pc[..., 2, :]], -2).reshape(27, Cc // 8, O // 32, 512)
+    mid = pc[..., 0, :].reshape(27, Cc // 8, O // 32, 256)
+    return torch.cat([hl, mid], -1).contiguous()
+
+
 def skip_fold_enabled() -> bool:
     """SP3D_FOLD_SKIP=0 keeps the 1x1x1 skip projections of the plan's residual blocks a library GEMM + residual epilogue"""
     return os.environ.get("SP3D_FOLD_SKIP", "1") not in ("0", "")
@@ -926,22 +939,73 @@ def conv3_split_(x: torch.Tensor, W3: torch.Tensor, shift: torch.Tensor, mode: i
     return y
 
 
+def quarter_direct_enabled() -> bool:
+    """SP3D_QUARTER_DIRECT=0 keeps the quarter-resolution 3x3x3 layers on the three-launch Winograd form"""
+    return os.environ.get("SP3D_QUARTER_DIRECT", "1") not in ("0", "")
+
+
+def quarter_direct_covers(B: int, C: int, O: int, X: int, Y: int, Z: int) -> bool:
+    """the layers wino_conv3d_ gives to the direct kernel (conv3_split128_) when it has their records: the widths the
+    kernel is built for, on grids its 5x5x5 output blocks tile without remainder, up to 64 blocks = 256 workgroups, one per
+    CU of an MI355X: 20x20x5 at batch 1..4 (the headline root net; 42.3 against 56.9 us per layer at batch 4, 29.2 against
+    36.6 at batch 1).  Measured and left to the three launches (profiles/r15_quarter_direct_shapes.json): 40x40x10 at batch
+    2 (four rounds of workgroups: 150.0 against 147.0 us) and the ragged grids, where the kernel is correct but multiplies
+    rows that are no outputs - 12x12x3 (38 % outputs: 27.9 against 22.2 us at batch 1, 31.4 against 31.9 at batch 4) and
+    16^3 (51 %: 269 against 158 us for 8 cubes)."""
+    blocks = B * (X // 5) * (Y // 5) * (Z // 5)
+    return O == 128 and C in (64, 128) and X % 5 == 0 and Y % 5 == 0 and Z % 5 == 0 and blocks <= 64
+
+
+def conv3_split128_(x: torch.Tensor, W3: torch.Tensor, shift: torch.Tensor, mode: int,
+                    residual: Optional[torch.Tensor] = None, *, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """3x3x3 stride-1 'same' conv of channels_last_3d x, (C, O) = (64 | 128, 128), with the fused epilogue: the direct
+    (implicit GEMM) kernel of the quarter-resolution layers on the bf16 matrix pipe with exact three-piece splits
+    (sp3d_conv3_split with O = 128); W3 = conv_weights_split24(w).  Any grid: output blocks of 5x5x5 voxels, ragged edges included.
+    Returns the channels_last_3d result (B,O,X,Y,Z), written into ``out`` when given."""
+    lib = load()
+    _require_cuda(x, "x")
+    B, Cc, X, Y, Z = (int(v) for v in x.shape)
+    _require_cl3d_f32(x, "conv3_split128_")
+    O = 128
+    if W3.device != x.device or W3.dtype != torch.bfloat16 or not W3.is_contiguous() or tuple(W3.shape) != (27, Cc // 8, O // 32, 768):
+        raise Sp3dError(f"conv3_split128_: W3 must be conv_weights_split24 of the ({O}, {Cc}, 3, 3, 3) weight on {x.device}; got "
+                        f"{tuple(W3.shape)}, {W3.dtype}, {W3.device}, contiguous={W3.is_contiguous()}")
+    if out is None:
+        out = _empty_cl3d(B, O, X, Y, Z, x.device)
+    else:
+        _require_cl3d_f32(out, "conv3_split128_")
+        if out.device != x.device or tuple(out.shape) != (B, O, X, Y, Z):
+            raise Sp3dError(f"conv3_split128_: out must be ({B}, {O}, {X}, {Y}, {Z}) on {x.device}, got {tuple(out.shape)} on {out.device}")
+    if residual is not None:
+        residual = _as_cl3d(residual)
+    check(lib.sp3d_conv3_split(x.data_ptr(), W3.data_ptr(), out.data_ptr(), shift.data_ptr(), _opt(residual), int(mode),
+                                  B, X, Y, Z, Cc, O, _stream(x.device)), "sp3d_conv3_split")
+    return out
+
+
 def wino_conv3d_(x: torch.Tensor, U: torch.Tensor, shift: torch.Tensor, mode: int,
-                 residual: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """3x3x3 stride-1 'same' conv of channels-last x (B,C,X,Y,Z as torch.channels_last_3d) with pre-transformed weights
-    U (64,C,O), fused with the layer epilogue; returns a channels_last_3d tensor (B,O,X,Y,Z)."""
+                 residual: Optional[torch.Tensor] = None, *, direct: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The entry of the quarter-resolution tier: 3x3x3 stride-1 'same' conv of channels-last x (B,C,X,Y,Z as
+    torch.channels_last_3d) fused with the layer epilogue; returns a channels_last_3d tensor (B,O,X,Y,Z).
+    With ``direct`` (conv_weights_split24(w)), (C, O) = (64 | 128, 128), a grid
+    quarter_direct_covers and SP3D_QUARTER_DIRECT not 0: ONE launch, the direct convolution on the bf16 matrix pipe with
+    exact three-piece splits (conv3_split128_: sp3d_conv3_split with O = 128).  Otherwise the fallback form, bit for bit what it always was: Winograd
+    F(2,3) with pre-transformed weights U (64,C,O) in three launches - input transform, the library's batched fp32 GEMM,
+    output transform + epilogue."""
     lib = load()
     _require_cuda(x, "x")
     B, Cc, X, Y, Z = (int(v) for v in x.shape)
     _require_cl3d_f32(x, "wino_conv3d_")
     O = int(U.shape[2])
+    if residual is not None:
+        residual = _as_cl3d(residual)
+    if direct is not None and quarter_direct_enabled() and quarter_direct_covers(B, Cc, O, X, Y, Z):
+        return conv3_split128_(x, direct, shift, mode, residual)
     T = B * ((X + 1) // 2) * ((Y + 1) // 2) * ((Z + 1) // 2)
     V = torch.empty((64, T, Cc), dtype=torch.float32, device=x.device)
     check(lib.sp3d_wino_input(x.data_ptr(), V.data_ptr(), B, X, Y, Z, Cc, _stream(x.device)), "sp3d_wino_input")
     M = torch.bmm(V, U)         # the 64 products: the library's fp32 batched GEMM (an own split-bf16 GEMM was not faster: round 3)
     y = _empty_cl3d(B, O, X, Y, Z, x.device)
-    if residual is not None:
-        residual = _as_cl3d(residual)
     check(lib.sp3d_wino_output(M.data_ptr(), y.data_ptr(), shift.data_ptr(), _opt(residual), int(mode), B, X, Y, Z, O,
                                _stream(x.device)), "sp3d_wino_output")
     return y

@@ -15,7 +15,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 SOURCES = ["sp3d_unproject.hip", "sp3d_unproject_tile.hip", "sp3d_unproject_pipe.hip", "sp3d_unproject_brick.hip", "sp3d_unproject_one.hip",
            "sp3d_unproject_bwd.hip", "sp3d_proposal.hip", "sp3d_epilogue.hip", "sp3d_upconv.hip", "sp3d_synth.hip", "sp3d_fftconv.hip", "sp3d_wino.hip",
-           "sp3d_wino_fused.hip", "sp3d_conv3_direct.hip", "sp3d_fft.hip", "sp3d_gbn.hip"]
+           "sp3d_wino_fused.hip", "sp3d_conv3_direct.hip", "sp3d_conv3_quarter.hip", "sp3d_fft.hip", "sp3d_gbn.hip"]
 HEADERS = [os.path.join("..", "pk_src1.py"), "sp3d_conv3_host.h", "sp3d_device.h", "sp3d_proj_pk.h", "sp3d_split.h", "sp3d_tuning.h",
            "sp3d_twiddles.h", "sp3d_unproject_host.h", "sp3d_unproject_pipe.h", os.path.join("..", "..", "include", "sp3d.h")]
 LIB = os.path.join(HERE, "libsp3d.so")
@@ -33,12 +33,13 @@ def needs_build() -> bool:
     return any(os.path.getmtime(d) > t for d in deps if os.path.exists(d))
 
 
-# per-source extra flags.  The three sources of the 3x3x3 convolutions (sp3d_wino.hip, sp3d_wino_fused.hip,
-# sp3d_conv3_direct.hip): no SLP vectorisation - next to matrix instructions the v_pk_add_f32 /
+# per-source extra flags.  The four sources of the 3x3x3 convolutions (sp3d_wino.hip, sp3d_wino_fused.hip,
+# sp3d_conv3_direct.hip, sp3d_conv3_quarter.hip): no SLP vectorisation - next to matrix instructions the v_pk_add_f32 /
 # v_pk_fma_f32 the vectoriser forms out of the operand transforms cost more than the scalar instructions they replace
 # (half-resolution fused Winograd kernel 83.4 -> 78.5 us); the unprojection kernels, on the other hand, want it.
 PER_SOURCE_FLAGS = {"sp3d_wino.hip": ["-fno-slp-vectorize"], "sp3d_wino_fused.hip": ["-fno-slp-vectorize"],
-                    "sp3d_conv3_direct.hip": ["-fno-slp-vectorize"], "sp3d_upconv.hip": ["-fno-slp-vectorize"],
+                    "sp3d_conv3_direct.hip": ["-fno-slp-vectorize"], "sp3d_conv3_quarter.hip": ["-fno-slp-vectorize"],
+                    "sp3d_upconv.hip": ["-fno-slp-vectorize"],
                     # round 4: the packed instructions the vectoriser formed in these kernels (complex multiplies: swapped
                     # halves of source 1) came out wrong next to another plan's matrix instructions; without the vectoriser
                     # they are immune at the same speed (bench step 1.563 vs 1.569 ms).  Round 5 found the one affected

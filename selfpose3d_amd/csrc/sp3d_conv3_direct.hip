@@ -410,6 +410,8 @@ static int conv3_split_launch(const float *x, const void *W3, float *y, const fl
 extern "C" int sp3d_conv3_split(const float *x, const void *W3, float *y, const float *shift, const float *residual, int mode,
                                 int B, int X, int Y, int Z, int C, int O, void *stream)
 {
+    // the quarter-resolution layers, (64 | 128) -> 128: another kernel, another weight format, the same checks in the same order
+    if (O == 128) return conv3_split128(x, W3, y, shift, residual, mode, B, X, Y, Z, C, O, stream);
     const Conv3Grid g = conv3_grid(B, X, Y, Z, CD_BX, CD_BY, CD_BZ);
     const bool supported = O == 32 && (C == 16 || C == 32) && !((reinterpret_cast<uintptr_t>(W3) | reinterpret_cast<uintptr_t>(y)) & 15);
     const bool in_range = (int64_t)X * Y * Z * C * 2 <= 0x7fffffff && g.blocks <= 0x7fffffff;

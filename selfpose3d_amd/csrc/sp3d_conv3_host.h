@@ -53,5 +53,10 @@ template <class F> inline auto with_mode(int mode, F &&f)
     }
 }
 
+// the quarter-resolution widths of sp3d_conv3_split, (C, O) = (64 | 128, 128): validation and launch of conv3_split128_kernel
+// (sp3d_conv3_quarter.hip), same arguments and return codes
+int conv3_split128(const float *x, const void *W3, float *y, const float *shift, const float *residual, int mode, int B, int X,
+                   int Y, int Z, int C, int O, void *stream);
+
 } // namespace sp3d
 #endif

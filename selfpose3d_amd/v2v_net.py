@@ -68,7 +68,10 @@ def conv3_route(cin, cout, shape, winograd=True, wino_split=True, direct_conv=Tr
     Wide layers on small grids (the 1/4- and 1/2-resolution blocks: a GEMM with few rows, where MIOpen's implicit-GEMM
     kernels drop to ~60 TFLOP/s) go through Winograd F(2x2x2,3x3x3): HIP input/output transforms around one batched
     rocBLAS GEMM, 2.1x faster at (4,128,20,20,5) and 1.2x at (4,64,40,40,10) (tools/exp_wino.py); the rule keeps the
-    transformed tensor (64*T*C floats) within reach of the Infinity Cache, beyond which the transforms eat the gain."""
+    transformed tensor (64*T*C floats) within reach of the Infinity Cache, beyond which the transforms eat the gain.
+    "wino_conv3d_" names the ENTRY of the quarter-resolution tier, not a form: given the layer's 24-byte weight records it
+    launches the direct kernel conv3_split128_ on the grids _lib.quarter_direct_covers (41 instead of 49.5 us per 128 -> 128
+    layer at (4,128,20,20,5)) and keeps the three Winograd launches, the fallback form, everywhere else."""
     B, X, Y, Z = shape
     full = cout == 32 and cin in (16, 32)                  # the full-resolution layers
     if not winograd or not (cin >= 64 or full or (cout == 64 and cin == 32)):
@@ -269,7 +272,7 @@ class _Conv(NamedTuple):
     shift: torch.Tensor                        # what is left of bias and BatchNorm, per output channel
     u: Optional[torch.Tensor] = None           # Winograd-domain weights (_lib.wino_weights)
     split: Optional[torch.Tensor] = None       # ... in three bf16 pieces (_lib.wino_weights_split): the fused kernels
-    direct: Optional[torch.Tensor] = None      # w in three bf16 pieces (_lib.conv_weights_split): conv3_split_
+    direct: Optional[torch.Tensor] = None      # w in three bf16 pieces: conv3_split_ (_lib.conv_weights_split), wino_conv3d_(direct=) (_lib.conv_weights_split24)
 
 
 class _Res(NamedTuple):
@@ -349,7 +352,13 @@ class _FoldedV2V:
         # layers of the fused kernels: weights split for the bf16 matrix pipe (lane quarters for 64 output channels)
         split = _lib.wino_weights_split(u, 16 if cout == 64 else 8) if "wino_fused_conv3d_" in routes else None
         # full-resolution layers (16 | 32 -> 32): direct convolution on the bf16 matrix pipe (three exact pieces)
-        direct = _lib.conv_weights_split(w) if "conv3_split_" in routes else None
+        # ... and the quarter-resolution layers (64 | 128 -> 128), which wino_conv3d_ runs as one direct kernel where it pays
+        if "conv3_split_" in routes:
+            direct = _lib.conv_weights_split(w)
+        elif "wino_conv3d_" in routes and cout == 128 and cin in (64, 128):
+            direct = _lib.conv_weights_split24(w)
+        else:
+            direct = None
         return _Conv(w, shift, u, split, direct)
 
     def _build(self):
@@ -402,7 +411,7 @@ class _FoldedV2V:
             return _lib.wino_fused_conv3d_(x, c.u, c.shift, mode, residual, c.split if split else None, xs=xs, skip_w=skip_w)
         assert xs is None and skip_w is None, route
         if route == "wino_conv3d_":
-            return _lib.wino_conv3d_(x, c.u, c.shift, mode, residual)
+            return _lib.wino_conv3d_(x, c.u, c.shift, mode, residual, direct=c.direct)
         return _lib.channel_shift_act_(F.conv3d(x, c.w, None, 1, 1), c.shift, mode, residual)
 
     def _folded_skip(self, x, h, r: "_Res"):
