@@ -219,6 +219,17 @@ def _require_cl3d_f32(x: torch.Tensor, who: str):
         raise Sp3dError(f"{who}: float32 channels_last_3d activations expected")
 
 
+def _result_cl3d(out: Optional[torch.Tensor], B: int, Cc: int, X: int, Y: int, Z: int, x: torch.Tensor, who: str) -> torch.Tensor:
+    """the (B,C,X,Y,Z) channels_last_3d fp32 result of an entry: a fresh uninitialised tensor, or the caller's ``out`` (a
+    view of a larger buffer, say) once it is that shape, type and layout on x's device - the kernels see only its pointer"""
+    if out is None:
+        return _empty_cl3d(B, Cc, X, Y, Z, x.device)
+    _require_cl3d_f32(out, who)
+    if out.device != x.device or tuple(out.shape) != (B, Cc, X, Y, Z):
+        raise Sp3dError(f"{who}: out must be ({B}, {Cc}, {X}, {Y}, {Z}) on {x.device}, got {tuple(out.shape)} on {out.device}")
+    return out
+
+
 def _as_cl3d(t: torch.Tensor) -> torch.Tensor:
     """a residual / skip operand as the kernels read it, dense channels_last_3d like the result it is added to; copies
     only when it is not that already (.contiguous returns its argument otherwise, so one condition covers every case)"""
@@ -911,9 +922,10 @@ def _require_skip(xs: torch.Tensor, skip_w: torch.Tensor, x: torch.Tensor, CS: i
 
 def conv3_split_(x: torch.Tensor, W3: torch.Tensor, shift: torch.Tensor, mode: int,
                  residual: Optional[torch.Tensor] = None, *, xs: Optional[torch.Tensor] = None,
-                 skip_w: Optional[torch.Tensor] = None) -> torch.Tensor:
+                 skip_w: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """3x3x3 stride-1 'same' conv of channels_last_3d x with the fused epilogue, direct (implicit GEMM) on the bf16 matrix
-    pipe with exact three-piece splits; W3 = conv_weights_split(w).  Returns the channels_last_3d result (B,O,X,Y,Z).
+    pipe with exact three-piece splits; W3 = conv_weights_split(w).  Returns the channels_last_3d result (B,O,X,Y,Z), written
+    into ``out`` when given.
     (Round 3's chained form - split activations handed from layer to layer - measured no gain and was removed in round 4.)
     With xs (B,16,X,Y,Z) and skip_w = conv_weights_split of the (32,16,1,1,1) skip weight: relu(conv3(x) + skip_w . xs + shift)
     in the same kernel (sp3d_conv3_split_skip; mode must be 1 and residual None - the projection is the residual)."""
@@ -923,7 +935,7 @@ def conv3_split_(x: torch.Tensor, W3: torch.Tensor, shift: torch.Tensor, mode: i
     _require_cl3d_f32(x, "conv3_split_")
     O = int(W3.shape[3])
     dev = x.device
-    y = _empty_cl3d(B, O, X, Y, Z, dev)
+    y = _result_cl3d(out, B, O, X, Y, Z, x, "conv3_split_")
     if xs is not None or skip_w is not None:
         if xs is None or skip_w is None or int(mode) != 1 or residual is not None:
             raise Sp3dError("conv3_split_: the folded skip takes xs AND skip_w, mode 1 and no residual")
@@ -970,12 +982,7 @@ def conv3_split128_(x: torch.Tensor, W3: torch.Tensor, shift: torch.Tensor, mode
     if W3.device != x.device or W3.dtype != torch.bfloat16 or not W3.is_contiguous() or tuple(W3.shape) != (27, Cc // 8, O // 32, 768):
         raise Sp3dError(f"conv3_split128_: W3 must be conv_weights_split24 of the ({O}, {Cc}, 3, 3, 3) weight on {x.device}; got "
                         f"{tuple(W3.shape)}, {W3.dtype}, {W3.device}, contiguous={W3.is_contiguous()}")
-    if out is None:
-        out = _empty_cl3d(B, O, X, Y, Z, x.device)
-    else:
-        _require_cl3d_f32(out, "conv3_split128_")
-        if out.device != x.device or tuple(out.shape) != (B, O, X, Y, Z):
-            raise Sp3dError(f"conv3_split128_: out must be ({B}, {O}, {X}, {Y}, {Z}) on {x.device}, got {tuple(out.shape)} on {out.device}")
+    out = _result_cl3d(out, B, O, X, Y, Z, x, "conv3_split128_")
     if residual is not None:
         residual = _as_cl3d(residual)
     check(lib.sp3d_conv3_split(x.data_ptr(), W3.data_ptr(), out.data_ptr(), shift.data_ptr(), _opt(residual), int(mode),
@@ -984,14 +991,15 @@ def conv3_split128_(x: torch.Tensor, W3: torch.Tensor, shift: torch.Tensor, mode
 
 
 def wino_conv3d_(x: torch.Tensor, U: torch.Tensor, shift: torch.Tensor, mode: int,
-                 residual: Optional[torch.Tensor] = None, *, direct: Optional[torch.Tensor] = None) -> torch.Tensor:
+                 residual: Optional[torch.Tensor] = None, *, direct: Optional[torch.Tensor] = None,
+                 out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """The entry of the quarter-resolution tier: 3x3x3 stride-1 'same' conv of channels-last x (B,C,X,Y,Z as
     torch.channels_last_3d) fused with the layer epilogue; returns a channels_last_3d tensor (B,O,X,Y,Z).
     With ``direct`` (conv_weights_split24(w)), (C, O) = (64 | 128, 128), a grid
     quarter_direct_covers and SP3D_QUARTER_DIRECT not 0: ONE launch, the direct convolution on the bf16 matrix pipe with
     exact three-piece splits (conv3_split128_: sp3d_conv3_split with O = 128).  Otherwise the fallback form, bit for bit what it always was: Winograd
     F(2,3) with pre-transformed weights U (64,C,O) in three launches - input transform, the library's batched fp32 GEMM,
-    output transform + epilogue."""
+    output transform + epilogue.  Either form writes the result into ``out`` when given."""
     lib = load()
     _require_cuda(x, "x")
     B, Cc, X, Y, Z = (int(v) for v in x.shape)
@@ -1000,12 +1008,12 @@ def wino_conv3d_(x: torch.Tensor, U: torch.Tensor, shift: torch.Tensor, mode: in
     if residual is not None:
         residual = _as_cl3d(residual)
     if direct is not None and quarter_direct_enabled() and quarter_direct_covers(B, Cc, O, X, Y, Z):
-        return conv3_split128_(x, direct, shift, mode, residual)
+        return conv3_split128_(x, direct, shift, mode, residual, out=out)
+    y = _result_cl3d(out, B, O, X, Y, Z, x, "wino_conv3d_")
     T = B * ((X + 1) // 2) * ((Y + 1) // 2) * ((Z + 1) // 2)
     V = torch.empty((64, T, Cc), dtype=torch.float32, device=x.device)
     check(lib.sp3d_wino_input(x.data_ptr(), V.data_ptr(), B, X, Y, Z, Cc, _stream(x.device)), "sp3d_wino_input")
     M = torch.bmm(V, U)         # the 64 products: the library's fp32 batched GEMM (an own split-bf16 GEMM was not faster: round 3)
-    y = _empty_cl3d(B, O, X, Y, Z, x.device)
     check(lib.sp3d_wino_output(M.data_ptr(), y.data_ptr(), shift.data_ptr(), _opt(residual), int(mode), B, X, Y, Z, O,
                                _stream(x.device)), "sp3d_wino_output")
     return y
@@ -1013,17 +1021,19 @@ def wino_conv3d_(x: torch.Tensor, U: torch.Tensor, shift: torch.Tensor, mode: in
 
 def wino_fused_conv3d_(x: torch.Tensor, U: torch.Tensor, shift: torch.Tensor, mode: int,
                        residual: Optional[torch.Tensor] = None, U3: Optional[torch.Tensor] = None, *,
-                       xs: Optional[torch.Tensor] = None, skip_w: Optional[torch.Tensor] = None) -> torch.Tensor:
+                       xs: Optional[torch.Tensor] = None, skip_w: Optional[torch.Tensor] = None,
+                       out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """one-launch Winograd 3x3x3 conv (C = 16 | 32 -> O = 32; with U3 also C = 32 | 64 -> O = 64) of channels_last_3d x
     with the fused epilogue; with U3 (wino_weights_split(U, 8 | 16)) the products run as exact three-piece bf16 splits
     on the bf16 matrix pipe.  With U3, xs (B,32,X,Y,Z) and skip_w = wino_weights_split of the (1,32,64) skip weight, chunk 16
-    (C = O = 64): relu(conv3(x) + skip_w . xs + shift) in the same kernel (sp3d_wino_fused_split64_skip; mode 1, no residual)."""
+    (C = O = 64): relu(conv3(x) + skip_w . xs + shift) in the same kernel (sp3d_wino_fused_split64_skip; mode 1, no residual).
+    The result is written into ``out`` when given."""
     lib = load()
     _require_cuda(x, "x")
     B, Cc, X, Y, Z = (int(v) for v in x.shape)
     _require_cl3d_f32(x, "wino_fused_conv3d_")
     O = int(U.shape[2])
-    y = _empty_cl3d(B, O, X, Y, Z, x.device)
+    y = _result_cl3d(out, B, O, X, Y, Z, x, "wino_fused_conv3d_")
     if xs is not None or skip_w is not None:
         if xs is None or skip_w is None or U3 is None or int(mode) != 1 or residual is not None:
             raise Sp3dError("wino_fused_conv3d_: the folded skip takes U3, xs AND skip_w, mode 1 and no residual")
@@ -1071,16 +1081,17 @@ def upconv_fused_covers(Cc: int, O: int, head: bool) -> bool:
 
 
 def upsample2x_(x: torch.Tensor, w_gemm: torch.Tensor, shift: torch.Tensor, skip: torch.Tensor,
-                w_split: Optional[torch.Tensor] = None) -> torch.Tensor:
+                w_split: Optional[torch.Tensor] = None, *, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """ConvTranspose3d(k=2,s=2) + shift + ReLU + skip on channels_last_3d activations.  With w_split
     (upconv_weights_split(w_gemm)) and a shape upconv_fused_covers: one kernel, sp3d_upconv2x_fused.  Otherwise: one rocBLAS
-    GEMM on the (voxels, Cin) view with w_gemm (Cin, 8*O) [columns (i,j,k,o)] + sp3d_upsample2x_scatter."""
+    GEMM on the (voxels, Cin) view with w_gemm (Cin, 8*O) [columns (i,j,k,o)] + sp3d_upsample2x_scatter.  The (B,O,2X,2Y,2Z)
+    result is written into ``out`` when given."""
     lib = load()
     _require_cuda(x, "x")
     B, Cc, X, Y, Z = (int(v) for v in x.shape)
     _require_cl3d_f32(x, "upsample2x_")
     O = int(w_gemm.shape[1]) // 8
-    out = _empty_cl3d(B, O, 2 * X, 2 * Y, 2 * Z, x.device)
+    out = _result_cl3d(out, B, O, 2 * X, 2 * Y, 2 * Z, x, "upsample2x_")
     skip = _as_cl3d(skip)
     if w_split is not None and upconv_fused_covers(Cc, O, False):
         _require_upconv_split(w_split, Cc, O, x)
@@ -1094,10 +1105,11 @@ def upsample2x_(x: torch.Tensor, w_gemm: torch.Tensor, shift: torch.Tensor, skip
 
 
 def upsample2x_head_(x: torch.Tensor, w_gemm: torch.Tensor, shift: torch.Tensor, skip: torch.Tensor, w_out: torch.Tensor,
-                     b_out: torch.Tensor, w_split: Optional[torch.Tensor] = None) -> torch.Tensor:
+                     b_out: torch.Tensor, w_split: Optional[torch.Tensor] = None, *,
+                     out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """upsample2x_ fused with the 1x1x1 output conv that is its only consumer: returns (B,J,2X,2Y,2Z) as a permuted view
     of a (B,2X,2Y,2Z,J) tensor (for J = 1 that is also the dense NCDHW tensor).  With w_split (upconv_weights_split(w_gemm))
-    and a shape upconv_fused_covers: one kernel, sp3d_upconv2x_fused."""
+    and a shape upconv_fused_covers: one kernel, sp3d_upconv2x_fused.  The result is written into ``out`` when given."""
     lib = load()
     _require_cuda(x, "x")
     B, Cc, X, Y, Z = (int(v) for v in x.shape)
@@ -1106,7 +1118,7 @@ def upsample2x_head_(x: torch.Tensor, w_gemm: torch.Tensor, shift: torch.Tensor,
     J = int(w_out.shape[0])
     skip = _as_cl3d(skip)
     wo = w_out.reshape(J, O).contiguous().float()
-    head = _empty_cl3d(B, J, 2 * X, 2 * Y, 2 * Z, x.device)
+    head = _result_cl3d(out, B, J, 2 * X, 2 * Y, 2 * Z, x, "upsample2x_head_")
     if w_split is not None and J <= 32 and upconv_fused_covers(Cc, O, True):
         _require_upconv_split(w_split, Cc, O, x)
         bo = None if b_out is None else b_out.contiguous().float()
