@@ -111,6 +111,11 @@ class Sp3dError(RuntimeError):
     pass
 
 
+def env_switch(name: str, default: bool) -> bool:
+    """an on/off environment variable, read at every call: unset -> ``default``; "0" and "" -> off; anything else -> on"""
+    return os.environ.get(name, "1" if default else "0") not in ("0", "")
+
+
 def shared_gpu() -> bool:
     """SP3D_SHARED_GPU=1 (or, when the variable is unset and NO *_VISIBLE_DEVICES variable narrows what this process sees,
     more local ranks than GPUs): this process is not alone on its GPU (another process, or a second stream of its own, may run
@@ -906,7 +911,7 @@ def conv_weights_split24(w: torch.Tensor) -> torch.Tensor:
 
 def skip_fold_enabled() -> bool:
     """SP3D_FOLD_SKIP=0 keeps the 1x1x1 skip projections of the plan's residual blocks a library GEMM + residual epilogue"""
-    return os.environ.get("SP3D_FOLD_SKIP", "1") not in ("0", "")
+    return env_switch("SP3D_FOLD_SKIP", True)
 
 
 def _require_skip(xs: torch.Tensor, skip_w: torch.Tensor, x: torch.Tensor, CS: int, numel: int, who: str):
@@ -953,11 +958,11 @@ def conv3_split_(x: torch.Tensor, W3: torch.Tensor, shift: torch.Tensor, mode: i
 
 def quarter_direct_enabled() -> bool:
     """SP3D_QUARTER_DIRECT=0 keeps the quarter-resolution 3x3x3 layers on the three-launch Winograd form"""
-    return os.environ.get("SP3D_QUARTER_DIRECT", "1") not in ("0", "")
+    return env_switch("SP3D_QUARTER_DIRECT", True)
 
 
 def quarter_direct_covers(B: int, C: int, O: int, X: int, Y: int, Z: int) -> bool:
-    """the layers wino_conv3d_ gives to the direct kernel (conv3_split128_) when it has their records: the widths the
+    """the layers v2v_net.conv3_route gives to the direct kernel (conv3_split128_): the widths the
     kernel is built for, on grids its 5x5x5 output blocks tile without remainder, up to 64 blocks = 256 workgroups, one per
     CU of an MI355X: 20x20x5 at batch 1..4 (the headline root net; 42.3 against 56.9 us per layer at batch 4, 29.2 against
     36.6 at batch 1).  Measured and left to the three launches (profiles/r15_quarter_direct_shapes.json): 40x40x10 at batch
@@ -991,15 +996,10 @@ def conv3_split128_(x: torch.Tensor, W3: torch.Tensor, shift: torch.Tensor, mode
 
 
 def wino_conv3d_(x: torch.Tensor, U: torch.Tensor, shift: torch.Tensor, mode: int,
-                 residual: Optional[torch.Tensor] = None, *, direct: Optional[torch.Tensor] = None,
-                 out: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """The entry of the quarter-resolution tier: 3x3x3 stride-1 'same' conv of channels-last x (B,C,X,Y,Z as
-    torch.channels_last_3d) fused with the layer epilogue; returns a channels_last_3d tensor (B,O,X,Y,Z).
-    With ``direct`` (conv_weights_split24(w)), (C, O) = (64 | 128, 128), a grid
-    quarter_direct_covers and SP3D_QUARTER_DIRECT not 0: ONE launch, the direct convolution on the bf16 matrix pipe with
-    exact three-piece splits (conv3_split128_: sp3d_conv3_split with O = 128).  Otherwise the fallback form, bit for bit what it always was: Winograd
-    F(2,3) with pre-transformed weights U (64,C,O) in three launches - input transform, the library's batched fp32 GEMM,
-    output transform + epilogue.  Either form writes the result into ``out`` when given."""
+                 residual: Optional[torch.Tensor] = None, *, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """3x3x3 stride-1 'same' conv of channels-last x (B,C,X,Y,Z as torch.channels_last_3d) fused with the layer epilogue:
+    Winograd F(2,3) with pre-transformed weights U (64,C,O) in three launches - input transform, the library's batched fp32
+    GEMM, output transform + epilogue.  Returns a channels_last_3d tensor (B,O,X,Y,Z), written into ``out`` when given."""
     lib = load()
     _require_cuda(x, "x")
     B, Cc, X, Y, Z = (int(v) for v in x.shape)
@@ -1007,8 +1007,6 @@ def wino_conv3d_(x: torch.Tensor, U: torch.Tensor, shift: torch.Tensor, mode: in
     O = int(U.shape[2])
     if residual is not None:
         residual = _as_cl3d(residual)
-    if direct is not None and quarter_direct_enabled() and quarter_direct_covers(B, Cc, O, X, Y, Z):
-        return conv3_split128_(x, direct, shift, mode, residual, out=out)
     y = _result_cl3d(out, B, O, X, Y, Z, x, "wino_conv3d_")
     T = B * ((X + 1) // 2) * ((Y + 1) // 2) * ((Z + 1) // 2)
     V = torch.empty((64, T, Cc), dtype=torch.float32, device=x.device)
@@ -1075,9 +1073,7 @@ def _require_upconv_split(w_split: torch.Tensor, Cc: int, O: int, x: torch.Tenso
 
 def upconv_fused_covers(Cc: int, O: int, head: bool) -> bool:
     """the shapes sp3d_upconv2x_fused has a kernel for; SP3D_FUSE_UPCONV=0 sends every shape down the GEMM + scatter path"""
-    if os.environ.get("SP3D_FUSE_UPCONV", "1") in ("0", ""):
-        return False
-    return (Cc, O, bool(head)) in ((64, 32, True), (128, 64, False))
+    return env_switch("SP3D_FUSE_UPCONV", True) and (Cc, O, bool(head)) in ((64, 32, True), (128, 64, False))
 
 
 def upsample2x_(x: torch.Tensor, w_gemm: torch.Tensor, shift: torch.Tensor, skip: torch.Tensor,

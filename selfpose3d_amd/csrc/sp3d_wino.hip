@@ -1,8 +1,8 @@
 // sp3d_wino.hip - input / output transforms of Winograd F(2x2x2, 3x3x3) for the low-resolution 3x3x3 convolutions
 // of the V2V nets in inference (reference: the `Res3DBlock`s of lib/models/v2v_net.py:23-45 at 1/4 resolution).
 // The FALLBACK FORM of that tier since sp3d_conv3_quarter.hip: grids of up to 64 whole 5x5x5 blocks (the headline 20x20x5 at
-// batch 4) run as one direct kernel per layer; _lib.wino_conv3d_ keeps these three launches for every other grid, for widths other
-// than (64 | 128) -> 128 and under SP3D_QUARTER_DIRECT=0.
+// batch 4) run as one direct kernel per layer (route "conv3_split128_" of v2v_net.conv3_route); the route "wino_conv3d_", these
+// three launches behind _lib.wino_conv3d_, is what every other grid, widths other than (64 | 128) -> 128 and SP3D_QUARTER_DIRECT=0 get.
 //
 // At 1/4 resolution (20x20x5 voxels, 128 channels, batch 4) a 3x3x3 convolution is a GEMM with only 8 000 rows;
 // MIOpen's implicit-GEMM kernels reach 60 TFLOP/s there (112 us per layer).  Winograd needs 64 multiplies per 8 outputs

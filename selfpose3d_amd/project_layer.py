@@ -13,7 +13,6 @@ tensors must live on the GPU and libsp3d.so must be built, otherwise this raises
 from __future__ import annotations
 
 import contextlib
-import os
 from typing import Sequence
 
 import numpy as np
@@ -298,21 +297,21 @@ class ProjectLayer(nn.Module):
         self._cam_dev = None
         self._static_cam = None       # see static_camera_table()
         # gradient scatter in 64-bit fixed point (bit-identical run to run) instead of fp32 atomics; SP3D_BWD_DETERMINISTIC=1
-        self.deterministic_backward = os.environ.get("SP3D_BWD_DETERMINISTIC", "0") not in ("", "0")
+        self.deterministic_backward = _lib.env_switch("SP3D_BWD_DETERMINISTIC", False)
         # opt-in (SP3D_ONE_CHANNEL=1 / ``one_channel = True``): a (B,1,h,w) heat-map list that is one channel of a wider
         # tensor goes through the one-channel kernel, read in place (one_channel_source), instead of slice copy + re-tile +
         # packed kernel.  Same bits either way; off until tools/bench_roothm.py has recorded that it is faster
-        self.one_channel = os.environ.get("SP3D_ONE_CHANNEL", "0") not in ("", "0")
+        self.one_channel = _lib.env_switch("SP3D_ONE_CHANNEL", False)
         # opt-in (SP3D_ONE_CHANNEL_GRAD=1 / ``one_channel_grad = True``), independent of ``one_channel``: the same kind of list
         # WITH a heat-map gradient trains through the one-channel pair (_lib.unproject_one_fwd_train / unproject_one_bwd)
         # instead of slice copy + re-tile + packed training forward + 4-channel scatter.  Same cubes, same deterministic
         # gradient bits; off until tools/bench_roothm_grad.py has recorded that it is faster
-        self.one_channel_grad = os.environ.get("SP3D_ONE_CHANNEL_GRAD", "0") not in ("", "0")
+        self.one_channel_grad = _lib.env_switch("SP3D_ONE_CHANNEL_GRAD", False)
         # opt-in (SP3D_WIDE_GRAD=1 / ``wide_grad = True``): 17..32 joints (fp32 storage) WITH a heat-map gradient train through
         # the channels-last pair - training forward with a two-plane pass mask, wide packed scatter (fp32 or deterministic) -
         # instead of planar forward + planar backward.  Same cubes as the no-grad forward; off until tools/bench_wide_grad.py
         # has recorded that it is faster in every leg
-        self.wide_grad = os.environ.get("SP3D_WIDE_GRAD", "0") not in ("", "0")
+        self.wide_grad = _lib.env_switch("SP3D_WIDE_GRAD", False)
 
     @contextlib.contextmanager
     def static_camera_table(self, table: torch.Tensor):

@@ -62,16 +62,17 @@ def pad_cin(x, w):
     return x, w
 
 
-def conv3_route(cin, cout, shape, winograd=True, wino_split=True, direct_conv=True) -> str:
+def conv3_route(cin, cout, shape, winograd=True, wino_split=True, direct_conv=True, quarter_direct=True) -> str:
     """Which kernel a 3x3x3 layer (cin -> cout) of the plan takes on a channels-last input of ``shape`` = (B, X, Y, Z)
     with its weights on the GPU: the name of the _lib entry point, or "library" (the library's conv + channel_shift_act_).
     Wide layers on small grids (the 1/4- and 1/2-resolution blocks: a GEMM with few rows, where MIOpen's implicit-GEMM
     kernels drop to ~60 TFLOP/s) go through Winograd F(2x2x2,3x3x3): HIP input/output transforms around one batched
     rocBLAS GEMM, 2.1x faster at (4,128,20,20,5) and 1.2x at (4,64,40,40,10) (tools/exp_wino.py); the rule keeps the
     transformed tensor (64*T*C floats) within reach of the Infinity Cache, beyond which the transforms eat the gain.
-    "wino_conv3d_" names the ENTRY of the quarter-resolution tier, not a form: given the layer's 24-byte weight records it
-    launches the direct kernel conv3_split128_ on the grids _lib.quarter_direct_covers (41 instead of 49.5 us per 128 -> 128
-    layer at (4,128,20,20,5)) and keeps the three Winograd launches, the fallback form, everywhere else."""
+    Each form of the quarter-resolution tier has its name: "conv3_split128_", the direct kernel, with ``quarter_direct`` on the
+    grids _lib.quarter_direct_covers (41 instead of 49.5 us per 128 -> 128 layer at (4,128,20,20,5)), and
+    "wino_conv3d_", the three Winograd launches, everywhere else.  Reads no environment: the switches are the caller's."""
+    from . import _lib
     B, X, Y, Z = shape
     full = cout == 32 and cin in (16, 32)                  # the full-resolution layers
     if not winograd or not (cin >= 64 or full or (cout == 64 and cin == 32)):
@@ -82,7 +83,7 @@ def conv3_route(cin, cout, shape, winograd=True, wino_split=True, direct_conv=Tr
         return "wino_fused_conv3d_"
     T = B * ((X + 1) // 2) * ((Y + 1) // 2) * ((Z + 1) // 2)
     if cin >= 128 or (cin >= 64 and 64 * T * cin * 4 <= 160e6):
-        return "wino_conv3d_"
+        return "conv3_split128_" if quarter_direct and _lib.quarter_direct_covers(B, cin, cout, X, Y, Z) else "wino_conv3d_"
     if full and wino_split and direct_conv:
         # implicit GEMM with exact three-piece bf16 splits: no Winograd transforms (which made the fused kernel
         # VALU-bound); 155 vs 163 us (ReLU), 159 vs 182 us (residual) at (4,32,80,80,20)
@@ -272,7 +273,8 @@ class _Conv(NamedTuple):
     shift: torch.Tensor                        # what is left of bias and BatchNorm, per output channel
     u: Optional[torch.Tensor] = None           # Winograd-domain weights (_lib.wino_weights)
     split: Optional[torch.Tensor] = None       # ... in three bf16 pieces (_lib.wino_weights_split): the fused kernels
-    direct: Optional[torch.Tensor] = None      # w in three bf16 pieces: conv3_split_ (_lib.conv_weights_split), wino_conv3d_(direct=) (_lib.conv_weights_split24)
+    direct: Optional[torch.Tensor] = None      # w in three bf16 pieces, 48-byte records: conv3_split_ (_lib.conv_weights_split)
+    direct24: Optional[torch.Tensor] = None    # ... in 24-byte blocks: conv3_split128_ (_lib.conv_weights_split24)
 
 
 class _Res(NamedTuple):
@@ -340,26 +342,26 @@ class _FoldedV2V:
         return w.contiguous(memory_format=fmt), ((b - bn.running_mean) * s + bn.bias).contiguous()
 
     @staticmethod
+    def _conv3_routes(cin, cout):
+        """the routes of a cin -> cout layer: either side of the Infinity-Cache bound, a grid of whole 5x5x5 blocks, all switches"""
+        return {conv3_route(cin, cout, s, True, ws, dc) for s in ((1, 2, 2, 2), (1 << 20, 2, 2, 2), (1, 5, 5, 5))
+                for ws in (True, False) for dc in (True, False)}
+
+    @staticmethod
     def _conv3_record(w, shift):
-        """a folded 3x3x3 conv with the weight forms of every route conv3_route can give it (weights on the GPU), over all
-        input sizes (either side of the Infinity-Cache bound) and settings of wino_split / direct_conv"""
+        """a folded 3x3x3 conv with the weight forms of every route conv3_route can give it (weights on the GPU)"""
         from . import _lib
         cout, cin = int(w.shape[0]), int(w.shape[1])
-        routes = {conv3_route(cin, cout, (b, 2, 2, 2), True, ws, dc) for b in (1, 1 << 20) for ws in (True, False) for dc in (True, False)}
+        routes = _FoldedV2V._conv3_routes(cin, cout)
         if not w.is_cuda or routes == {"library"}:
             return _Conv(w, shift)
         u = _lib.wino_weights(w)
         # layers of the fused kernels: weights split for the bf16 matrix pipe (lane quarters for 64 output channels)
         split = _lib.wino_weights_split(u, 16 if cout == 64 else 8) if "wino_fused_conv3d_" in routes else None
-        # full-resolution layers (16 | 32 -> 32): direct convolution on the bf16 matrix pipe (three exact pieces)
-        # ... and the quarter-resolution layers (64 | 128 -> 128), which wino_conv3d_ runs as one direct kernel where it pays
-        if "conv3_split_" in routes:
-            direct = _lib.conv_weights_split(w)
-        elif "wino_conv3d_" in routes and cout == 128 and cin in (64, 128):
-            direct = _lib.conv_weights_split24(w)
-        else:
-            direct = None
-        return _Conv(w, shift, u, split, direct)
+        # full-resolution (16 | 32 -> 32) and quarter-resolution layers (64 | 128 -> 128): direct convolution, three exact pieces
+        direct = _lib.conv_weights_split(w) if "conv3_split_" in routes else None
+        direct24 = _lib.conv_weights_split24(w) if "conv3_split128_" in routes else None
+        return _Conv(w, shift, u, split, direct, direct24)
 
     def _build(self):
         from . import _lib
@@ -393,11 +395,13 @@ class _FoldedV2V:
         self.layers, self.spectra, self.xpad = layers, {}, {}
 
     def _route(self, x, c: "_Conv") -> str:
+        from . import _lib
         n = self.net
         if c.u is None or not is_cl(x):
             return "library"
         return conv3_route(int(c.w.shape[1]), int(c.w.shape[0]), (x.shape[0],) + tuple(x.shape[2:]), n.winograd,
-                           getattr(n, "wino_split", True), getattr(n, "direct_conv", True))
+                           getattr(n, "wino_split", True), getattr(n, "direct_conv", True),
+                           quarter_direct=c.direct24 is not None and _lib.quarter_direct_enabled())
 
     def _conv3(self, x, c: "_Conv", mode, residual=None, xs=None, skip_w=None):
         """3x3x3 conv + fused epilogue on the route conv3_route names (weights on the GPU and channels-last x); xs, skip_w:
@@ -410,8 +414,10 @@ class _FoldedV2V:
         if route == "wino_fused_conv3d_":
             return _lib.wino_fused_conv3d_(x, c.u, c.shift, mode, residual, c.split if split else None, xs=xs, skip_w=skip_w)
         assert xs is None and skip_w is None, route
+        if route == "conv3_split128_":
+            return _lib.conv3_split128_(x, c.direct24, c.shift, mode, residual)
         if route == "wino_conv3d_":
-            return _lib.wino_conv3d_(x, c.u, c.shift, mode, residual, direct=c.direct)
+            return _lib.wino_conv3d_(x, c.u, c.shift, mode, residual)
         return _lib.channel_shift_act_(F.conv3d(x, c.w, None, 1, 1), c.shift, mode, residual)
 
     def _folded_skip(self, x, h, r: "_Res"):
@@ -455,10 +461,10 @@ class _FoldedV2V:
 
     @staticmethod
     def _tunable():
-        import os
+        from . import _lib
         on = _FoldedV2V._tune_gemms
         if on is None:
-            on = os.environ.get("SP3D_TUNE_GEMM", "0") not in ("0", "")
+            on = _lib.env_switch("SP3D_TUNE_GEMM", False)
         return getattr(torch.cuda, "tunable", None) if on else None
 
     def _run_tuned(self, x):
@@ -595,10 +601,9 @@ class _FoldedV2V:
         """channel contraction of the opening conv on the kz-slowest spectrum: with the weight spectrum's y transform rebuilt
         per bin (17.7 MB of table instead of 223 MB of spectrum on the root grid) when the kernel covers the shape"""
         from . import _lib
-        import os
         # measured (profiles/r06_contract_ty.md): 12.6x fewer weight bytes, but no faster in the step (1.4512 vs 1.4507 ms) - the
         # rebuilt spectrum costs the VALU what the stream cost the HBM.  Opt-in: V2VNet.contract_ty = True / SP3D_CONTRACT_TY=1.
-        on = getattr(self.net, "contract_ty", os.environ.get("SP3D_CONTRACT_TY", "0") not in ("0", ""))
+        on = getattr(self.net, "contract_ty", _lib.env_switch("SP3D_CONTRACT_TY", False))
         if on and int(w0.shape[2]) == 7 and int(w0.shape[1]) <= 16 and 4 * S[1] <= 384:
             T, tw = self._weights_ty(w0, S)
             return _lib.freq_contract_ty(Xs, T, tw)
@@ -796,8 +801,8 @@ class V2VNet(nn.Module):
         """SZ when the next inference forward can start from the cubes' z-spectrum (``TiledZSpectrum``: the unprojection
         fused with the opening conv's z pass, root grid), else None.  ``fuse_zdft`` (default on; SP3D_FUSE_ZDFT=0 turns it
         off for A/B) and the conditions of the direct z-DFT form + 88 x 88 planes + a float32 inference plan."""
-        import os
-        if not getattr(self, "fuse_zdft", os.environ.get("SP3D_FUSE_ZDFT", "1") not in ("0", "")):
+        from . import _lib
+        if not getattr(self, "fuse_zdft", _lib.env_switch("SP3D_FUSE_ZDFT", True)):
             return None
         if self.training or torch.is_grad_enabled() or not self.fused_inference or not self.wants_channels_last_cubes(X, Y, Z):
             return None

@@ -1,6 +1,6 @@
 """conv3_split128_kernel (csrc/sp3d_conv3_quarter.hip), the direct 3x3x3 convolution of the quarter-resolution layers, against
 float64 F.conv3d + the epilogue.  Every output buffer is NaN before the launch, so a row the kernel does not write fails.
-Metric and bound: max|got - f64| / max(1, max|f64|) <= 2.0e-6, the bound of the wino_conv3d_ entry these layers run behind
+Metric and bound: max|got - f64| / max(1, max|f64|) <= 2.0e-6, the bound of the conv3_split128_ entry in the plan
 (tests/test_gpu_v2v_plan_f64.py BOUNDS); with two samples of different magnitude it is taken per sample.
 Measured on the MI355X (profiles/r15_quarter_direct_errors.json)."""
 import functools
@@ -91,9 +91,16 @@ def test_direct_and_three_launch_forms_agree():
     assert metric(yd, yw.double()) <= ed + ew
 
 
-def test_wino_conv3d_takes_the_direct_kernel_where_it_covers(monkeypatch):
-    """wino_conv3d_(direct=) IS conv3_split128_ on a grid of whole 5x5x5 blocks (bit for bit), stays the three launches on a
-    ragged grid, for other widths and without the records"""
+def bare_plan():
+    """a plan object with the default switches and no layers: _conv3 dispatches a record made by _conv3_record"""
+    import types
+    from selfpose3d_amd.v2v_net import _FoldedV2V
+    return _FoldedV2V(types.SimpleNamespace(winograd=True, wino_split=True, direct_conv=True))
+
+
+def test_plan_takes_the_direct_kernel_where_it_covers(monkeypatch):
+    """the plan's dispatch (_conv3 on a record of _conv3_record) IS conv3_split128_ on a grid of whole 5x5x5 blocks (bit for
+    bit) and stays the three launches on a ragged grid; each entry runs its own form only"""
     from selfpose3d_amd import _lib
     monkeypatch.delenv("SP3D_QUARTER_DIRECT", raising=False)
     g = torch.Generator(device="cpu").manual_seed(5)
@@ -101,19 +108,28 @@ def test_wino_conv3d_takes_the_direct_kernel_where_it_covers(monkeypatch):
     w = (torch.randn((128, 64, 3, 3, 3), generator=g) * 0.05).cuda()
     shift = torch.randn((128,), generator=g).cuda()
     U, rec = _lib.wino_weights(w), _lib.conv_weights_split24(w)
+    plan = bare_plan()
+    c = plan._conv3_record(w, shift)
+    assert torch.equal(c.u, U) and torch.equal(c.direct24, rec) and c.direct is None
     x = torch.randn((1, 64, 10, 5, 5), generator=g).cuda().contiguous(memory_format=cl)
     direct, three = _lib.conv3_split128_(x, rec, shift, 1), _lib.wino_conv3d_(x, U, shift, 1)
     assert not torch.equal(direct, three)                # the comparison below can tell the two forms apart
-    assert torch.equal(_lib.wino_conv3d_(x, U, shift, 1, direct=rec), direct)
+    assert plan._route(x, c) == "conv3_split128_"
+    assert torch.equal(plan._conv3(x, c, 1), direct)
     xr = torch.randn((1, 64, 6, 5, 5), generator=g).cuda().contiguous(memory_format=cl)
-    assert torch.equal(_lib.wino_conv3d_(xr, U, shift, 1, direct=rec), _lib.wino_conv3d_(xr, U, shift, 1))
+    assert plan._route(xr, c) == "wino_conv3d_"
+    assert torch.equal(plan._conv3(xr, c, 1), _lib.wino_conv3d_(xr, U, shift, 1))
     assert not torch.equal(_lib.wino_conv3d_(xr, U, shift, 1), _lib.conv3_split128_(xr, rec, shift, 1))
+    # a record without the 24-byte form stays on the three launches
+    assert torch.equal(plan._conv3(x, c._replace(direct24=None), 1), three)
     with pytest.raises(_lib.Sp3dError):
-        _lib.wino_conv3d_(x, U, shift, 1, direct=rec[:, :4].contiguous())
+        _lib.conv3_split128_(x, rec[:, :4].contiguous(), shift, 1)
+    with pytest.raises(TypeError):
+        _lib.wino_conv3d_(x, U, shift, 1, direct=rec)
 
 
 def test_switch_off_is_the_three_launch_form_bit_for_bit(monkeypatch):
-    """SP3D_QUARTER_DIRECT=0 (read at every call): wino_conv3d_ with the records gives the bits it gives without them"""
+    """SP3D_QUARTER_DIRECT=0 (read at every call): the plan's dispatch gives the bits of the three-launch entry"""
     from selfpose3d_amd import _lib
     g = torch.Generator(device="cpu").manual_seed(5)
     cl = torch.channels_last_3d
@@ -121,13 +137,15 @@ def test_switch_off_is_the_three_launch_form_bit_for_bit(monkeypatch):
     shift = torch.randn((128,), generator=g).cuda()
     x = torch.randn((2, 128, 10, 5, 5), generator=g).cuda().contiguous(memory_format=cl)
     res = torch.randn((2, 128, 10, 5, 5), generator=g).cuda().contiguous(memory_format=cl)
-    U, rec = _lib.wino_weights(w), _lib.conv_weights_split24(w)
+    plan = bare_plan()
+    c = plan._conv3_record(w, shift)
     monkeypatch.setenv("SP3D_QUARTER_DIRECT", "0")
     for m in (1, 2):
         r = res if m >= 2 else None
-        assert torch.equal(_lib.wino_conv3d_(x, U, shift, m, r, direct=rec), _lib.wino_conv3d_(x, U, shift, m, r))
+        assert torch.equal(plan._conv3(x, c, m, r), _lib.wino_conv3d_(x, c.u, shift, m, r))
     monkeypatch.delenv("SP3D_QUARTER_DIRECT")
-    assert not torch.equal(_lib.wino_conv3d_(x, U, shift, 2, res, direct=rec), _lib.wino_conv3d_(x, U, shift, 2, res))
+    assert not torch.equal(plan._conv3(x, c, 2, res), _lib.wino_conv3d_(x, c.u, shift, 2, res))
+    assert torch.equal(plan._conv3(x, c, 2, res), _lib.conv3_split128_(x, c.direct24, shift, 2, res))
 
 
 def test_plan_runs_the_six_quarter_layers_in_one_launch_each(monkeypatch):

@@ -31,7 +31,8 @@ pytestmark = pytest.mark.gpu
 # ---- census: the kernel every layer takes, from the dispatch rules of v2v_net.py --------------------------------------------
 # v2v_net.conv3_route on channels-last activations with the default switches: 16|32 -> 32 at full resolution ->
 # conv3_split_; 32|64 -> 64 (16-column split) -> wino_fused_conv3d_ (split64); 64|128 -> 128 have no split, C >= 128 or
-# 64*T*C*4 <= 160e6 at every shape below -> wino_conv3d_.  _FoldedV2V._pool: channels-last, C % 4 == 0, even sides ->
+# 64*T*C*4 <= 160e6 at every shape below -> the quarter-resolution tier: conv3_split128_ where QUARTER_FORM says so, else
+# wino_conv3d_ (the three launches, what TAIL names).  _FoldedV2V._pool: channels-last, C % 4 == 0, even sides ->
 # maxpool2x.  _FoldedV2V._up2x: 64 output channels -> upsample2x_.  _FoldedV2V._tail: the 32-channel up-sampling + 1^3
 # output conv -> upsample2x_head_.
 # (layer, kernels in call order, input channels, resolution divisor of the input)
@@ -55,14 +56,23 @@ FRONTS = {
     "zdft_cl": ("zdft_fwd_cl", "cfft2d_", "freq_contract", "cfft2d_", "zdft_inv_cl"),     # channels-last 16-channel cubes
     "rfft": ("rfft3d", "freq_contract", "irfft3d_", "crop_shift_act_cl"),               # padded planar buffer / generic
 }
-LIB_ENTRIES = ("conv3_split_", "wino_fused_conv3d_", "wino_conv3d_", "channel_shift_act_", "upsample2x_", "upsample2x_head_",
+# the form of the quarter-resolution tier (encoder_res2, mid_res, decoder_res2) per configuration, written out: the direct
+# kernel on grids of whole 5x5x5 blocks, at most 64 of them (_lib.quarter_direct_covers) - 20x20x5 at B = 1, 2 and 4 (16, 32
+# and, on the boundary of the rule, 64 blocks); the three launches at 12x12x3 and 16^3 (ragged) and at 40x40x10, B = 2 (256 blocks)
+QUARTER_LAYERS = ("encoder_res2", "mid_res", "decoder_res2")
+QUARTER_FORM = {
+    "R1_b4": "conv3_split128_", "R2_b1": "conv3_split128_", "R2_b2": "conv3_split128_", "R3_b1": "conv3_split128_",
+    "R3_b4": "conv3_split128_", "R4_b2": "wino_conv3d_", "R5_b2": "wino_conv3d_",
+    "P1_p1": "wino_conv3d_", "P1_p3": "wino_conv3d_", "P1_p8": "wino_conv3d_", "P1_p11": "wino_conv3d_",
+}
+LIB_ENTRIES = ("conv3_split_", "wino_fused_conv3d_", "wino_conv3d_", "conv3_split128_", "channel_shift_act_", "upsample2x_", "upsample2x_head_",
                "maxpool2x", "crop_shift_act_cl", "zdft_fwd_cl", "zdft_inv_cl", "freq_contract", "freq_contract_ty", "rfft3d",
                "irfft3d_", "cfft2d_", "cfft2d_88_tiled")
 
 # id: (net, grid, batch, front kind, channels of the front's input tensor, seed).  What each runs, with the input shape of
 # every layer (B, C, X, Y, Z) from TAIL (C, X/d, Y/d, Z/d):
 #   R1  V2VNet(15,1) in CuboidProposalNet, 80x80x20, B=4: fused z-spectrum front (the bench's path); conv3_split_ at
-#       80x80x20, split64 32->64 and 64->64 at 40x40x10, wino_conv3d_ 64->128 and 128->128 at 20x20x5, upsample2x_
+#       80x80x20, split64 32->64 and 64->64 at 40x40x10, conv3_split128_ 64->128 and 128->128 at 20x20x5, upsample2x_
 #       20x20x5 -> 40x40x10, head 40x40x10 -> 80x80x20 (J=1)
 #   R2  the same with fuse_zdft=False, B=1 and B=2: channels-last 16-channel cubes -> zdft_fwd_cl
 #   R3  NETWORK.ROOTNET_ROOTHM: V2VNet(1,1), cin=1, channels-last 4-channel cubes -> generic rFFT front + crop_shift_act_cl,
@@ -83,10 +93,12 @@ ROOT_CONFIGS = {
 POSE_CONFIGS = {"P1_p1": (1, 1, 711), "P1_p3": (2, 2, 712), "P1_p8": (2, 4, 713), "P1_p11": (3, 4, 714)}   # (B, K, seed)
 
 
-def expected_census(front, fc, B, cube):
+def expected_census(cid, front, fc, B, cube):
     X, Y, Z = cube
     rows = [("front", FRONTS[front], (B, fc, X, Y, Z))]
     for name, kernels, c, d in TAIL:
+        if name in QUARTER_LAYERS:
+            kernels = (QUARTER_FORM[cid],) * 2
         rows.append((name, kernels, (B, c, X // d, Y // d, Z // d)))
     return rows
 
@@ -97,11 +109,14 @@ def expected_census(front, fc, B, cube):
 #   1.6e-6), wino_conv3d_ 6.95e-7 (R3 B=4 decoder_res2; 2.6e-6), upsample2x_ 5.25e-7 (R5; 4.2e-7), head 3.05e-7 (P1 P=8;
 #   3.9e-7), whole net 2.0e-6 (P1 P=8; 2.4e-6; the R1 graph replay 1.02e-6).  Each bound is <= 3x its measured worst: a wrong
 #   tile, brick, channel scale or folded BatchNorm term is off by >= 1e-3 of the range (test_comparison_rejects_altered_outputs).
+# With the quarter-resolution forms told apart (profiles/r17_v2v_plan_f64.json): conv3_split128_ 1.17e-6 (R3 B=4 decoder_res2),
+# wino_conv3d_ 7.52e-7 (P1 P=11 mid_res).
 BOUNDS = {
     "front": 1.7e-6,
     "conv3_split_": 4.7e-6,
     "wino_fused_conv3d_": 2.3e-6,
     "wino_conv3d_": 2.0e-6,
+    "conv3_split128_": 2.0e-6,           # the bound of the other form of the same layers (tests/test_gpu_quarter_direct.py, tests/conv_sweep_cases.py)
     "upsample2x_": 1.5e-6,
     "upsample2x_head_": 9.0e-7,
 }
@@ -460,7 +475,7 @@ def test_root_net_plan_layers_vs_float64(dev, cid, monkeypatch):
     net, hms, meta, cubes = _root_setup(dev, c)
     cap, rc, _ = _capture_root(monkeypatch, net, hms, meta, dev)
     assert len(cap.calls) == 1, len(cap.calls)
-    census = [expected_census(c["front"], c["fc"], c["B"], c["cube"])]
+    census = [expected_census(cid, c["front"], c["fc"], c["B"], c["cube"])]
     ref = Referee(net.v2v_net)
     records = []
     # the fused front's referee input: the oracle's whole-volume cubes for the same heat-maps
@@ -532,7 +547,7 @@ def test_pose_net_plan_layers_vs_float64(dev, cid, monkeypatch):
     sizes = [min(8, P - s) for s in range(0, P, 8)]
     padded = [1 << (n - 1).bit_length() for n in sizes]
     assert [r[0] for r in cap.soft] == sizes and [r[2] for r in cap.soft] == sizes, (cap.soft, sizes)
-    census = [expected_census("rfft", J, m, (X, Y, Z)) for m in padded]
+    census = [expected_census(cid, "rfft", J, m, (X, Y, Z)) for m in padded]
     assert len(cap.calls) == len(sizes)
     # the padding cube's output never reaches the caller: the soft-argmax reads the first n cubes of each chunk's output
     for (n, ptr, _), layers in zip(cap.soft, cap.calls):

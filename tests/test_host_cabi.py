@@ -580,13 +580,15 @@ def test_padded_fft_input_view_is_recognised_by_address_not_by_python_attribute(
 
 
 def test_conv3_route_reproduces_the_census_of_every_configuration():
-    """v2v_net.conv3_route, a function of channels, input shape and the three switches alone, gives every 3x3x3 layer of
-    every root and pose configuration the kernel that tests/test_gpu_v2v_plan_f64.py pins on the GPU (TAIL), and the
+    """v2v_net.conv3_route, a function of channels, input shape and the four switches alone, gives every 3x3x3 layer of
+    every root and pose configuration the kernel that tests/test_gpu_v2v_plan_f64.py pins on the GPU (TAIL, with the form of
+    the quarter-resolution tier from QUARTER_FORM; TAIL itself, the three launches, with quarter_direct off), and the
     documented routes when wino_split / direct_conv are off (bench.py's fp32-matrix leg): the full-resolution layers fall
     back to the one-launch Winograd kernel, the 32 -> 64 layer to the library, and a 64 -> 64 layer to wino_conv3d_ only
-    while its transformed tensor 64 * T * 64 * 4 bytes fits the 160e6-byte Infinity-Cache bound (T <= 9765 tiles)"""
+    while its transformed tensor 64 * T * 64 * 4 bytes fits the 160e6-byte Infinity-Cache bound (T <= 9765 tiles); neither
+    switch moves the quarter-resolution tier, and winograd=False is the library whatever quarter_direct says"""
     from selfpose3d_amd.v2v_net import conv3_route
-    from tests.test_gpu_v2v_plan_f64 import POSE_CONFIGS, ROOT_CONFIGS, TAIL
+    from tests.test_gpu_v2v_plan_f64 import POSE_CONFIGS, QUARTER_FORM, QUARTER_LAYERS, ROOT_CONFIGS, TAIL
     cout = {"front_res": 32, "skip_res1": 32, "encoder_res1": 64, "skip_res2": 64, "encoder_res2": 128, "mid_res": 128,
             "decoder_res2": 128, "decoder_res1": 64}
     res = [row for row in TAIL if row[0] in cout]
@@ -607,17 +609,35 @@ def test_conv3_route_reproduces_the_census_of_every_configuration():
     assert fits["R1_b4"] and not fits["R5_b2"] and fits["P1_p1_chunk1"] and not fits["P1_p8_chunk8"]     # 8000, 32000, 4096, 32768
     n = 0
     for cid, (B, cube) in cfgs.items():
-        for name, kernels, cin, d in res:
+        for name, tail_kernels, cin, d in res:
+            kernels = (QUARTER_FORM[cid.split("_chunk")[0]],) * 2 if name in QUARTER_LAYERS else tail_kernels
             assert routes(name, cin, d, B, cube) == kernels, (cid, name)
-            assert routes(name, cin, d, B, cube, winograd=False) == ("library", "library"), (cid, name)
+            assert routes(name, cin, d, B, cube, quarter_direct=False) == tail_kernels, (cid, name)
+            for qd in (True, False):
+                assert routes(name, cin, d, B, cube, winograd=False, quarter_direct=qd) == ("library", "library"), (cid, name)
             fused = ("wino_fused_conv3d_",) * 2 if cout[name] == 32 else kernels
             assert routes(name, cin, d, B, cube, direct_conv=False) == fused, (cid, name)
             w64 = "wino_conv3d_" if fits[cid] else "library"
-            nosplit = {32: ("wino_fused_conv3d_",) * 2, 64: ("library" if cin == 32 else w64, w64), 128: ("wino_conv3d_",) * 2}
+            nosplit = {32: ("wino_fused_conv3d_",) * 2, 64: ("library" if cin == 32 else w64, w64), 128: kernels}
             assert routes(name, cin, d, B, cube, wino_split=False) == nosplit[cout[name]], (cid, name)
             assert routes(name, cin, d, B, cube, wino_split=False, direct_conv=False) == nosplit[cout[name]], (cid, name)
             n += 1
     assert n == 8 * len(cfgs) and len(cfgs) == len(ROOT_CONFIGS) + 5
+    assert set(QUARTER_FORM) == set(ROOT_CONFIGS) | set(POSE_CONFIGS) and set(QUARTER_FORM.values()) == {"conv3_split128_", "wino_conv3d_"}
+
+
+def test_env_switch_reads_the_variable_at_every_call(monkeypatch):
+    """_lib.env_switch, the one spelling of an on/off environment variable: unset is the default, "0" and "" are off,
+    anything else is on; nothing is cached"""
+    from selfpose3d_amd import _lib
+    name = "SP3D_TEST_ENV_SWITCH"
+    monkeypatch.delenv(name, raising=False)
+    assert _lib.env_switch(name, True) is True and _lib.env_switch(name, False) is False
+    for value, want in (("0", False), ("", False), ("1", True), ("off", True), ("0", False)):
+        monkeypatch.setenv(name, value)
+        assert _lib.env_switch(name, True) is want and _lib.env_switch(name, False) is want, value
+    monkeypatch.delenv(name)
+    assert _lib.env_switch(name, True) is True and _lib.env_switch(name, False) is False
 
 
 def test_three_piece_weight_splits_are_exact_and_laid_out_as_documented():

@@ -45,7 +45,7 @@ def test_entry_refuses_in_the_documented_order(lib):
 
 
 def test_routing_rule_and_switch(monkeypatch):
-    """wino_conv3d_ gives the direct kernel the two widths on grids of at most 64 whole 5x5x5 blocks; SP3D_QUARTER_DIRECT=0 none"""
+    """conv3_route gives the direct kernel the two widths on grids of at most 64 whole 5x5x5 blocks; SP3D_QUARTER_DIRECT=0 none"""
     cov = _lib.quarter_direct_covers
     assert cov(4, 128, 128, 20, 20, 5) and cov(4, 64, 128, 20, 20, 5) and cov(1, 128, 128, 20, 20, 5) and cov(1, 64, 128, 10, 10, 5)
     assert not cov(2, 128, 128, 40, 40, 10) and not cov(5, 128, 128, 20, 20, 5)          # more than one workgroup per CU
@@ -85,4 +85,10 @@ def test_plan_builds_the_records_for_the_quarter_layers_only_on_the_gpu():
     """_conv3_record on CPU weights makes no GPU forms (the library runs such a net); the widths it would add records for"""
     from selfpose3d_amd.v2v_net import _FoldedV2V
     rec = _FoldedV2V._conv3_record(torch.zeros(128, 64, 3, 3, 3), torch.zeros(128))
-    assert rec.u is None and rec.direct is None
+    assert rec.u is None and rec.direct is None and rec.direct24 is None
+    # the routes the record is built for: the probe reaches the direct kernel for the two widths it covers, and only those
+    for (o, c), want in (((128, 64), True), ((128, 128), True), ((64, 64), False), ((32, 16), False)):
+        routes = _FoldedV2V._conv3_routes(c, o)
+        assert ("conv3_split128_" in routes) == want, (o, c, routes)
+        assert ("conv3_split_" in routes) == ((o, c) == (32, 16)), (o, c, routes)
+    assert "wino_conv3d_" in _FoldedV2V._conv3_routes(64, 128)          # the fallback form keeps its weights too

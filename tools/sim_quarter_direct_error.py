@@ -10,7 +10,7 @@ alternating accumulator sets per wave) partial sums added in fp32 in their fixed
 not: the matrix instruction's internal summation order, hence the rule "emulated error <= half the bound".
 Block: x (1,128,20,20,5) >= 0 (a ReLU output of unit spread), y = relu(conv2(relu(conv1(x) + s1)) + s2 + x), weights of
 unit output spread (what tests/test_gpu_v2v_plan_f64.py::fill_far_from_identity arranges).  Metric: max|d| / max(1, max|f64|),
-bound 2.0e-6 (BOUNDS["wino_conv3d_"])."""
+bound 2.0e-6 (BOUNDS["conv3_split128_"], the same figure as the three-launch form's BOUNDS["wino_conv3d_"])."""
 import argparse
 import json
 import os
