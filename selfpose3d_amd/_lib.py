@@ -235,6 +235,21 @@ def _result_cl3d(out: Optional[torch.Tensor], B: int, Cc: int, X: int, Y: int, Z
     return out
 
 
+def _result_dense(out: Optional[torch.Tensor], shape, dtype, device, who: str, align: int = 1, cl3d: bool = False) -> torch.Tensor:
+    """the result of an entry of the opening conv: a fresh uninitialised tensor, or the caller's ``out`` (a view of a larger
+    buffer, say) once it is that shape and type on that device, dense (``cl3d``: in channels_last_3d order) and aligned to
+    the ``align`` bytes the C entry demands of its pointer - the kernels see only that pointer"""
+    shape = tuple(int(v) for v in shape)
+    if out is None:
+        return _empty_cl3d(*shape, device, dtype) if cl3d else torch.empty(shape, dtype=dtype, device=device)
+    dense = out.permute(0, 2, 3, 4, 1).is_contiguous() if cl3d and out.dim() == 5 else out.is_contiguous()
+    if tuple(out.shape) != shape or out.dtype != dtype or out.device != device or not dense or out.data_ptr() % align:
+        raise Sp3dError(f"{who}: out must be a dense {dtype} {shape} tensor on {device}, {align}-byte aligned; got "
+                        f"{tuple(out.shape)}, {out.dtype}, {out.device}, strides {tuple(out.stride())}, address % {align} = "
+                        f"{out.data_ptr() % align}")
+    return out
+
+
 def _as_cl3d(t: torch.Tensor) -> torch.Tensor:
     """a residual / skip operand as the kernels read it, dense channels_last_3d like the result it is added to; copies
     only when it is not that already (.contiguous returns its argument otherwise, so one condition covers every case)"""
@@ -561,7 +576,7 @@ def cfft2d_(spec: torch.Tensor, inverse: bool, rows_in: Optional[int] = None, ro
     return spec
 
 
-def zdft_fwd_cl(x: torch.Tensor, cout: int, S) -> torch.Tensor:
+def zdft_fwd_cl(x: torch.Tensor, cout: int, S, *, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """channels_last_3d (B,C,X,Y,Z) real -> (B,cout,SZ//2+1,SX,SY) complex64: z-DFT of the rows zero-padded to S"""
     lib = load()
     _require_cuda(x, "x")
@@ -569,14 +584,15 @@ def zdft_fwd_cl(x: torch.Tensor, cout: int, S) -> torch.Tensor:
     if x.dtype != torch.float32 or not x.permute(0, 2, 3, 4, 1).is_contiguous():
         raise Sp3dError("zdft_fwd_cl: dense fp32 channels_last_3d cubes expected")
     SX, SY, SZ = (int(v) for v in S)
-    spec = torch.empty((B, int(cout), SZ // 2 + 1, SX, SY), dtype=torch.complex64, device=x.device)
+    spec = _result_dense(out, (B, int(cout), SZ // 2 + 1, SX, SY), torch.complex64, x.device, "zdft_fwd_cl")
     check(lib.sp3d_zdft_fwd_cl(x.data_ptr(), spec.data_ptr(), B, Cc, int(cout), X, Y, Z, SX, SY, SZ, _stream(x.device)),
           "sp3d_zdft_fwd_cl")
     return spec
 
 
 def unproject_fwd_zdft(views: Sequence[torch.Tensor], jp: int, cam: torch.Tensor, centers: torch.Tensor, valid: torch.Tensor,
-                       batch: int, J: int, h: int, w: int, cube_size, grid_size, img_size, SZ: int) -> torch.Tensor:
+                       batch: int, J: int, h: int, w: int, cube_size, grid_size, img_size, SZ: int, *,
+                       out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """root grid, inference: the unprojection's result as the z-spectrum of its cubes (include/sp3d.h,
     sp3d_unproject_fwd_zdft) -> (B, J, SZ//2+1, X/4, Y/4, 16) complex64, 4 x 4-tiled planes without padding"""
     lib = load()
@@ -588,47 +604,49 @@ def unproject_fwd_zdft(views: Sequence[torch.Tensor], jp: int, cam: torch.Tensor
             raise Sp3dError("unproject_fwd_zdft: dense fp32 (B,h,w,16) heat-map views expected")
     if (Z, int(SZ), jp) not in ZDFT_SHAPES or X % 4 or Y % 4:
         raise Sp3dError(f"unproject_fwd_zdft: built for (Z, SZ, channels) in {sorted(ZDFT_SHAPES)} and X, Y multiples of 4")
-    spec = torch.empty((batch, J, int(SZ) // 2 + 1, X // 4, Y // 4, 16), dtype=torch.complex64, device=cam.device)
+    spec = _result_dense(out, (batch, J, int(SZ) // 2 + 1, X // 4, Y // 4, 16), torch.complex64, cam.device, "unproject_fwd_zdft", 128)
     check(lib.sp3d_unproject_fwd_zdft(_ptr_array(views), jp, cam.data_ptr(), centers.data_ptr(), valid.data_ptr(),
                                       spec.data_ptr(), batch, len(views), J, h, w, X, Y, Z, _f3(grid_size), int(img_size[0]),
                                       int(img_size[1]), int(SZ), _stream(cam.device)), "sp3d_unproject_fwd_zdft")
     return spec
 
 
-def cfft2d_88_tiled(spec: torch.Tensor, X: int, Y: int) -> torch.Tensor:
+def cfft2d_88_tiled(spec: torch.Tensor, X: int, Y: int, *, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """(..., X/4, Y/4, 16) complex64 tiled planes -> (..., 88, 88) complex64: forward x,y transform of the zero-padded planes"""
     lib = load()
     _require_cuda(spec, "spec")
     if spec.dtype != torch.complex64 or not spec.is_contiguous() or tuple(spec.shape[-3:]) != (X // 4, Y // 4, 16):
         raise Sp3dError("cfft2d_88_tiled: dense complex64 (..., X/4, Y/4, 16) expected")
-    out = torch.empty(tuple(spec.shape[:-3]) + (88, 88), dtype=torch.complex64, device=spec.device)
+    out = _result_dense(out, tuple(spec.shape[:-3]) + (88, 88), torch.complex64, spec.device, "cfft2d_88_tiled", 16)
     batch = out.numel() // (88 * 88)
     check(lib.sp3d_cfft2d_88_tiled(spec.data_ptr(), out.data_ptr(), batch, int(X), int(Y), _stream(spec.device)),
           "sp3d_cfft2d_88_tiled")
     return out
 
 
-def zdft_inv_cl(spec: torch.Tensor, X: int, Y: int, Z: int, SZ: int, shift: torch.Tensor, relu: bool = True) -> torch.Tensor:
+def zdft_inv_cl(spec: torch.Tensor, X: int, Y: int, Z: int, SZ: int, shift: torch.Tensor, relu: bool = True, *,
+                out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """(B,O,SZ//2+1,SX,SY) complex64 -> channels_last_3d (B,O,X,Y,Z) = act(shift[o] + unnormalised C2R along z)"""
     lib = load()
     _require_cuda(spec, "spec")
     if not spec.is_contiguous() or spec.dtype != torch.complex64 or spec.dim() != 5 or spec.shape[2] != SZ // 2 + 1:
         raise Sp3dError("zdft_inv_cl: dense complex64 (B,O,SZ//2+1,SX,SY) spectrum expected")
     B, O, _, SX, SY = (int(v) for v in spec.shape)
-    y = _empty_cl3d(B, O, X, Y, Z, spec.device)
+    y = _result_dense(out, (B, O, X, Y, Z), torch.float32, spec.device, "zdft_inv_cl", 16, cl3d=True)
     check(lib.sp3d_zdft_inv_cl(spec.data_ptr(), y.data_ptr(), shift.data_ptr(), B, O, X, Y, Z, SX, SY, int(SZ),
                                1 if relu else 0, _stream(spec.device)), "sp3d_zdft_inv_cl")
     return y
 
 
-def crop_shift_act_cl(src: torch.Tensor, X: int, Y: int, Z: int, shift: torch.Tensor, relu: bool = True) -> torch.Tensor:
+def crop_shift_act_cl(src: torch.Tensor, X: int, Y: int, Z: int, shift: torch.Tensor, relu: bool = True, *,
+                      out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """planar (B,C,SX,SY,SZ) -> channels_last_3d (B,C,X,Y,Z) = act(src[:, :, :X, :Y, :Z] + shift[c]) in one pass"""
     lib = load()
     _require_cuda(src, "src")
     if not src.is_contiguous() or src.dtype != torch.float32:
         raise Sp3dError("crop_shift_act_cl: src must be a dense fp32 (B,C,SX,SY,SZ) tensor")
     B, Cc, SX, SY, SZ = (int(v) for v in src.shape)
-    y = _empty_cl3d(B, Cc, X, Y, Z, src.device)
+    y = _result_dense(out, (B, Cc, X, Y, Z), torch.float32, src.device, "crop_shift_act_cl", 16, cl3d=True)
     check(lib.sp3d_crop_shift_act_cl(src.data_ptr(), y.data_ptr(), shift.data_ptr(), B, Cc, X, Y, Z, SX, SY, SZ,
                                      1 if relu else 0, _stream(src.device)), "sp3d_crop_shift_act_cl")
     return y
@@ -791,7 +809,7 @@ def render_root_heatmaps(roots: torch.Tensor, cam: torch.Tensor, h: int, w: int,
     return out
 
 
-def freq_contract(Xf: torch.Tensor, Wf: torch.Tensor) -> torch.Tensor:
+def freq_contract(Xf: torch.Tensor, Wf: torch.Tensor, *, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Xf (B,C,*F) complex64, Wf (O,C,*F) complex64 (contiguous) -> Yf (B,O,*F) = sum_c Xf * Wf"""
     lib = load()
     _require_cuda(Xf, "Xf")
@@ -803,13 +821,13 @@ def freq_contract(Xf: torch.Tensor, Wf: torch.Tensor) -> torch.Tensor:
     Fn = 1
     for d in Xf.shape[2:]:
         Fn *= int(d)
-    Yf = torch.empty((B, O) + tuple(Xf.shape[2:]), dtype=torch.complex64, device=Xf.device)
+    Yf = _result_dense(out, (B, O) + tuple(Xf.shape[2:]), torch.complex64, Xf.device, "freq_contract")
     check(lib.sp3d_freq_contract(Xf.data_ptr(), Wf.data_ptr(), Yf.data_ptr(), B, Cc, O, Fn, _stream(Xf.device)),
           "sp3d_freq_contract")
     return Yf
 
 
-def freq_contract_ty(Xf: torch.Tensor, T: torch.Tensor, tw: torch.Tensor) -> torch.Tensor:
+def freq_contract_ty(Xf: torch.Tensor, T: torch.Tensor, tw: torch.Tensor, *, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Xf (B,C,KZ,SX,SY) complex64, T (KZ*SX, O, C, 14) fp32 (v2v_net._FoldedV2V._weights_ty), tw (SY,3,2) fp32
     -> (B,O,KZ,SX,SY) complex64: the forward contraction with W^ rebuilt per bin along y (include/sp3d.h)"""
     lib = load()
@@ -819,13 +837,13 @@ def freq_contract_ty(Xf: torch.Tensor, T: torch.Tensor, tw: torch.Tensor) -> tor
     if Xf.dtype != torch.complex64 or not Xf.is_contiguous() or T.dtype != torch.float32 or not T.is_contiguous() or \
             tuple(T.shape) != (KZ * SX, O, Cc, 14) or tuple(tw.shape) != (SY, 3, 2) or not tw.is_contiguous():
         raise Sp3dError("freq_contract_ty: (B,C,KZ,SX,SY) complex64 x (KZ*SX,O,C,14) fp32 table expected")
-    Yf = torch.empty((B, O, KZ, SX, SY), dtype=torch.complex64, device=Xf.device)
+    Yf = _result_dense(out, (B, O, KZ, SX, SY), torch.complex64, Xf.device, "freq_contract_ty")
     check(lib.sp3d_freq_contract_ty(Xf.data_ptr(), T.data_ptr(), tw.data_ptr(), Yf.data_ptr(), B, Cc, O, rows, SY,
                                     _stream(Xf.device)), "sp3d_freq_contract_ty")
     return Yf
 
 
-def freq_contract_ex(Pf: torch.Tensor, Qf: torch.Tensor, mode: str) -> torch.Tensor:
+def freq_contract_ex(Pf: torch.Tensor, Qf: torch.Tensor, mode: str, *, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """the three products of the frequency-domain conv on contiguous complex64 (A,B,*F) operands:
     'fwd'  Pf = X (B,C,*F), Qf = W^ (O,C,*F)  -> (B,O,*F) = sum_c X conj(W^)
     'dx'   Pf = Gy (B,O,*F), Qf = W^ (O,C,*F) -> (B,C,*F) = sum_o Gy W^
@@ -855,7 +873,7 @@ def freq_contract_ex(Pf: torch.Tensor, Qf: torch.Tensor, mode: str) -> torch.Ten
         raise Sp3dError(f"freq_contract_ex: unknown mode {mode}")
     if not ok:
         raise Sp3dError("freq_contract_ex: contracted dimensions differ")
-    Y = torch.empty((I, J) + tuple(Pf.shape[2:]), dtype=torch.complex64, device=Pf.device)
+    Y = _result_dense(out, (I, J) + tuple(Pf.shape[2:]), torch.complex64, Pf.device, "freq_contract_ex")
     check(lib.sp3d_freq_contract_ex(Pf.data_ptr(), Qf.data_ptr(), Y.data_ptr(), I, J, K, Fn, sPi, sPk, sQj, sQk, cp, cq,
                                     _stream(Pf.device)), "sp3d_freq_contract_ex")
     return Y
