@@ -132,7 +132,8 @@ const char *sp3d_error_string(int code);
 int sp3d_pack_heatmaps(const float *const *hm_views, float *packed, int B, int V, int J, int Jp, int h, int w,
                        void *stream);
 /* same with explicit storage types: in_bf16 / out_bf16 = 1 when the planar inputs / the packed output
- * hold bf16 instead of fp32 (bf16 needs Jp == 16 or 32) */
+ * hold bf16 instead of fp32 (bf16 needs Jp == 16 or 32).  fp32 -> bf16 rounds to nearest even, as torch's conversion
+ * does (0x7f7fffff becomes inf); NaN heat-maps stay NaN in bf16 storage (sign kept, payload not specified). */
 int sp3d_pack_heatmaps_ex(const void *const *hm_views, void *packed, int in_bf16, int out_bf16, int B, int V, int J,
                           int Jp, int h, int w, void *stream);
 
@@ -363,6 +364,8 @@ int sp3d_soft_argmax_grid_bwd(const float *x, const float *centers, const float 
  *   mode 3: relu(y + shift[c]) + residual
  * replacing the separate bias / BatchNorm3d / ReLU / add kernels of lib/models/v2v_net.py:13-17,
  * 26-45, 60-69, 100-108.  Needs C % 4 == 0 (channels_last) or inner % 4 == 0 (planar).
+ * The ReLU is fmaxf(., 0): in modes 1-3 a NaN sum becomes 0 (torch.relu would keep it; mode 3 still adds the residual to
+ * that 0), in mode 0 a NaN stays NaN.
  */
 int sp3d_channel_shift_act(float *y, const float *shift, const float *residual, int mode, int64_t batch, int C,
                            int64_t inner, int channels_last, void *stream);
@@ -457,7 +460,9 @@ int sp3d_render_root_heatmaps(const float *roots, int B, int R, const float *cam
  * Differentiable joint rendering of the self-supervised pose loss (lib/models/multi_person_posenet_ssv.py:409-465):
  * kps (N, P, J, 2) projected joints in heat-map pixels (N = views x samples), count (N) people per entry (NULL: P),
  * out (N, J, h, w) = clip(sum over people of sigma-Gaussians, 0, 1); _bwd returns d loss / d kps given d loss / d out.
- * P <= 16.
+ * P <= 16.  A count[n] above P is clamped to P; gradient rows p >= count[n] are written as 0.  A NaN key-point (n, p, j) with
+ * p < count[n] makes the whole map (n, j) NaN, as torch.clip does (no other map and no other map's gradient changes);
+ * a +-inf co-ordinate contributes exp(-inf) = 0.
  */
 int sp3d_render_joints_fwd(const float *kps, const int *count, int N, int P, int J, int h, int w, float sigma, float *out,
                            void *stream);

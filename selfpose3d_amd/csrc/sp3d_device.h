@@ -301,11 +301,21 @@ __device__ __forceinline__ uint16_t f32_to_bf16(float f)       // round to neare
     u += 0x7fffu + ((u >> 16) & 1u);
     return (uint16_t)(u >> 16);
 }
+// the same for caller data (the packed heat-maps), which nothing makes finite: the integer rounding above carries a NaN
+// with a full low half into the exponent or the sign (0x7f800001 -> +inf, 0x7fffffff -> -0.0, 0xffffffff -> +0.0), so
+// a NaN keeps its sign and high payload bits and gets the quiet bit instead.  +-inf and 0x7f7fffff -> inf go through
+// the rounding as torch's conversion does.
+__device__ __forceinline__ uint16_t f32_to_bf16_any(float f)
+{
+    const uint32_t u = __float_as_uint(f);
+    return (u & 0x7fffffffu) > 0x7f800000u ? (uint16_t)((u >> 16) | 0x0040u) : f32_to_bf16(f);
+}
 
 template <typename T> struct Store4;
 template <> struct Store4<float> {
     __device__ __forceinline__ static float4 load(const float *p) { return *reinterpret_cast<const float4 *>(p); }
     __device__ __forceinline__ static void store(float *p, float4 v) { *reinterpret_cast<float4 *>(p) = v; }
+    __device__ __forceinline__ static void store_any(float *p, float4 v) { store(p, v); }     // caller data: see Store4<bf16_t>
     // the cubes are written once and read by a later kernel: non-temporal stores keep them from evicting the
     // heat-map lines the gather re-uses out of the XCD's L2 (-2.5 % on the bench workload, -8 % when the maps fit).
     // Not for the packed heat-maps: those are re-read by the very next kernel and should stay cached.
@@ -332,6 +342,15 @@ template <> struct Store4<bf16_t> {
         return r;
     }
     __device__ __forceinline__ static void store(bf16_t *p, float4 v) { *reinterpret_cast<uint2 *>(p) = pack4(v); }
+    // store_any: caller data, which nothing makes finite (the pack kernel's heat-maps): a NaN stays a NaN.  store / store_nt /
+    // store1 / pack4 are for cube values clamped to [0, 1] and do without the test
+    __device__ __forceinline__ static void store_any(bf16_t *p, float4 v)
+    {
+        uint2 r;
+        r.x = (uint32_t)f32_to_bf16_any(v.x) | ((uint32_t)f32_to_bf16_any(v.y) << 16);
+        r.y = (uint32_t)f32_to_bf16_any(v.z) | ((uint32_t)f32_to_bf16_any(v.w) << 16);
+        *reinterpret_cast<uint2 *>(p) = r;
+    }
     __device__ __forceinline__ static void store_nt(bf16_t *p, float4 v)
     {
         typedef uint32_t v2u __attribute__((ext_vector_type(2)));

@@ -136,7 +136,7 @@ __global__ __launch_bounds__(256) void render_joints_fwd_kernel(const float *__r
             const float ex = (xx - sk[2 * p]) / sigma, ey = (yy - sk[2 * p + 1]) / sigma;
             s += expf(-(ex * ex) / 2.0f - (ey * ey) / 2.0f);
         }
-        o[pidx] = fminf(fmaxf(s, 0.0f), 1.0f);
+        o[pidx] = s < 0.0f ? 0.0f : (s > 1.0f ? 1.0f : s);        // torch.clip: a NaN sum (a NaN key-point) stays NaN
     }
 }
 

@@ -132,7 +132,7 @@ __global__ __launch_bounds__(256) void pack_nhwc_kernel(Views hm, float *__restr
             float4 o;
             o.x = tile[4 * q + 0][px]; o.y = tile[4 * q + 1][px];
             o.z = tile[4 * q + 2][px]; o.w = tile[4 * q + 3][px];
-            Store4<TO>::store(dst + (size_t)px * JP + 4 * q, o);
+            Store4<TO>::store_any(dst + (size_t)px * JP + 4 * q, o);           // heat-maps are caller data: NaN stays NaN
         }
     }
 }
