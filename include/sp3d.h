@@ -114,7 +114,19 @@ enum {
      * launch, for Jp != 32, for SP3D_OUT_CHANNELS_LAST, for either bf16 flag, for SP3D_HM_ONE_CHANNEL, for heat-maps below
      * 2x2 or above 2^24 pixels, and for the flag on any other forward entry (_fwd, _fwd_indexed, _fwd_strided,
      * sp3d_unproject_one_fwd_train).  Read back by sp3d_unproject_bwd_packed[_det] with SP3D_SCATTER_WIDE. */
-    SP3D_HM_WIDE_MASK = 0x1000
+    SP3D_HM_WIDE_MASK = 0x1000,
+    /* OR-ed into hm_layout of sp3d_unproject_fwd and sp3d_unproject_fwd_indexed ONLY: `cubes` receives the z-SPECTRUM of the
+     * cubes instead of the cubes, (P, J, SZ/2+1, X/4, Y/4, 16) complex64 with SZ = 28 implied (P = B without sample_of),
+     * layout and values exactly as documented at sp3d_unproject_fwd_zdft below; a cube that `valid` skips gets an all-zero
+     * spectrum.  Takes SP3D_LAYOUT_NHWC, fp32 maps, Jp == 16 with J <= 16 or Jp == 32 with J <= 32, Z == 20,
+     * X % 4 == Y % 4 == 0, heat-maps of 2x2 .. 2^24 pixels, grids == NULL and a 128-byte aligned `cubes`.  At Jp == 16 it
+     * is the launch of sp3d_unproject_fwd_zdft (same kernel, grid and bits); at Jp == 32 the two channel groups of the
+     * Jp = 32 paragraph below, group 1 writing 16 channel planes (16 * (SZ/2+1) * (X/4) * (Y/4) * 16 complex values) into
+     * each sample's spectrum (J <= 16: one launch).  SP3D_EUNSUPPORTED, before any launch, for SP3D_OUT_CHANNELS_LAST,
+     * SP3D_HM_BF16, SP3D_OUT_BF16, SP3D_HM_ONE_CHANNEL or SP3D_HM_WIDE_MASK next to it, for SP3D_LAYOUT_PLANAR, for any other
+     * Jp, Z or X / Y, for a non-NULL grids, for a misaligned `cubes`, and for the flag on sp3d_unproject_fwd_strided,
+     * sp3d_unproject_fwd_train and sp3d_unproject_one_fwd_train. */
+    SP3D_OUT_ZSPECTRUM = 0x2000
 };
 
 int sp3d_abi_version(void);
@@ -142,7 +154,9 @@ int sp3d_pack_heatmaps_ex(const void *const *hm_views, void *packed, int in_bf16
  * configurations).  A 32-float pixel is one 128-byte line, gathered as two channel groups (channels 0-15, 16..J-1) by
  * one launch each of the 16-channel kernels; each group is bit-identical to the oracle.  At Jp = 32 the NHWC forward
  * entries (_fwd, _fwd_indexed, _fwd_strided) take fp32 or bf16 maps and cubes, with or without sample_of and grids, for
- * heat-maps of at least 2x2 pixels; SP3D_EUNSUPPORTED for a channels-last result and for sp3d_unproject_fwd_zdft.  The
+ * heat-maps of at least 2x2 pixels; SP3D_EUNSUPPORTED for a channels-last result and for sp3d_unproject_fwd_zdft.  With
+ * SP3D_OUT_ZSPECTRUM (_fwd, _fwd_indexed; fp32, no grids) the two groups leave as the z-spectrum of the root grid's cubes,
+ * one spectrum over all J channels, instead of planar cubes.  The
  * training pair takes Jp = 32 by request only: the pass mask of sp3d_unproject_fwd_train holds 16 bits per voxel, so that
  * entry and both sp3d_unproject_bwd_packed entries answer SP3D_EUNSUPPORTED at Jp = 32 as they are called for Jp <= 16;
  * with SP3D_HM_WIDE_MASK the forward writes one 16-bit mask plane per channel group, and with SP3D_SCATTER_WIDE the two

@@ -25,6 +25,7 @@ HM_BF16 = 0x200
 OUT_BF16 = 0x400
 HM_ONE_CHANNEL = 0x800      # one channel of a wider tensor, read in place (include/sp3d.h)
 HM_WIDE_MASK = 0x1000       # sp3d_unproject_fwd_train at Jp = 32: a (2, P, N) pass mask, one plane per channel group
+OUT_ZSPECTRUM = 0x2000      # sp3d_unproject_fwd[_indexed]: the root grid's cubes leave as their z-spectrum (Jp = 16 or 32)
 SCATTER_AUTO, SCATTER_PER_TAP, SCATTER_MERGE = 0, 2, 3      # include/sp3d.h: per-call scatter choice of unproject_bwd_packed
 SCATTER_WIDE = 0x100        # OR-ed into that choice: 17..32 joints, 32-element pixels, the two-plane mask
 MAX_VIEWS = 16
@@ -608,6 +609,31 @@ def unproject_fwd_zdft(views: Sequence[torch.Tensor], jp: int, cam: torch.Tensor
     check(lib.sp3d_unproject_fwd_zdft(_ptr_array(views), jp, cam.data_ptr(), centers.data_ptr(), valid.data_ptr(),
                                       spec.data_ptr(), batch, len(views), J, h, w, X, Y, Z, _f3(grid_size), int(img_size[0]),
                                       int(img_size[1]), int(SZ), _stream(cam.device)), "sp3d_unproject_fwd_zdft")
+    return spec
+
+
+def unproject_fwd_zspectrum(views: Sequence[torch.Tensor], jp: int, cam: torch.Tensor, centers: torch.Tensor, valid: torch.Tensor,
+                            batch: int, J: int, h: int, w: int, cube_size, grid_size, img_size, SZ: int, *,
+                            out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``unproject_fwd_zdft`` through the flag SP3D_OUT_ZSPECTRUM of sp3d_unproject_fwd (include/sp3d.h): packed pixels of
+    ``jp`` = 16 (J <= 16, the same launch) or 32 (J <= 32, one launch per channel group) -> ONE
+    (B, J, SZ//2+1, X/4, Y/4, 16) complex64 spectrum over all J channels"""
+    lib = load()
+    _require_cam(cam)
+    X, Y, Z = (int(c) for c in cube_size)
+    if jp not in (16, 32) or not 1 <= J <= jp:
+        raise Sp3dError(f"unproject_fwd_zspectrum: packed pixels of 16 or 32 channels and J <= jp expected, got jp {jp}, J {J}")
+    for v in views:
+        _require_cuda(v, "heat-map view")
+        if v.dtype != torch.float32 or not v.is_contiguous() or tuple(v.shape) != (batch, h, w, jp):
+            raise Sp3dError(f"unproject_fwd_zspectrum: dense fp32 (B,h,w,{jp}) heat-map views expected")
+    if (Z, int(SZ), 16) not in ZDFT_SHAPES or X % 4 or Y % 4:
+        raise Sp3dError(f"unproject_fwd_zspectrum: built for (Z, SZ, channels) in {sorted(ZDFT_SHAPES)} and X, Y multiples of 4")
+    spec = _result_dense(out, (batch, J, int(SZ) // 2 + 1, X // 4, Y // 4, 16), torch.complex64, cam.device,
+                         "unproject_fwd_zspectrum", 128)
+    check(lib.sp3d_unproject_fwd(_ptr_array(views), LAYOUT_NHWC | OUT_ZSPECTRUM, jp, cam.data_ptr(), centers.data_ptr(),
+                                 valid.data_ptr(), spec.data_ptr(), None, batch, len(views), J, h, w, X, Y, Z, _f3(grid_size),
+                                 int(img_size[0]), int(img_size[1]), _stream(cam.device)), "sp3d_unproject_fwd (z-spectrum)")
     return spec
 
 

@@ -34,7 +34,9 @@ int sp3d_unproject_fwd_variant(const float *const *hm_views, int Jp, const float
  *   entry        which entry point asks: _INDEXED (hm_layout with its flag bits as in include/sp3d.h), _STRIDED (the same,
  *                with out_strides, NULL = dense), _TRAIN (the same, with a pass mask), _ZDFT, _TUNING (NHWC fp32 and the
  *                word `variant`, bit 24 included; `variant` is read for this entry only), _ONE_TRAIN
- *                (sp3d_unproject_one_fwd_train: SP3D_HM_ONE_CHANNEL implied, with a pass mask)
+ *                (sp3d_unproject_one_fwd_train: SP3D_HM_ONE_CHANNEL implied, with a pass mask).  SP3D_OUT_ZSPECTRUM in
+ *                hm_layout is planned for _INDEXED and refused for the other entries, as the entry points refuse it; _ZDFT
+ *                refuses Jp != 16 as sp3d_unproject_fwd_zdft does
  *   names        SP3D_PLAN_NAME bytes per launch: the kernel with its template arguments, as a kernel trace prints it
  *                without namespaces and parameter list
  *   fields       SP3D_PLAN_FIELDS int32 per launch: workgroups, workgroup size, dynamic LDS bytes, number of kernel

@@ -200,6 +200,9 @@ static int resolve_one(const FwdRequest &rq, Launch &L)
 // strided path already carries full-volume strides), the two planar defaults only (pipe / brick stacks).  A pass mask only
 // with SP3D_HM_WIDE_MASK (sp3d_unproject_fwd_train): each group writes the 16-bit words of its own channels into its own
 // plane of P * N words - group 1's mask pointer lies P * N words further, bit j of its words being channel 16 + j.
+// SP3D_OUT_ZSPECTRUM (rq.zd): the same two groups through the ZD brick kernels.  The spectrum is (P, J, K, X/4, Y/4, 16)
+// complex over ALL J channels, so the sample stride comes from here (Geom.sB, in complex elements - the ZD form reads no
+// other result stride) and group 1 starts 16 channel planes = 16 * K * (X/4) * (Y/4) * 16 complex values further.
 
 // The one place a forward request becomes launches: every downgrade and refusal, in this order.  Pure host arithmetic.
 static int resolve_fwd(const FwdRequest &rq, FwdTuning t, Launch (&plan)[SP3D_PLAN_RECORDS], int &n)
@@ -207,9 +210,13 @@ static int resolve_fwd(const FwdRequest &rq, FwdTuning t, Launch (&plan)[SP3D_PL
     n = 1;
     Launch &L = plan[0];
     L = Launch{};
-    L.g = rq.g; L.grid_y = 1; L.grids = true;
+    L.g = rq.g; L.grid_y = 1; L.grids = !rq.zd;      // a z-spectrum launch writes no grids (its entries take none)
     // the two-plane mask belongs to the Jp = 32 training forward with a planar fp32 result, and to nothing else
     if (rq.wide_mask && (rq.one || !rq.g.pass_mask || rq.layout != SP3D_LAYOUT_NHWC || rq.Jp != WIDE_PS || rq.out_cl || rq.io))
+        return SP3D_EUNSUPPORTED;
+    // the z-spectrum result: packed fp32 maps at Jp = 16 or 32, the one grid shape the z-DFT is built for, nothing else next to it
+    if (rq.zd && (rq.one || rq.wide_mask || rq.layout != SP3D_LAYOUT_NHWC || rq.io || rq.out_cl || rq.g.pass_mask ||
+                  (rq.Jp != 16 && rq.Jp != WIDE_PS) || rq.g.Z != ZDZ || (rq.g.X % BR) || (rq.g.Y % BR)))
         return SP3D_EUNSUPPORTED;
     if (rq.one) return resolve_one(rq, L);
     if (rq.layout == SP3D_LAYOUT_PLANAR) {
@@ -226,11 +233,15 @@ static int resolve_fwd(const FwdRequest &rq, FwdTuning t, Launch (&plan)[SP3D_PL
     const FwdTuning asked = t, pipe = default_tuning(FWD_PIPE), stacks = default_tuning(FWD_BRICK_STACKS);
     // the pipelined kernels clamp a 2x2 block (needs a 2x2 image) and form pixel indices with 24-bit multiplies
     const bool tile_only = g.w < 2 || g.h < 2 || (int64_t)g.h * g.w > (1 << 24);
+    if (rq.zd) {
+        if (tile_only) return SP3D_EUNSUPPORTED;
+        g.sB = (long long)g.J * (ZDSZ / 2 + 1) * (g.X / BR) * (g.Y / BR) * 16;
+    }
     if (tile_only) t.pipe = t.brick = 0;
     if (t.brick) t.pipe = 1;
     if (rq.io) t.one_wave = 1;                 // bf16 storage: one wave per workgroup only
     if (rq.Jp == WIDE_PS) {
-        if (g.J > WIDE_PS || rq.out_cl || (g.pass_mask && !rq.wide_mask) || rq.zd || tile_only) return SP3D_EUNSUPPORTED;
+        if (g.J > WIDE_PS || rq.out_cl || (g.pass_mask && !rq.wide_mask) || tile_only) return SP3D_EUNSUPPORTED;
         if (memcmp(&asked, &pipe, sizeof(t)) && memcmp(&asked, &stacks, sizeof(t))) return SP3D_EUNSUPPORTED;
         Geom gg = g;
         gg.J = g.J < 16 ? g.J : 16;
@@ -241,7 +252,8 @@ static int resolve_fwd(const FwdRequest &rq, FwdTuning t, Launch (&plan)[SP3D_PL
         gg.J = g.J - 16;
         if (g.pass_mask) gg.pass_mask = g.pass_mask + (size_t)g.B * g.N;
         L1.view_off = 16 * ((rq.io & 1) ? 2 : 4);
-        L1.out_off = (size_t)16 * g.sJ * ((rq.io & 2) ? 2 : 4);
+        L1.out_off = rq.zd ? (size_t)16 * (ZDSZ / 2 + 1) * (g.X / BR) * (g.Y / BR) * 16 * 8
+                           : (size_t)16 * g.sJ * ((rq.io & 2) ? 2 : 4);
         L1.grids = false;
         return resolve_group(rq, t, gg, rq.io ? 16 : (gg.J + 3) / 4 * 4, WIDE_PS, L1);
     }
@@ -282,7 +294,8 @@ static int fwd_request(FwdRequest &rq, int hm_layout, int Jp, bool ptrs, int B, 
     rq.one = (hm_layout & SP3D_HM_ONE_CHANNEL) != 0;
     rq.out_cl = (hm_layout & SP3D_OUT_CHANNELS_LAST) != 0;
     rq.wide_mask = (hm_layout & SP3D_HM_WIDE_MASK) != 0;
-    rq.zd = false; rq.out_aligned = true; rq.one_train = false;
+    rq.zd = (hm_layout & SP3D_OUT_ZSPECTRUM) != 0;
+    rq.out_aligned = true; rq.one_train = false;
     return SP3D_OK;
 }
 
@@ -378,6 +391,10 @@ extern "C" int sp3d_unproject_fwd_indexed(const float *const *hm_views, int hm_l
     if (rc) return rc;
     rq.g.sample_of = sample_of;
     rq.out_aligned = ((uintptr_t)cubes & 15) == 0;
+    if (rq.zd) {    // SP3D_OUT_ZSPECTRUM: `cubes` is the spectrum, whole 128-byte lines; the brick stacks as sp3d_unproject_fwd_zdft
+        if (grids || ((uintptr_t)cubes & 127)) return SP3D_EUNSUPPORTED;
+        return run_fwd(rq, default_tuning(FWD_BRICK_STACKS), hm_views, cam, centers, valid, cubes, nullptr, stream);
+    }
     return run_fwd(rq, default_tuning(rq.g, rq.out_cl), hm_views, cam, centers, valid, cubes, grids, stream);
 }
 
@@ -391,7 +408,7 @@ extern "C" int sp3d_unproject_fwd_strided(const float *const *hm_views, int hm_l
                          X, Y, Z, grid_size, W_in, H_in);
     if (rc) return rc;
     // the one-channel read takes either layout
-    if ((!rq.one && rq.layout != SP3D_LAYOUT_NHWC) || rq.out_cl || w < 2 || h < 2) return SP3D_EUNSUPPORTED;
+    if ((!rq.one && rq.layout != SP3D_LAYOUT_NHWC) || rq.out_cl || rq.zd || w < 2 || h < 2) return SP3D_EUNSUPPORTED;
     rc = set_result_strides(rq.g, out_strides, cubes);
     if (rc) return rc;
     rq.g.sample_of = sample_of;
@@ -451,9 +468,12 @@ extern "C" int sp3d_unproject_fwd_plan(int entry, int hm_layout, int Jp, const i
     int rc = fwd_request(rq, hm_layout, Jp, true, B, V, J, h, w, X, Y, Z, grid_size, 1, 1);
     if (!rc && entry == SP3D_PLAN_STRIDED && out_strides) rc = set_result_strides(rq.g, out_strides, nullptr);
     if (rc) return rc;
+    // SP3D_OUT_ZSPECTRUM belongs to the indexed entry alone; sp3d_unproject_fwd_zdft keeps its own Jp == 16
+    if (rq.zd && entry != SP3D_PLAN_INDEXED) return SP3D_EUNSUPPORTED;
+    if (entry == SP3D_PLAN_ZDFT && Jp != 16) return SP3D_EUNSUPPORTED;
     rq.one_train = entry == SP3D_PLAN_ONE_TRAIN;
     if (entry == SP3D_PLAN_TRAIN || rq.one_train) rq.g.pass_mask = reinterpret_cast<uint16_t *>(records);    // "there is one": never dereferenced
-    rq.zd = entry == SP3D_PLAN_ZDFT;
+    rq.zd = rq.zd || entry == SP3D_PLAN_ZDFT;
     const FwdTuning t = entry == SP3D_PLAN_TUNING ? decode_tuning(variant)
                                                   : (rq.zd ? default_tuning(FWD_BRICK_STACKS) : default_tuning(rq.g, rq.out_cl));
     memcpy(tuning, &t, sizeof(t));
@@ -487,7 +507,7 @@ extern "C" int sp3d_unproject_fwd_train(const float *const *hm_views, int hm_lay
     const int rc = fwd_request(rq, hm_layout, Jp, cam && centers && valid && cubes && pass_mask, P, V, J, h, w,
                                X, Y, Z, grid_size, W_in, H_in);
     if (rc) return rc;
-    if (rq.layout != SP3D_LAYOUT_NHWC || rq.io || rq.one || w < 2 || h < 2) return SP3D_EUNSUPPORTED;
+    if (rq.layout != SP3D_LAYOUT_NHWC || rq.io || rq.one || rq.zd || w < 2 || h < 2) return SP3D_EUNSUPPORTED;
     rq.g.sample_of = sample_of;
     rq.g.pass_mask = pass_mask;
     return run_fwd(rq, default_tuning(rq.g, rq.out_cl), hm_views, cam, centers, valid, cubes, grids, stream);
@@ -505,6 +525,7 @@ extern "C" int sp3d_unproject_one_fwd_train(const float *const *hm_views, int hm
     const int rc = fwd_request(rq, hm_layout | SP3D_HM_ONE_CHANNEL, Jp, cam && centers && valid && cubes && pass_mask, P, V,
                                J, h, w, X, Y, Z, grid_size, W_in, H_in);
     if (rc) return rc;
+    if (rq.zd) return SP3D_EUNSUPPORTED;
     rq.one_train = true;
     rq.g.sample_of = sample_of;
     rq.g.pass_mask = pass_mask;

@@ -194,7 +194,9 @@ __global__ __launch_bounds__(512, ZD ? SP3D_ZD_MINW : SP3D_BRICK_MINW) void unpr
             const float4 q4 = *reinterpret_cast<const float4 *>(bsmem + wz * WLDS + c * WOSTR + pos * 4);
             v[4 * wz] = q4.x; v[4 * wz + 1] = q4.y; v[4 * wz + 2] = q4.z; v[4 * wz + 3] = q4.w;
         }
-        float2 *o = reinterpret_cast<float2 *>(cubes) + ((((size_t)b * g.J + c) * K) * (size_t)g.bk_nxy + (size_t)t) * 16 + pos;
+        // g.sB: complex values per sample of the WHOLE spectrum, from the host - a channel group of Jp = 32 has g.J channels
+        // of its own but lies inside a spectrum of all J (resolve_fwd); the ZD form reads no other result stride
+        float2 *o = reinterpret_cast<float2 *>(cubes) + (size_t)b * (size_t)g.sB + (((size_t)c * K) * (size_t)g.bk_nxy + (size_t)t) * 16 + pos;
         const size_t kstride = (size_t)g.bk_nxy * 16;
         float re[K], im[K];
         zdft_real<ZDZ, ZDSZ>(v, re, im);
@@ -456,6 +458,17 @@ __global__ __launch_bounds__(512, SP3D_BRICK_MINW) void unproject_brick_h_kernel
 // bf16 heat-maps: two lanes per pixel, 16 channels
 #define SP3D_BRICK_H(CL_, TO_, PS_) \
     SP3D_ROW(BrickFn, (KernelKey{16, PS_, false, 0, CL_, 1 | io_of<float, TO_>()}), unproject_brick_h_kernel, CL_, TO_, PS_)
+// Jp = 32 channel groups with the z-spectrum result (SP3D_OUT_ZSPECTRUM): group 0 at JP = 16, group 1 at ceil4(J - 16).
+// The rows are a table of their own behind find_brick_kernel: the row census of tests/test_fwd_option_sweep_reference.py counts
+// the rows of find_brick_kernel that its sweep of cube-writing options reaches; these write no cubes, and each of them is
+// planned by tests/test_wide_front_host.py and run by tests/test_gpu_wide_front.py.
+static int find_brick_zspectrum32_kernel(const KernelKey &key, const void *&fn, const char *&name)
+{
+    SP3D_BRICK(16, false, float, float, true, 32) SP3D_BRICK(4, false, float, float, true, 32)
+    SP3D_BRICK(8, false, float, float, true, 32) SP3D_BRICK(12, false, float, float, true, 32)
+    return SP3D_EUNSUPPORTED;
+}
+
 int find_brick_kernel(const KernelKey &key, const void *&fn, const char *&name)
 {
     SP3D_BRICK(4, false, float, float, false, 4) SP3D_BRICK(4, true, float, float, false, 4)
@@ -469,7 +482,7 @@ int find_brick_kernel(const KernelKey &key, const void *&fn, const char *&name)
     SP3D_BRICK(4, false, float, float, false, 32) SP3D_BRICK(8, false, float, float, false, 32)
     SP3D_BRICK(12, false, float, float, false, 32) SP3D_BRICK(16, false, float, float, false, 32)
     SP3D_BRICK(16, false, float, bf16_t, false, 32) SP3D_BRICK_H(false, float, 32) SP3D_BRICK_H(false, bf16_t, 32)
-    return SP3D_EUNSUPPORTED;
+    return find_brick_zspectrum32_kernel(key, fn, name);
 }
 
 } // namespace sp3d

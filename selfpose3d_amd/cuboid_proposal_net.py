@@ -86,8 +86,11 @@ class CuboidProposalNet(nn.Module):
         # ... or, round 6, not at all: the kernel keeps a 4 x 4 bundle of z columns in LDS and emits their z-spectrum, which
         # is what the opening conv computes from the cubes first (sp3d_unproject_fwd_zdft; bit-identical, one launch and
         # 2 x 32.8 MB of HBM traffic less at B = 4)
-        sz = self.v2v_net.wants_zspectrum(*self.cube_size, hms[0].shape[1]) if cl16 else None
-        if sz is not None and self.project_layer.io_dtype == torch.float32 and self.project_layer.jp_for(hms[0].shape[1]) == 16 \
+        # ... and, opt-in (SP3D_WIDE_FRONT=1), at 17..32 joints too: one launch per channel group of the 32-float pixel
+        jp = self.project_layer.jp_for(hms[0].shape[1])
+        wide = direct and jp == 32 and self.project_layer.wide_zspectrum and getattr(self.v2v_net, "wide_front", False)
+        sz = self.v2v_net.wants_zspectrum(*self.cube_size, hms[0].shape[1]) if cl16 or wide else None
+        if sz is not None and self.project_layer.io_dtype == torch.float32 and (jp == 16 or wide) \
                 and self.project_layer.mode in ("auto", "nhwc"):
             from .v2v_net import TiledZSpectrum
             spec = self.project_layer.get_voxel_zspectrum(hms, meta, self.grid_size, [self.grid_center], self.cube_size, sz,

@@ -312,6 +312,10 @@ class ProjectLayer(nn.Module):
         # instead of planar forward + planar backward.  Same cubes as the no-grad forward; off until tools/bench_wide_grad.py
         # has recorded that it is faster in every leg
         self.wide_grad = _lib.env_switch("SP3D_WIDE_GRAD", False)
+        # opt-in (SP3D_WIDE_FRONT=1 / ``wide_zspectrum = True``, with ``V2VNet.wide_front``): ``get_voxel_zspectrum`` also takes
+        # 17..32 joints - two launches, one per channel group of the 32-float pixel, into one z-spectrum - instead of raising.
+        # Off until tools/bench_coco17.py has recorded that the root net is faster with it on both rigs
+        self.wide_zspectrum = _lib.env_switch("SP3D_WIDE_FRONT", False)
 
     @contextlib.contextmanager
     def static_camera_table(self, table: torch.Tensor):
@@ -454,17 +458,22 @@ class ProjectLayer(nn.Module):
         B, J, h, w = heatmaps[0].shape
         if [w, h] != self.heatmap_size:
             raise _lib.Sp3dError(f"heat-map tensor is {w}x{h} but cfg.NETWORK.HEATMAP_SIZE is {self.heatmap_size}")
-        if self.io_dtype != torch.float32 or self.jp_for(J) != 16 or self.mode not in ("auto", "nhwc") or w < 2 or h < 2:
+        jp = self.jp_for(J)
+        wide = self.wide_zspectrum and jp == 32 and J <= 32
+        if self.io_dtype != torch.float32 or not (jp == 16 or wide) or self.mode not in ("auto", "nhwc") or w < 2 or h < 2:
             raise _lib.Sp3dError("get_voxel_zspectrum: fp32 NHWC path with 13..16 joints only")
         cam = self.camera_table(meta, B, flip_xcoords, device)
         centers, valid = self.centers_valid(grid_center, B, device)
-        source = _packed_source(heatmaps, 16, torch.float32)
+        source = _packed_source(heatmaps, jp, torch.float32)
         if source is not None:
             packed = source.detach()
         elif self.cache_packs:
-            packed = packed_heatmaps(heatmaps, 16, torch.float32)
+            packed = packed_heatmaps(heatmaps, jp, torch.float32)
         else:
-            packed = _lib.pack_heatmaps([x.detach() for x in heatmaps], jp=16)
+            packed = _lib.pack_heatmaps([x.detach() for x in heatmaps], jp=jp)
+        if wide:    # 17..32 joints: one launch per channel group into one spectrum (SP3D_OUT_ZSPECTRUM)
+            return _lib.unproject_fwd_zspectrum([packed[c] for c in range(len(heatmaps))], 32, cam, centers, valid, B, J, h, w,
+                                                [int(v) for v in cube_size], [float(v) for v in grid_size], self.img_size, int(SZ))
         return _lib.unproject_fwd_zdft([packed[c] for c in range(len(heatmaps))], 16, cam, centers, valid, B, J, h, w,
                                        [int(v) for v in cube_size], [float(v) for v in grid_size], self.img_size, int(SZ))
 

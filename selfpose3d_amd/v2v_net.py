@@ -105,6 +105,17 @@ def _zdft_front_ok(w0, w1, Z, SZ, channels=16) -> bool:
                 and is_cl(w1))
 
 
+def _wide_front_ok(w0, w1, Z, SZ) -> bool:
+    """the static conditions of the z-spectrum form of the opening conv at 17..32 input channels (``V2VNet.wide_front``):
+    the (Z, SZ) the z-DFT kernels are built for, 16 output channels and a channels-last conv stack behind it, as
+    _zdft_front_ok asks - only the input side differs: the spectrum arrives from the unprojection (two channel groups), and
+    the plane transforms and the contraction take any channel count.  Nothing else reads this predicate: cubes of 17..32
+    channels keep the library transforms (_zdft_front_ok stays at <= 16)"""
+    from . import _lib
+    return bool((int(Z), int(SZ), 16) in _lib.ZDFT_SHAPES and int(w0.shape[0]) == 16 and 17 <= int(w0.shape[1]) <= 32
+                and is_cl(w1))
+
+
 class _FreqConv3d(torch.autograd.Function):
     """Stride-1 'same' Conv3d (odd cubic kernel) in the frequency domain, forward AND backward, for the 7x7x7 opening
     conv of the V2V nets (v2v_net.py:113-117) on the GPU: zero-padded rFFT (rocFFT through torch.fft) -> channel
@@ -714,6 +725,9 @@ class V2VNet(nn.Module):
         self.zdft = True                 # ... root grid: direct z-DFTs + dense 2-D transforms instead of the 3-D real plans
         self.wino_split = True           # ... fused Winograd layers: exact 3-piece bf16 splits on the bf16 matrix pipe
         self.direct_conv = True          # ... full-resolution 3x3x3 layers: direct (implicit GEMM) split convolution
+        # opt-in (SP3D_WIDE_FRONT=1): at 17..32 input channels the opening conv may start from the unprojection's z-spectrum too
+        from . import _lib
+        self.wide_front = _lib.env_switch("SP3D_WIDE_FRONT", False)
         self._plan = None
         self.reset_parameters()
 
@@ -800,13 +814,21 @@ class V2VNet(nn.Module):
     def wants_zspectrum(self, X, Y, Z, cin: int):
         """SZ when the next inference forward can start from the cubes' z-spectrum (``TiledZSpectrum``: the unprojection
         fused with the opening conv's z pass, root grid), else None.  ``fuse_zdft`` (default on; SP3D_FUSE_ZDFT=0 turns it
-        off for A/B) and the conditions of the direct z-DFT form + 88 x 88 planes + a float32 inference plan."""
+        off for A/B) and the conditions of the direct z-DFT form + 88 x 88 planes + a float32 inference plan.  With
+        ``wide_front`` (default off; SP3D_WIDE_FRONT=1) it also answers for 17 <= cin <= 32 (_wide_front_ok)."""
         from . import _lib
         if not getattr(self, "fuse_zdft", _lib.env_switch("SP3D_FUSE_ZDFT", True)):
             return None
-        if self.training or torch.is_grad_enabled() or not self.fused_inference or not self.wants_channels_last_cubes(X, Y, Z):
+        if self.training or torch.is_grad_enabled() or not self.fused_inference:
             return None
         w0 = self.front_layers[0].block[0].weight
+        if 17 <= int(cin) <= 32:      # opt-in: the spectrum of 17..32 channels, one unprojection launch per channel group
+            if not (getattr(self, "wide_front", False) and self.wants_planar_input() and getattr(self, "zdft", True) and w0.is_cuda
+                    and tuple(w0.shape[2:]) == (7, 7, 7)
+                    and _wide_front_ok(w0, self.front_layers[1].res_branch[0].weight, Z, _FoldedV2V._fft_shape(X, Y, Z, 7)[2])):
+                return None
+        elif not self.wants_channels_last_cubes(X, Y, Z):
+            return None
         S = _FoldedV2V._fft_shape(X, Y, Z, int(w0.shape[2]))
         if S[0] != 88 or S[1] != 88 or X % 4 or Y % 4 or int(w0.shape[1]) != int(cin) or w0.dtype != torch.float32:
             return None

@@ -6,6 +6,9 @@ For both rigs at B = 4, J = 17 (configs/campus_synthetic_coco17_cam3.yaml, confi
   (b) person_cubes     eight 64^3 person cubes through sample_of into the V2V plan's FFT input buffer vs planar cubes
   (c) root_graph       the graphed root-net forward (GraphedRootNet) with either unprojection
   (d) eval_frame       one eval frame from heat-maps: root net, then pose net on the proposals it found
+  (e) root_graph_channels_last   the graphed root net after use_channels_last(True) - the configuration validate_3d.py and
+                       bench.py run; (a)-(d) never call it, so their V2V stack is the planar library route - with the
+                       17..32-joint z-spectrum front (SP3D_WIDE_FRONT) off and on; --legs e, profiles/r20_coco17_wide_front.json
 Device events, warm-up first, then --iters timed iterations per leg; the two paths alternate in blocks of --block
 iterations inside one process.  bytes/s counts the algorithmic bytes 4 B (V J h w + J N) of (a) and (b).
 
@@ -68,6 +71,61 @@ class PlanarRoot(torch.nn.Module):
                                                 want_grids=False)
         root_cubes = r.v2v_net(cubes).squeeze(1)
         return root_cubes, r.proposal_layer(root_cubes, meta)
+
+
+def rig_inputs(name, dev, B):
+    """cfg, heat-maps of synthetic people on the device, meta - what every leg of a rig runs on"""
+    from selfpose3d_amd.synthetic_dataset import SyntheticPanoptic
+    from torch.utils.data import default_collate
+    # every proposal slot valid (random-init nets): (d) runs the pose net on B x 4 = 16 person cubes
+    cfg = load_config(os.path.join(ROOT, YAML[name]), MULTI_PERSON__THRESHOLD=-1e9, MULTI_PERSON__MAX_PEOPLE_NUM=4)
+    V = int(cfg.DATASET.CAMERA_NUM)
+    ds = SyntheticPanoptic(cfg, num_frames=B, seed=5, images=False)
+    items = [ds[i] for i in range(B)]
+    hms = [torch.stack([it[1][v] for it in items]).to(dev) for v in range(V)]
+    meta = [default_collate([it[4][v] for it in items]) for v in range(V)]
+    return cfg, ds, hms, meta
+
+
+def run_root_graph_channels_last(name, dev, iters, warmup, block, repeats=3, variant="both"):
+    """(e) the graphed root net in the configuration validate_3d.py and bench.py run - use_channels_last(True), which legs
+    (a)-(d) never call, so their V2V stack is the planar library route - with the 17..32-joint z-spectrum front
+    (SP3D_WIDE_FRONT: ProjectLayer.wide_zspectrum + V2VNet.wide_front) off and on.  Both graphs live in one process and
+    alternate in blocks (timed_pair); the pair is timed ``repeats`` times, and the largest difference between the
+    switched-on medians is the run-to-run spread.  Rule for a later default flip: the slowest
+    switched-on repeat is below the switched-off median by more than the spread, on both rigs."""
+    from selfpose3d_amd.cuboid_proposal_net import CuboidProposalNet
+    from selfpose3d_amd.graphs import GraphedRootNet
+    B = 4
+    cfg, ds, hms, meta = rig_inputs(name, dev, B)
+    torch.manual_seed(0)
+    root = CuboidProposalNet(cfg).eval().to(dev).use_channels_last(True)
+    static = [x.clone() for x in hms]
+
+    def graphed(on):
+        root.project_layer.wide_zspectrum = root.v2v_net.wide_front = on      # read while capturing
+        try:
+            return GraphedRootNet(root, static, meta)
+        finally:
+            root.project_layer.wide_zspectrum = root.v2v_net.wide_front = False
+    if variant != "both":       # one graph alone, for a kernel trace of its own (rocprofv3 --kernel-trace --stats)
+        g = graphed(variant == "on")
+        t, _ = timed_pair(lambda: g(), lambda: g(), iters, warmup, block)
+        return {"variant": variant, variant: stats(t)}
+    g_off, g_on = graphed(False), graphed(True)
+    a, b = g_off()[0].clone(), g_on()[0].clone()
+    torch.cuda.synchronize()
+    runs = []
+    for _ in range(repeats):
+        t_off, t_on = timed_pair(lambda: g_off(), lambda: g_on(), iters, warmup, block)
+        runs.append({"off": stats(t_off), "on": stats(t_on)})
+    on_med = [r["on"]["median_us"] for r in runs]
+    off_med = float(np.median([r["off"]["median_us"] for r in runs]))
+    spread = float(max(on_med) - min(on_med))
+    return {"repeats": runs, "off_median_us": off_med, "on_medians_us": on_med, "on_spread_us": spread,
+            "on_slowest_minus_off_us": float(max(on_med) - off_med),
+            "on_wins_by_more_than_the_spread": bool(max(on_med) < off_med - spread),
+            "root_cubes_max_abs_diff": float((a - b).abs().max()), "root_cubes_max_abs": float(a.abs().max())}
 
 
 def run_rig(name, dev, iters, warmup, block):
@@ -159,14 +217,24 @@ def main():
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--block", type=int, default=20)
     ap.add_argument("--rigs", default="campus,shelf")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r07_coco17.json"))
+    ap.add_argument("--legs", default="abcd,e", help="'abcd' (legs a-d), 'e' (the channels-last root graph), or both")
+    ap.add_argument("--e-variant", choices=["both", "off", "on"], default="both",
+                    help="leg e: 'off' / 'on' replays that graph alone (for a kernel trace of its own)")
+    ap.add_argument("--out", default=None, help="default: profiles/r07_coco17.json with legs a-d, else profiles/r20_coco17_wide_front.json")
     args = ap.parse_args()
+    legs = set(args.legs.split(","))
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "r07_coco17.json" if "abcd" in legs else "r20_coco17_wide_front.json")
     dev = torch.device("cuda:0")
     res = {"what": __doc__.strip().split("\n")[0], "device": torch.cuda.get_device_name(0), "iters": args.iters,
            "bytes_formula": "4*B*(V*J*h*w + J*N)", "rigs": {}}
     for name in args.rigs.split(","):
-        res["rigs"][name] = run_rig(name, dev, args.iters, args.warmup, args.block)
+        res["rigs"][name] = run_rig(name, dev, args.iters, args.warmup, args.block) if "abcd" in legs else {}
         print(json.dumps({name: {k: v.get("speedup") for k, v in res["rigs"][name].items() if isinstance(v, dict)}}), flush=True)
+        if "e" in legs:
+            e = res["rigs"][name]["e_root_graph_channels_last"] = run_root_graph_channels_last(
+                name, dev, args.iters, args.warmup, args.block, variant=args.e_variant)
+            print(json.dumps({name: {k: e[k] for k in ("off_median_us", "on_medians_us", "on_spread_us") if k in e}}), flush=True)
     os.makedirs(os.path.dirname(args.out), exist_ok=True)
     with open(args.out, "w") as f:
         json.dump(res, f, indent=1)
