@@ -126,7 +126,20 @@ enum {
      * SP3D_HM_BF16, SP3D_OUT_BF16, SP3D_HM_ONE_CHANNEL or SP3D_HM_WIDE_MASK next to it, for SP3D_LAYOUT_PLANAR, for any other
      * Jp, Z or X / Y, for a non-NULL grids, for a misaligned `cubes`, and for the flag on sp3d_unproject_fwd_strided,
      * sp3d_unproject_fwd_train and sp3d_unproject_one_fwd_train. */
-    SP3D_OUT_ZSPECTRUM = 0x2000
+    SP3D_OUT_ZSPECTRUM = 0x2000,
+    /* OR-ed into hm_layout of sp3d_unproject_fwd and sp3d_unproject_fwd_indexed ONLY: the one-channel read of
+     * SP3D_HM_ONE_CHANNEL (hm_views, the layout byte and Jp exactly as documented there; fp32 maps, 4-byte alignment) with the
+     * z-spectrum result of SP3D_OUT_ZSPECTRUM at J = 1: `cubes` receives (P, 1, SZ/2+1, X/4, Y/4, 16) complex64 with SZ = 28
+     * implied, layout and values as documented at sp3d_unproject_fwd_zdft below - bit-identical to sp3d_zdft_fwd_cl of the cubes
+     * SP3D_HM_ONE_CHANNEL writes; a cube that `valid` skips gets an all-zero spectrum.  One launch, no cubes, no grids, no
+     * pass mask (the root net of the ROOTNET_ROOTHM configurations, V2VNet(1, 1)).  Takes J == 1, Z == 20,
+     * X % 4 == Y % 4 == 0, heat-maps of 2x2 .. 2^24 pixels, grids == NULL and a 128-byte aligned `cubes`.  SP3D_EUNSUPPORTED,
+     * before any launch, for any other flag next to it (SP3D_OUT_CHANNELS_LAST, SP3D_HM_BF16, SP3D_OUT_BF16,
+     * SP3D_HM_ONE_CHANNEL, SP3D_HM_WIDE_MASK, SP3D_OUT_ZSPECTRUM), for any other J, Z or X / Y, for a non-NULL grids, for a
+     * misaligned `cubes`, for a sample of more than 2^31 bytes, and for the flag on sp3d_unproject_fwd_strided,
+     * sp3d_unproject_fwd_train and sp3d_unproject_one_fwd_train; SP3D_EINVAL for Jp < 1 and for a layout byte that is neither
+     * SP3D_LAYOUT_PLANAR nor SP3D_LAYOUT_NHWC. */
+    SP3D_HM_ONE_ZSPECTRUM = 0x4000
 };
 
 int sp3d_abi_version(void);

@@ -26,6 +26,7 @@ OUT_BF16 = 0x400
 HM_ONE_CHANNEL = 0x800      # one channel of a wider tensor, read in place (include/sp3d.h)
 HM_WIDE_MASK = 0x1000       # sp3d_unproject_fwd_train at Jp = 32: a (2, P, N) pass mask, one plane per channel group
 OUT_ZSPECTRUM = 0x2000      # sp3d_unproject_fwd[_indexed]: the root grid's cubes leave as their z-spectrum (Jp = 16 or 32)
+HM_ONE_ZSPECTRUM = 0x4000   # sp3d_unproject_fwd[_indexed]: one channel read in place, its cubes leave as their z-spectrum (J = 1)
 SCATTER_AUTO, SCATTER_PER_TAP, SCATTER_MERGE = 0, 2, 3      # include/sp3d.h: per-call scatter choice of unproject_bwd_packed
 SCATTER_WIDE = 0x100        # OR-ed into that choice: 17..32 joints, 32-element pixels, the two-plane mask
 MAX_VIEWS = 16
@@ -634,6 +635,30 @@ def unproject_fwd_zspectrum(views: Sequence[torch.Tensor], jp: int, cam: torch.T
     check(lib.sp3d_unproject_fwd(_ptr_array(views), LAYOUT_NHWC | OUT_ZSPECTRUM, jp, cam.data_ptr(), centers.data_ptr(),
                                  valid.data_ptr(), spec.data_ptr(), None, batch, len(views), J, h, w, X, Y, Z, _f3(grid_size),
                                  int(img_size[0]), int(img_size[1]), _stream(cam.device)), "sp3d_unproject_fwd (z-spectrum)")
+    return spec
+
+
+def unproject_one_fwd_zspectrum(views: Sequence[torch.Tensor], layout: int, jp: int, cam: torch.Tensor, centers: torch.Tensor,
+                                valid: torch.Tensor, batch: int, h: int, w: int, cube_size, grid_size, img_size, SZ: int, *,
+                                sample_of: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """the one-channel read of ``unproject_fwd(one_channel=True)`` (``views``, ``layout`` and ``jp`` as documented there) with
+    the result of ``unproject_fwd_zdft`` at J = 1 (SP3D_HM_ONE_ZSPECTRUM, include/sp3d.h): one launch, no cubes ->
+    (P, 1, SZ//2+1, X/4, Y/4, 16) complex64, P = ``batch`` cubes (``sample_of``: cube p reads sample sample_of[p])"""
+    lib = load()
+    _require_cam(cam)
+    X, Y, Z = (int(c) for c in cube_size)
+    for v in views:
+        _require_cuda(v, "heat-map view")
+        if v.dtype != torch.float32:
+            raise Sp3dError("unproject_one_fwd_zspectrum: fp32 heat-map views expected")
+    if (Z, int(SZ)) != (20, 28) or X % 4 or Y % 4:
+        raise Sp3dError("unproject_one_fwd_zspectrum: built for (Z, SZ) = (20, 28) and X, Y multiples of 4")
+    spec = _result_dense(out, (batch, 1, int(SZ) // 2 + 1, X // 4, Y // 4, 16), torch.complex64, cam.device,
+                         "unproject_one_fwd_zspectrum", 128)
+    check(lib.sp3d_unproject_fwd_indexed(_ptr_array(views), layout | HM_ONE_ZSPECTRUM, jp, cam.data_ptr(), _opt(sample_of),
+                                         centers.data_ptr(), valid.data_ptr(), spec.data_ptr(), None, batch, len(views), 1, h, w,
+                                         X, Y, Z, _f3(grid_size), int(img_size[0]), int(img_size[1]), _stream(cam.device)),
+          "sp3d_unproject_fwd_indexed (one-channel z-spectrum)")
     return spec
 
 

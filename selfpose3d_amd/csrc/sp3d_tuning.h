@@ -36,7 +36,9 @@ int sp3d_unproject_fwd_variant(const float *const *hm_views, int Jp, const float
  *                word `variant`, bit 24 included; `variant` is read for this entry only), _ONE_TRAIN
  *                (sp3d_unproject_one_fwd_train: SP3D_HM_ONE_CHANNEL implied, with a pass mask).  SP3D_OUT_ZSPECTRUM in
  *                hm_layout is planned for _INDEXED and refused for the other entries, as the entry points refuse it; _ZDFT
- *                refuses Jp != 16 as sp3d_unproject_fwd_zdft does
+ *                refuses Jp != 16 as sp3d_unproject_fwd_zdft does.  SP3D_HM_ONE_ZSPECTRUM likewise: planned for _INDEXED (one
+ *                launch of unproject_one_zd_kernel, P * (X/4) * (Y/4) workgroups of 320 threads, 1280 bytes of LDS), refused
+ *                for every other entry
  *   names        SP3D_PLAN_NAME bytes per launch: the kernel with its template arguments, as a kernel trace prints it
  *                without namespaces and parameter list
  *   fields       SP3D_PLAN_FIELDS int32 per launch: workgroups, workgroup size, dynamic LDS bytes, number of kernel

@@ -3,7 +3,7 @@
 //   sp3d_unproject_tile.hip   unproject_planar_kernel, pack_nhwc_kernel, unproject_nhwc_kernel; sp3d_pack_heatmaps[_ex]
 //   sp3d_unproject_pipe.hip   unproject_pipe_kernel
 //   sp3d_unproject_brick.hip  unproject_brick_kernel, unproject_brick_h_kernel
-//   sp3d_unproject_one.hip    unproject_one_kernel, unproject_one_bwd_kernel; sp3d_unproject_one_bwd[_det]
+//   sp3d_unproject_one.hip    unproject_one_kernel, unproject_one_zd_kernel, unproject_one_bwd_kernel; sp3d_unproject_one_bwd[_det]
 //   sp3d_unproject_bwd.hip    unproject_bwd_kernel, unproject_bwd2_kernel, unproject_bwd3_kernel; sp3d_unproject_bwd*
 // and this file reaches them through the kernel tables sp3d_unproject_host.h declares.
 //
@@ -87,6 +87,7 @@ struct FwdRequest {
     bool one, out_cl, zd, out_aligned;   // one-channel read; channels-last result; z-spectrum result; result 16-byte aligned
     bool one_train;      // one-channel read that also writes the pass mask (sp3d_unproject_one_fwd_train)
     bool wide_mask;      // SP3D_HM_WIDE_MASK: the pass mask has two planes of P * N words, one per channel group of Jp = 32
+    bool one_zd;         // SP3D_HM_ONE_ZSPECTRUM: the one-channel read with the z-spectrum result
     Geom g;
 };
 
@@ -189,6 +190,29 @@ static int resolve_one(const FwdRequest &rq, Launch &L)
     return find_one_kernel(KernelKey{1, 1, vt, vt > 8 ? 8 : 4, rq.out_cl, g.pass_mask ? 4 : 0}, L.fn, L.name);
 }
 
+// SP3D_HM_ONE_ZSPECTRUM (include/sp3d.h): the one-channel read with the z-spectrum result of the brick ZD form at J = 1,
+// unproject_one_zd_kernel.  One workgroup of ZDZ / BR waves per 4 x 4 tile of z columns, exactly P * tiles of them (the kernel
+// deals them to the XCDs itself), a slab of 16 x ZDZ floats of LDS.  Nothing may stand next to the flag.
+static int resolve_one_zd(const FwdRequest &rq, Launch &L)
+{
+    Geom &g = L.g;
+    if ((rq.layout != SP3D_LAYOUT_PLANAR && rq.layout != SP3D_LAYOUT_NHWC) || rq.Jp < 1) return SP3D_EINVAL;
+    if (rq.io || rq.one || rq.out_cl || rq.wide_mask || rq.zd || rq.one_train || g.pass_mask) return SP3D_EUNSUPPORTED;
+    if (g.J != 1 || g.Z != ZDZ || (g.X % BR) || (g.Y % BR) || !g.dense) return SP3D_EUNSUPPORTED;
+    if (g.w < 2 || g.h < 2 || (int64_t)g.h * g.w > (1 << 24)) return SP3D_EUNSUPPORTED;
+    const int64_t px = rq.layout == SP3D_LAYOUT_NHWC ? rq.Jp : 1, row = (int64_t)g.w * px;
+    // 24-bit multiplies form the tap offset, a 32-bit byte offset addresses it
+    if (row >= (1 << 24) || (int64_t)g.h * row * 4 > (int64_t)0x7fffffff) return SP3D_EUNSUPPORTED;
+    const int nby = g.Y / BR, tiles = (g.X / BR) * nby;
+    set_xcd_fields(g, tiles);
+    set_brick_fields(g, tiles, nby);
+    const int64_t sample = rq.layout == SP3D_LAYOUT_NHWC ? (int64_t)g.h * row : (int64_t)rq.Jp * g.h * g.w;
+    set_launch(L, (unsigned)(g.B * tiles), 64 * (ZDZ / BR), (size_t)16 * ZDZ * sizeof(float), 3, sample, (int)row, (int)px);
+    L.grids = false;
+    const int vt = g.V <= 6 ? g.V : (g.V <= 8 ? 8 : (g.V <= 10 ? 10 : (g.V <= 12 ? 12 : 16)));
+    return find_one_zd_kernel(KernelKey{1, 1, vt, vt > 8 ? 8 : 4, false, 8}, L.fn, L.name);
+}
+
 // Jp = 32 (17..32 joints: the 17 COCO joints of the Shelf / Campus configurations).  A packed fp32 pixel is exactly one
 // 128-byte line.  It is gathered as two channel groups, one launch each, both reading pixels at a stride of PS = 32:
 //   group 0   channels 0-15 through the JP = 16 kernel;
@@ -211,6 +235,7 @@ static int resolve_fwd(const FwdRequest &rq, FwdTuning t, Launch (&plan)[SP3D_PL
     Launch &L = plan[0];
     L = Launch{};
     L.g = rq.g; L.grid_y = 1; L.grids = !rq.zd;      // a z-spectrum launch writes no grids (its entries take none)
+    if (rq.one_zd) return resolve_one_zd(rq, L);
     // the two-plane mask belongs to the Jp = 32 training forward with a planar fp32 result, and to nothing else
     if (rq.wide_mask && (rq.one || !rq.g.pass_mask || rq.layout != SP3D_LAYOUT_NHWC || rq.Jp != WIDE_PS || rq.out_cl || rq.io))
         return SP3D_EUNSUPPORTED;
@@ -295,6 +320,7 @@ static int fwd_request(FwdRequest &rq, int hm_layout, int Jp, bool ptrs, int B, 
     rq.out_cl = (hm_layout & SP3D_OUT_CHANNELS_LAST) != 0;
     rq.wide_mask = (hm_layout & SP3D_HM_WIDE_MASK) != 0;
     rq.zd = (hm_layout & SP3D_OUT_ZSPECTRUM) != 0;
+    rq.one_zd = (hm_layout & SP3D_HM_ONE_ZSPECTRUM) != 0;
     rq.out_aligned = true; rq.one_train = false;
     return SP3D_OK;
 }
@@ -391,6 +417,10 @@ extern "C" int sp3d_unproject_fwd_indexed(const float *const *hm_views, int hm_l
     if (rc) return rc;
     rq.g.sample_of = sample_of;
     rq.out_aligned = ((uintptr_t)cubes & 15) == 0;
+    if (rq.one_zd) {    // SP3D_HM_ONE_ZSPECTRUM: `cubes` is the spectrum of the one channel, whole 128-byte lines, no grids
+        if (grids || ((uintptr_t)cubes & 127)) return SP3D_EUNSUPPORTED;
+        return run_fwd(rq, default_tuning(FWD_PIPE), hm_views, cam, centers, valid, cubes, nullptr, stream);
+    }
     if (rq.zd) {    // SP3D_OUT_ZSPECTRUM: `cubes` is the spectrum, whole 128-byte lines; the brick stacks as sp3d_unproject_fwd_zdft
         if (grids || ((uintptr_t)cubes & 127)) return SP3D_EUNSUPPORTED;
         return run_fwd(rq, default_tuning(FWD_BRICK_STACKS), hm_views, cam, centers, valid, cubes, nullptr, stream);
@@ -408,7 +438,7 @@ extern "C" int sp3d_unproject_fwd_strided(const float *const *hm_views, int hm_l
                          X, Y, Z, grid_size, W_in, H_in);
     if (rc) return rc;
     // the one-channel read takes either layout
-    if ((!rq.one && rq.layout != SP3D_LAYOUT_NHWC) || rq.out_cl || rq.zd || w < 2 || h < 2) return SP3D_EUNSUPPORTED;
+    if ((!rq.one && rq.layout != SP3D_LAYOUT_NHWC) || rq.out_cl || rq.zd || rq.one_zd || w < 2 || h < 2) return SP3D_EUNSUPPORTED;
     rc = set_result_strides(rq.g, out_strides, cubes);
     if (rc) return rc;
     rq.g.sample_of = sample_of;
@@ -461,7 +491,7 @@ extern "C" int sp3d_unproject_fwd_plan(int entry, int hm_layout, int Jp, const i
     if (!names || !fields || !tuning || !records) return SP3D_ENULL;
     if (entry < SP3D_PLAN_INDEXED || entry > SP3D_PLAN_ONE_TRAIN) return SP3D_EINVAL;
     const float grid_size[3] = {1.0f, 1.0f, 1.0f};
-    if (entry == SP3D_PLAN_ZDFT) hm_layout = SP3D_LAYOUT_NHWC | (hm_layout & SP3D_HM_WIDE_MASK);     // the entry has no layout word; the flag is kept to be refused
+    if (entry == SP3D_PLAN_ZDFT) hm_layout = SP3D_LAYOUT_NHWC | (hm_layout & (SP3D_HM_WIDE_MASK | SP3D_HM_ONE_ZSPECTRUM));     // the entry has no layout word; the flags are kept to be refused
     if (entry == SP3D_PLAN_TUNING) hm_layout = SP3D_LAYOUT_NHWC | ((variant & SP3D_TUNING_CHANNELS_LAST) ? SP3D_OUT_CHANNELS_LAST : 0);
     if (entry == SP3D_PLAN_ONE_TRAIN) hm_layout |= SP3D_HM_ONE_CHANNEL;
     FwdRequest rq;
@@ -469,7 +499,7 @@ extern "C" int sp3d_unproject_fwd_plan(int entry, int hm_layout, int Jp, const i
     if (!rc && entry == SP3D_PLAN_STRIDED && out_strides) rc = set_result_strides(rq.g, out_strides, nullptr);
     if (rc) return rc;
     // SP3D_OUT_ZSPECTRUM belongs to the indexed entry alone; sp3d_unproject_fwd_zdft keeps its own Jp == 16
-    if (rq.zd && entry != SP3D_PLAN_INDEXED) return SP3D_EUNSUPPORTED;
+    if ((rq.zd || rq.one_zd) && entry != SP3D_PLAN_INDEXED) return SP3D_EUNSUPPORTED;
     if (entry == SP3D_PLAN_ZDFT && Jp != 16) return SP3D_EUNSUPPORTED;
     rq.one_train = entry == SP3D_PLAN_ONE_TRAIN;
     if (entry == SP3D_PLAN_TRAIN || rq.one_train) rq.g.pass_mask = reinterpret_cast<uint16_t *>(records);    // "there is one": never dereferenced
@@ -507,7 +537,7 @@ extern "C" int sp3d_unproject_fwd_train(const float *const *hm_views, int hm_lay
     const int rc = fwd_request(rq, hm_layout, Jp, cam && centers && valid && cubes && pass_mask, P, V, J, h, w,
                                X, Y, Z, grid_size, W_in, H_in);
     if (rc) return rc;
-    if (rq.layout != SP3D_LAYOUT_NHWC || rq.io || rq.one || rq.zd || w < 2 || h < 2) return SP3D_EUNSUPPORTED;
+    if (rq.layout != SP3D_LAYOUT_NHWC || rq.io || rq.one || rq.zd || rq.one_zd || w < 2 || h < 2) return SP3D_EUNSUPPORTED;
     rq.g.sample_of = sample_of;
     rq.g.pass_mask = pass_mask;
     return run_fwd(rq, default_tuning(rq.g, rq.out_cl), hm_views, cam, centers, valid, cubes, grids, stream);
@@ -525,7 +555,7 @@ extern "C" int sp3d_unproject_one_fwd_train(const float *const *hm_views, int hm
     const int rc = fwd_request(rq, hm_layout | SP3D_HM_ONE_CHANNEL, Jp, cam && centers && valid && cubes && pass_mask, P, V,
                                J, h, w, X, Y, Z, grid_size, W_in, H_in);
     if (rc) return rc;
-    if (rq.zd) return SP3D_EUNSUPPORTED;
+    if (rq.zd || rq.one_zd) return SP3D_EUNSUPPORTED;
     rq.one_train = true;
     rq.g.sample_of = sample_of;
     rq.g.pass_mask = pass_mask;

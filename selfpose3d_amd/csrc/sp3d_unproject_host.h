@@ -86,7 +86,7 @@ inline int load_views(Views &v, const float *const *hm_views, int V)
 struct KernelKey {
     int jp, ps;          // channels gathered; channels between pixels
     int a, b;            // tile: XCD map, unroll; pipe: XCD map, waves; brick: z-spectrum, 0; one-channel: views, chunk; else 0, 0
-    int cl, io;          // channels-last result; FwdRequest::io (one-channel: 4 = the kernel that also writes the pass mask)
+    int cl, io;          // channels-last result; FwdRequest::io (one-channel: 4 = the kernel that also writes the pass mask, 8 = the z-spectrum form)
 };
 using PackFn = void (*)(Views, float *, int, int, int);
 using PlanarFn = void (*)(Views, const float *, const float *, const uint8_t *, float *, float *, Geom);
@@ -108,6 +108,7 @@ int find_tile_kernel(const KernelKey &key, const void *&fn, const char *&name);
 int find_pipe_kernel(const KernelKey &key, const void *&fn, const char *&name);
 int find_brick_kernel(const KernelKey &key, const void *&fn, const char *&name);
 int find_one_kernel(const KernelKey &key, const void *&fn, const char *&name);
+int find_one_zd_kernel(const KernelKey &key, const void *&fn, const char *&name);
 
 #ifdef SP3D_TIMELINE
 // measurement builds only: the timeline buffer is a __device__ variable, and one of those cannot cross files (the library

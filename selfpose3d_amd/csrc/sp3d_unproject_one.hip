@@ -1,9 +1,11 @@
-// sp3d_unproject_one.hip - the one-channel path (SP3D_HM_ONE_CHANNEL): unproject_one_kernel with its kernel table, and the
+// sp3d_unproject_one.hip - the one-channel path (SP3D_HM_ONE_CHANNEL): unproject_one_kernel with its kernel table, its
+// z-spectrum form unproject_one_zd_kernel (SP3D_HM_ONE_ZSPECTRUM, resolve_one_zd) with a table of its own, and the
 // backward of that channel, unproject_one_bwd_kernel behind sp3d_unproject_one_bwd[_det].  The forward entries are in
 // sp3d_unproject.hip (resolve_one).
 #include <type_traits>
 
 #include "sp3d_unproject_pipe.h"
+#include "sp3d_twiddles.h"
 
 namespace sp3d {
 
@@ -144,6 +146,136 @@ __global__ __launch_bounds__(64) void unproject_one_kernel(Views hm, const float
 }
 
 // ------------------------------------------------------------------------------------------
+// one channel in, z-spectrum out (SP3D_HM_ONE_ZSPECTRUM): unproject_one_kernel's read and arithmetic with the result of
+// unproject_brick_kernel<..., ZD> at J = 1 - the cubes are never written.  `cubes` is the (P, 1, K, X/4, Y/4, 16) complex
+// spectrum, K = ZDSZ/2+1; grids are not written (the entries refuse them), there is no pass mask.
+//
+// A workgroup owns one 4 x 4 tile of z columns over the whole z extent (Z == ZDZ == 20): 320 threads = 5 waves, wave = brick
+// of 4 z layers, lane = voxel with the brick kernel's mapping (lx = lane/16, ly = (lane/4)%4, lz = lane%4), so a wave's 64
+// voxels project onto neighbouring pixels.  X % 4 == Y % 4 == 0 and Z == 20 (resolve_one_zd): every lane has a voxel.
+// Per lane the chunked gather of unproject_one_kernel, operation for operation: project_pk / make_record_pk, CS views' taps in
+// flight while the next chunk is projected, the FMAs in view order, the wave-uniform view skip, fuse_rcp - the fused value has
+// the bits unproject_one_kernel gives (a view no voxel of the wave sees adds an exact zero there, so the different voxels a
+// wave holds change nothing for finite maps, as between the pipe and the brick kernels).  The gather is written out here a
+// second time on purpose: as a function both kernels call it changed the instructions of every unproject_one_kernel
+// instantiation (compared per kernel in the build's assembly), and those kernels are shipped as they are.
+// The 320 fused values go to a 16 x 20 float slab in LDS (pos * 20 + z: 64 distinct banks per wave on the way in, 16 distinct
+// 16-byte columns on the way out), one barrier, then 16 lanes run zdft_real<ZDZ, ZDSZ> on a column each - the table and FMA
+// order of zdft_fwd_cl_kernel and the brick kernel's ZD epilogue, hence their bits - and store K float2 apiece: 16 lanes x
+// 8 bytes = one whole 128-byte line per plane, at tile t = bx * (Y/4) + by whatever workgroup order the XCD map chose.
+// A sample that `valid` skips writes its K all-zero lines.
+//
+// blockIdx -> (sample, tile): the grid is exactly P * tiles workgroups; block bid runs on XCD bid % 8, and XCD x takes the
+// x-th eighth of the (sample, tile) sequence (tiles are x-major: a slab of the volume of one or two samples per XCD).
+// ------------------------------------------------------------------------------------------
+template <int VT, int CS>
+__global__ __launch_bounds__(64 * (ZDZ / BR)) void unproject_one_zd_kernel(Views hm, const float *__restrict__ cam,
+                                                                          const float *__restrict__ centers,
+                                                                          const uint8_t *__restrict__ valid,
+                                                                          float *__restrict__ cubes, float *__restrict__ grids,
+                                                                          Geom g, long long s_sample, int s_row, int s_px)
+{
+    constexpr int NCH = (VT + CS - 1) / CS;
+    constexpr int K = ZDSZ / 2 + 1;
+    extern __shared__ __attribute__((aligned(16))) float slab[];       // 16 columns x ZDZ floats (resolve_one_zd)
+    (void)grids;
+    // the x-th eighth of the g.B * g.xm_tiles (sample, tile) pairs, the first `total % 8` eighths one pair longer
+    const int total = g.B * g.xm_tiles, xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
+    const int lin = xcd * (total >> 3) + min(xcd, total & 7) + slot;
+    int b, t;
+    udiv_magic((uint32_t)lin, (uint32_t)g.xm_tiles, g.xm_magic_tiles, b, t);
+    int bx, by;
+    udiv_magic((uint32_t)t, (uint32_t)g.bk_nby, g.bk_magic_nby, bx, by);
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    float2 *o = reinterpret_cast<float2 *>(cubes) + ((size_t)b * K * (size_t)g.xm_tiles + (size_t)t) * 16 + tid;
+    const size_t kstride = (size_t)g.xm_tiles * 16;
+    if (!valid[b]) {                                // skipped sample: its all-zero spectrum lines
+        if (tid < 16) {
+#pragma unroll
+            for (int k = 0; k < K; ++k) o[(size_t)k * kstride] = make_float2(0.0f, 0.0f);
+        }
+        return;
+    }
+    const int bs = g.sample_of ? g.sample_of[b] : b;
+    const int lx = lane >> 4, ly = (lane >> 2) & 3, lz = lane & 3;
+    const int vx = bx * BR + lx, vy = by * BR + ly, vz = wave * BR + lz;
+    {
+        const float x = linspace_step(g.Lx, g.stepx, g.X, vx) + centers[3 * b + 0];
+        const float y = linspace_step(g.Ly, g.stepy, g.Y, vy) + centers[3 * b + 1];
+        const float z = linspace_step(g.Lz, g.stepz, g.Z, vz) + centers[3 * b + 2];
+        const unsigned long long inbm = ~0ull;      // every lane has a voxel
+        uint32_t mymask = 0;                        // views that see MY voxel (+ bit 31: NaN position)
+        uint32_t have = 0;                          // wave-uniform: views with a record (some voxel of the wave sees them)
+        uint32_t off[VT];                           // byte offset of the 2x2 block inside the sample's image
+        float w00[VT], w10[VT], w01[VT], w11[VT];
+        float t00[VT], t10[VT], t01[VT], t11[VT];
+        const size_t pxb = (size_t)s_px * sizeof(float), rowb = (size_t)s_row * sizeof(float);
+#pragma unroll
+        for (int ch = 0; ch < NCH; ++ch) {
+#pragma unroll
+            for (int c = ch * CS; c < (ch + 1) * CS && c < VT; ++c) {
+                off[c] = 0u;
+                w00[c] = w10[c] = w01[c] = w11[c] = 0.0f;
+                if (c < g.V) {
+                    const float *cm = cam + ((size_t)bs * g.V + c) * SP3D_CAM_STRIDE;
+                    P1State st;
+                    const bool go = project_pk(cm, g, x, y, z, inbm, st);
+                    add_mask(mymask, st.bm);
+                    if (st.nm != 0ull && lane_of(st.nm)) mymask |= 0x80000000u;
+                    const unsigned long long um = st.bm & ~st.nm;
+                    if (go && um != 0ull) {         // else: no voxel of this wave sees camera c
+                        const RecPk r = make_record_pk(lane_of(um), st.i, g.w, g.h);
+                        off[c] = (__umul24((unsigned)r.y0, (unsigned)s_row) + __umul24((unsigned)r.x0, (unsigned)s_px)) << 2;
+                        w00[c] = r.wt.x; w10[c] = r.wt.y; w01[c] = r.wb.x; w11[c] = r.wb.y;
+                        have |= 1u << c;
+                    }
+                }
+            }
+            __builtin_amdgcn_sched_barrier(0);
+            // the chunk's taps as unproject_one_kernel issues them: wave-uniform bases, one 32-bit byte offset per lane, no
+            // branch between the loads, in the reverse of the order the interpolation consumes them
+#pragma unroll
+            for (int c = min((ch + 1) * CS, VT) - 1; c >= ch * CS; --c) {
+                const char *vb = reinterpret_cast<const char *>((c < g.V ? hm.p[c] : hm.p[0]) + (ptrdiff_t)bs * s_sample);
+                const char *vb2 = vb + rowb;
+                t11[c] = *reinterpret_cast<const float *>(vb2 + pxb + off[c]);
+                t01[c] = *reinterpret_cast<const float *>(vb2 + off[c]);
+                t10[c] = *reinterpret_cast<const float *>(vb + pxb + off[c]);
+                t00[c] = *reinterpret_cast<const float *>(vb + off[c]);
+            }
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        float acc = 0.0f;
+#pragma unroll
+        for (int c = 0; c < VT; ++c) {
+            // ATen's bilinear chain: fma(se, wse, fma(sw, wsw, fma(ne, wne, nw * wnw)))
+            float v = t00[c] * w00[c];
+            v = fmaf(t10[c], w10[c], v);
+            v = fmaf(t01[c], w01[c], v);
+            v = fmaf(t11[c], w11[c], v);
+            const float a = acc + v;
+            acc = ((have >> c) & 1u) ? a : acc;     // wave-uniform, as the pipelined kernels skip such a view
+        }
+        // view fusion (project_layer.py:96-99): den = #views seeing the voxel + 1e-6; NaN sample position -> 0
+        const float den = (float)(mymask & 0x7fffffffu) + 1e-6f;
+        const float rden = (mymask & 0x80000000u) ? 0.0f : 1.0f / den;
+        slab[(lane >> 2) * ZDZ + wave * BR + lz] = fuse_rcp(acc, den, rden);
+    }
+    __syncthreads();
+    if (tid >= 16) return;
+    float v[ZDZ];
+#pragma unroll
+    for (int wz = 0; wz < ZDZ / BR; ++wz) {
+        const float4 q4 = *reinterpret_cast<const float4 *>(slab + tid * ZDZ + wz * BR);
+        v[4 * wz] = q4.x; v[4 * wz + 1] = q4.y; v[4 * wz + 2] = q4.z; v[4 * wz + 3] = q4.w;
+    }
+    float re[K], im[K];
+    zdft_real<ZDZ, ZDSZ>(v, re, im);
+#pragma unroll
+    for (int k = 0; k < K; ++k) o[(size_t)k * kstride] = make_float2(re[k], im[k]);
+}
+
+// ------------------------------------------------------------------------------------------
 // one-channel backward (sp3d_unproject_one_bwd[_det]): the scatter of bwd2 for ONE gradient channel, into dense (V,B,h,w)
 // planes instead of channel 0 of 16-byte pixels.  bwd2<4> runs this case on 16 of its 64 lanes and three of every four
 // atomics it issues add the zero gradient of a pad channel; here lane = voxel throughout and every atomic carries a value.
@@ -233,6 +365,15 @@ int find_one_kernel(const KernelKey &key, const void *&fn, const char *&name)
 {
     SP3D_ONE(1, 4) SP3D_ONE(2, 4) SP3D_ONE(3, 4) SP3D_ONE(4, 4) SP3D_ONE(5, 4) SP3D_ONE(6, 4) SP3D_ONE(8, 4) SP3D_ONE(10, 8)
     SP3D_ONE(12, 8) SP3D_ONE(16, 8)
+    return SP3D_EUNSUPPORTED;
+}
+
+// the z-spectrum form (SP3D_HM_ONE_ZSPECTRUM): the same view slots and chunks; key.io = 8
+#define SP3D_ONE_ZD(VT_, CS_) SP3D_ROW(OneFn, (KernelKey{1, 1, VT_, CS_, false, 8}), unproject_one_zd_kernel, VT_, CS_)
+int find_one_zd_kernel(const KernelKey &key, const void *&fn, const char *&name)
+{
+    SP3D_ONE_ZD(1, 4) SP3D_ONE_ZD(2, 4) SP3D_ONE_ZD(3, 4) SP3D_ONE_ZD(4, 4) SP3D_ONE_ZD(5, 4) SP3D_ONE_ZD(6, 4) SP3D_ONE_ZD(8, 4)
+    SP3D_ONE_ZD(10, 8) SP3D_ONE_ZD(12, 8) SP3D_ONE_ZD(16, 8)
     return SP3D_EUNSUPPORTED;
 }
 

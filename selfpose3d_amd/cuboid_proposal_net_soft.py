@@ -64,7 +64,16 @@ class CuboidProposalNetSoft(nn.Module):
         return self
 
     # -- shared: heat-maps -> root cubes ---------------------------------------------------------------
-    def _root_cubes(self, hms, meta, flip_xcoords):
+    def _root_cubes(self, hms, meta, flip_xcoords, one_front=False):
+        # opt-in (SP3D_ONE_FRONT=1), ROOTNET_ROOTHM inference: the one channel read where it lies, its z-spectrum straight into
+        # the opening conv (cuboid_proposal_net.one_front_route); anything else runs the code below as before
+        from .cuboid_proposal_net import one_front_route
+        if one_front and one_front_route(self, hms):     # (the synthetic-root branch never asks)
+            from .v2v_net import TiledZSpectrum
+            sz = self.v2v_net.wants_zspectrum(*self.cube_size, 1)
+            spec = self.project_layer.get_voxel_zspectrum(hms, meta, self.grid_size, [self.grid_center], self.cube_size, sz,
+                                                          flip_xcoords=flip_xcoords)
+            return self.v2v_net(TiledZSpectrum(spec, *self.cube_size, sz)).squeeze(1)
         planar = self.v2v_net.wants_planar_input() and hms[0].is_cuda      # FFT opening conv: plain J-channel cubes
         out = self.v2v_net.input_view(hms[0].shape[0], *self.cube_size, hms[0].device) \
             if planar and nhwc_direct_ok(hms, self.project_layer) and not torch.is_grad_enabled() else None
@@ -78,7 +87,7 @@ class CuboidProposalNetSoft(nn.Module):
             hms = [a[:, self.root_id:self.root_id + 1] for a in all_heatmaps]      # a view: read in place with ProjectLayer.one_channel, copied otherwise
         else:
             hms = all_heatmaps
-        root_cubes = self._root_cubes(hms, meta, flip_xcoords)
+        root_cubes = self._root_cubes(hms, meta, flip_xcoords, one_front=True)
         return root_cubes, self.proposal_layer(root_cubes, meta, None)
 
     # -- synthetic-root branch (training) ---------------------------------------------------------------

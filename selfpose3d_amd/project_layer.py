@@ -316,6 +316,11 @@ class ProjectLayer(nn.Module):
         # 17..32 joints - two launches, one per channel group of the 32-float pixel, into one z-spectrum - instead of raising.
         # Off until tools/bench_coco17.py has recorded that the root net is faster with it on both rigs
         self.wide_zspectrum = _lib.env_switch("SP3D_WIDE_FRONT", False)
+        # opt-in (SP3D_ONE_FRONT=1 / ``one_zspectrum = True``, with ``V2VNet.one_front``): ``get_voxel_zspectrum`` also takes a
+        # (B,1,h,w) list that is one channel of a wider tensor (one_channel_source) - read in place, one launch, the z-spectrum
+        # of the one channel (SP3D_HM_ONE_ZSPECTRUM) - instead of raising.  Off until tools/bench_roothm_front.py has recorded
+        # that the ROOTNET_ROOTHM root net is faster with it
+        self.one_zspectrum = _lib.env_switch("SP3D_ONE_FRONT", False)
 
     @contextlib.contextmanager
     def static_camera_table(self, table: torch.Tensor):
@@ -449,7 +454,10 @@ class ProjectLayer(nn.Module):
         """Inference only, root grid only (round 6): ``get_voxel`` FUSED with the z pass of the V2V net's frequency-domain
         opening conv - the cubes are never written.  Returns the (B, J, SZ//2+1, X/4, Y/4, 16) complex64 z-spectrum of the
         cubes ``get_voxel`` would return (bit-identical to ``_lib.zdft_fwd_cl`` of its channels-last result), in the
-        4 x 4-tiled layout ``_lib.cfft2d_88_tiled`` reads.  Same reference semantics (project_layer.py:42-102)."""
+        4 x 4-tiled layout ``_lib.cfft2d_88_tiled`` reads.  Same reference semantics (project_layer.py:42-102).
+        13..16 joints; 17..32 with ``wide_zspectrum``; with ``one_zspectrum`` a ``list[V] of (B,1,h,w)`` that
+        ``one_channel_source`` classifies (a slice of a planar tensor, a slice of the (V,B,h,w,16|32) buffer of
+        ``PoseResNet.forward_views``, a contiguous (B,1,h,w)), read in place."""
         if torch.is_grad_enabled() and any(h.requires_grad for h in heatmaps):
             raise _lib.Sp3dError("get_voxel_zspectrum is an inference path (no autograd); use get_voxel")
         device = heatmaps[0].device
@@ -460,10 +468,19 @@ class ProjectLayer(nn.Module):
             raise _lib.Sp3dError(f"heat-map tensor is {w}x{h} but cfg.NETWORK.HEATMAP_SIZE is {self.heatmap_size}")
         jp = self.jp_for(J)
         wide = self.wide_zspectrum and jp == 32 and J <= 32
-        if self.io_dtype != torch.float32 or not (jp == 16 or wide) or self.mode not in ("auto", "nhwc") or w < 2 or h < 2:
+        # one channel of a wider tensor (the ROOTNET_ROOTHM root nets): strides are looked at only here, behind every refusal
+        # that shapes alone decide
+        one = one_channel_source(heatmaps) if (self.one_zspectrum and J == 1 and self.io_dtype == torch.float32 and w >= 2
+                                               and h >= 2 and self.mode in ("auto", "nhwc")) else None
+        if one is None and (self.io_dtype != torch.float32 or not (jp == 16 or wide) or self.mode not in ("auto", "nhwc")
+                            or w < 2 or h < 2):
             raise _lib.Sp3dError("get_voxel_zspectrum: fp32 NHWC path with 13..16 joints only")
         cam = self.camera_table(meta, B, flip_xcoords, device)
         centers, valid = self.centers_valid(grid_center, B, device)
+        if one is not None:     # read where it lies: no slice copy, no re-tiling pass, no pack-cache entry
+            return _lib.unproject_one_fwd_zspectrum([x.detach() for x in heatmaps], one[0], one[1], cam, centers, valid, B, h, w,
+                                                    [int(v) for v in cube_size], [float(v) for v in grid_size], self.img_size,
+                                                    int(SZ))
         source = _packed_source(heatmaps, jp, torch.float32)
         if source is not None:
             packed = source.detach()

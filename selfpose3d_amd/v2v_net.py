@@ -116,6 +116,16 @@ def _wide_front_ok(w0, w1, Z, SZ) -> bool:
                 and is_cl(w1))
 
 
+def _one_front_ok(w0, w1, Z, SZ) -> bool:
+    """the static conditions of the z-spectrum form of the opening conv at ONE input channel (``V2VNet.one_front``, the
+    ROOTNET_ROOTHM root nets): as _wide_front_ok, with a 7x7x7 weight of one input channel - the spectrum arrives from the
+    one-channel unprojection (SP3D_HM_ONE_ZSPECTRUM).  Nothing else reads this predicate: one-channel cubes keep the route
+    they take today (_zdft_ok asks for 16-channel cubes, so they run the library's 3-D transforms)"""
+    from . import _lib
+    return bool((int(Z), int(SZ), 16) in _lib.ZDFT_SHAPES and int(w0.shape[0]) == 16 and int(w0.shape[1]) == 1
+                and tuple(w0.shape[2:]) == (7, 7, 7) and is_cl(w1))
+
+
 class _FreqConv3d(torch.autograd.Function):
     """Stride-1 'same' Conv3d (odd cubic kernel) in the frequency domain, forward AND backward, for the 7x7x7 opening
     conv of the V2V nets (v2v_net.py:113-117) on the GPU: zero-padded rFFT (rocFFT through torch.fft) -> channel
@@ -728,6 +738,9 @@ class V2VNet(nn.Module):
         # opt-in (SP3D_WIDE_FRONT=1): at 17..32 input channels the opening conv may start from the unprojection's z-spectrum too
         from . import _lib
         self.wide_front = _lib.env_switch("SP3D_WIDE_FRONT", False)
+        # opt-in (SP3D_ONE_FRONT=1): at ONE input channel (ROOTNET_ROOTHM) the opening conv may start from the z-spectrum of the
+        # one-channel unprojection instead of cubes through the library's 3-D transforms
+        self.one_front = _lib.env_switch("SP3D_ONE_FRONT", False)
         self._plan = None
         self.reset_parameters()
 
@@ -815,7 +828,9 @@ class V2VNet(nn.Module):
         """SZ when the next inference forward can start from the cubes' z-spectrum (``TiledZSpectrum``: the unprojection
         fused with the opening conv's z pass, root grid), else None.  ``fuse_zdft`` (default on; SP3D_FUSE_ZDFT=0 turns it
         off for A/B) and the conditions of the direct z-DFT form + 88 x 88 planes + a float32 inference plan.  With
-        ``wide_front`` (default off; SP3D_WIDE_FRONT=1) it also answers for 17 <= cin <= 32 (_wide_front_ok)."""
+        ``wide_front`` (default off; SP3D_WIDE_FRONT=1) it also answers for 17 <= cin <= 32 (_wide_front_ok), with
+        ``one_front`` (default off; SP3D_ONE_FRONT=1) for cin == 1 (_one_front_ok); without it cin == 1 is None - no
+        unprojection delivers the spectrum of one channel otherwise."""
         from . import _lib
         if not getattr(self, "fuse_zdft", _lib.env_switch("SP3D_FUSE_ZDFT", True)):
             return None
@@ -826,6 +841,10 @@ class V2VNet(nn.Module):
             if not (getattr(self, "wide_front", False) and self.wants_planar_input() and getattr(self, "zdft", True) and w0.is_cuda
                     and tuple(w0.shape[2:]) == (7, 7, 7)
                     and _wide_front_ok(w0, self.front_layers[1].res_branch[0].weight, Z, _FoldedV2V._fft_shape(X, Y, Z, 7)[2])):
+                return None
+        elif int(cin) == 1:           # opt-in: the spectrum of the one channel of the ROOTNET_ROOTHM root nets, one launch
+            if not (getattr(self, "one_front", False) and self.wants_planar_input() and getattr(self, "zdft", True) and w0.is_cuda
+                    and _one_front_ok(w0, self.front_layers[1].res_branch[0].weight, Z, _FoldedV2V._fft_shape(X, Y, Z, 7)[2])):
                 return None
         elif not self.wants_channels_last_cubes(X, Y, Z):
             return None
