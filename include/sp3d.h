@@ -534,7 +534,15 @@ int sp3d_wino_fused_split(const float *x, const void *U3, float *y, const float 
 
 /* The same scheme for the half-resolution layers (C = 32 | 64 -> O = 64): blocks of 4x4x1 tiles x 64 outputs on
  * v_mfma_f32_16x16x32_bf16, 16-channel chunks.  U3 records [mid(4ch) hi(4ch) lo(4ch)] at index
- * ((p*(C/16) + chunk)*4 + group)*64 + o, channel = 16*chunk + 4*group + q (_lib.wino_weights_split(U, 16)). */
+ * ((p*(C/16) + chunk)*4 + group)*64 + o, channel = 16*chunk + 4*group + q (_lib.wino_weights_split(U, 16)).
+ *
+ * SP3D_CONV3_WINO_YZ OR-ed into `mode` (and into `CS` of sp3d_wino_fused_split64_skip, which has no mode): Winograd F(2x2,3x3)
+ * in y and z only, a plain 3-tap convolution along x.  U3 then holds 48 points instead of 64, p = dx*16 + j*4 + k: the
+ * weights transformed with G along y and z and left raw along x (tap dx), same records and index rule
+ * (_lib.wino_yz_weights_split).  The same 36 matrix instructions per step; the x input transform, the sign flips of the
+ * weights and a quarter of the weight loads are gone.  Arguments, checks and return codes are those of the entry without
+ * the bit (a mode outside 0..3 once the bit is taken off: SP3D_EINVAL); no other entry takes the bit. */
+#define SP3D_CONV3_WINO_YZ 0x100
 int sp3d_wino_fused_split64(const float *x, const void *U3, float *y, const float *shift, const float *residual, int mode,
                             int B, int X, int Y, int Z, int C, int O, void *stream);
 

@@ -29,6 +29,7 @@ OUT_ZSPECTRUM = 0x2000      # sp3d_unproject_fwd[_indexed]: the root grid's cube
 HM_ONE_ZSPECTRUM = 0x4000   # sp3d_unproject_fwd[_indexed]: one channel read in place, its cubes leave as their z-spectrum (J = 1)
 SCATTER_AUTO, SCATTER_PER_TAP, SCATTER_MERGE = 0, 2, 3      # include/sp3d.h: per-call scatter choice of unproject_bwd_packed
 SCATTER_WIDE = 0x100        # OR-ed into that choice: 17..32 joints, 32-element pixels, the two-plane mask
+CONV3_WINO_YZ = 0x100       # OR-ed into the mode of sp3d_wino_fused_split64 / the CS of its _skip form: Winograd in y,z, direct in x
 MAX_VIEWS = 16
 MAX_TOPK = 32
 ABI_VERSION = 3
@@ -954,6 +955,25 @@ def wino_weights_split(U: torch.Tensor, chunk: int = 8) -> torch.Tensor:
     return pieces.permute(1, 2, 3, 5, 0, 4).contiguous()                                  # [p, chunk, group, o, piece, q]
 
 
+def wino_yz_weights(w: torch.Tensor) -> torch.Tensor:
+    """(O,C,3,3,3) conv weights -> (48, C, O): G g G^T along y and z only, raw along x; point = dx*16 + j*4 + k.  Computed in
+    float64 and rounded to fp32 once, as wino_weights does"""
+    G = torch.tensor(_WINO_G, dtype=torch.float64, device=w.device)
+    u = torch.einsum("bj,ck,ozijk->ibczo", G, G, w.double())
+    return u.reshape(48, w.shape[1], w.shape[0]).float().contiguous()
+
+
+def wino_yz_weights_split(w: torch.Tensor) -> torch.Tensor:
+    """(64,C,3,3,3) conv weights, C = 32 | 64 -> what sp3d_wino_fused_split64 reads under CONV3_WINO_YZ: the 24-byte records
+    of wino_weights_split(., 16), (48, C/16, 4, 64, 3, 4) bfloat16, for the 48 points of wino_yz_weights"""
+    return wino_weights_split(wino_yz_weights(w), 16)
+
+
+def wino_yz_enabled() -> bool:
+    """SP3D_WINO_YZ=0 keeps the half-resolution layers on the 64-point form of wino_fused16_kernel (x transformed too)"""
+    return env_switch("SP3D_WINO_YZ", True)
+
+
 def conv_weights_split(w: torch.Tensor) -> torch.Tensor:
     """(O,C,3,3,3) conv weights -> the bf16 operand records sp3d_conv3_split reads: (27, C/8, 2, O, 6, 4) bfloat16 = the
     three B operands {hi,lo} {hi,hi} {mid,mid} of 4 channels each, tap = kz*9 + ky*3 + kx, channel = 8*chunk + 4*half + q.
@@ -1089,11 +1109,13 @@ def wino_conv3d_(x: torch.Tensor, U: torch.Tensor, shift: torch.Tensor, mode: in
 def wino_fused_conv3d_(x: torch.Tensor, U: torch.Tensor, shift: torch.Tensor, mode: int,
                        residual: Optional[torch.Tensor] = None, U3: Optional[torch.Tensor] = None, *,
                        xs: Optional[torch.Tensor] = None, skip_w: Optional[torch.Tensor] = None,
-                       out: Optional[torch.Tensor] = None) -> torch.Tensor:
+                       U3yz: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """one-launch Winograd 3x3x3 conv (C = 16 | 32 -> O = 32; with U3 also C = 32 | 64 -> O = 64) of channels_last_3d x
     with the fused epilogue; with U3 (wino_weights_split(U, 8 | 16)) the products run as exact three-piece bf16 splits
     on the bf16 matrix pipe.  With U3, xs (B,32,X,Y,Z) and skip_w = wino_weights_split of the (1,32,64) skip weight, chunk 16
     (C = O = 64): relu(conv3(x) + skip_w . xs + shift) in the same kernel (sp3d_wino_fused_split64_skip; mode 1, no residual).
+    U3yz (wino_yz_weights_split(w); O = 64, next to U3): the same layer with Winograd in y and z only and the three x taps
+    convolved directly - taken instead of U3 unless SP3D_WINO_YZ=0, which runs the U3 form bit for bit.
     The result is written into ``out`` when given."""
     lib = load()
     _require_cuda(x, "x")
@@ -1101,13 +1123,20 @@ def wino_fused_conv3d_(x: torch.Tensor, U: torch.Tensor, shift: torch.Tensor, mo
     _require_cl3d_f32(x, "wino_fused_conv3d_")
     O = int(U.shape[2])
     y = _result_cl3d(out, B, O, X, Y, Z, x, "wino_fused_conv3d_")
+    yz = 0
+    if U3yz is not None and U3 is not None and O == 64 and wino_yz_enabled():
+        # the kernel reads 48 * C * 64 pieces of three bf16 behind this pointer: refuse anything that is not exactly that
+        if U3yz.device != x.device or U3yz.dtype != torch.bfloat16 or not U3yz.is_contiguous() or U3yz.numel() != 48 * Cc * O * 3:
+            raise Sp3dError(f"wino_fused_conv3d_: U3yz must be wino_yz_weights_split of the ({O}, {Cc}, 3, 3, 3) weight on {x.device}; "
+                            f"got {tuple(U3yz.shape)}, {U3yz.dtype}, {U3yz.device}, contiguous={U3yz.is_contiguous()}")
+        U3, yz = U3yz, CONV3_WINO_YZ
     if xs is not None or skip_w is not None:
         if xs is None or skip_w is None or U3 is None or int(mode) != 1 or residual is not None:
             raise Sp3dError("wino_fused_conv3d_: the folded skip takes U3, xs AND skip_w, mode 1 and no residual")
         CS = 32
         _require_skip(xs, skip_w, x, CS, CS * O * 3, "wino_fused_conv3d_")
         check(lib.sp3d_wino_fused_split64_skip(x.data_ptr(), U3.data_ptr(), y.data_ptr(), shift.data_ptr(), xs.data_ptr(),
-                                               skip_w.data_ptr(), B, X, Y, Z, Cc, O, CS, _stream(x.device)),
+                                               skip_w.data_ptr(), B, X, Y, Z, Cc, O, CS | yz, _stream(x.device)),
               "sp3d_wino_fused_split64_skip")
         return y
     if residual is not None:
@@ -1116,7 +1145,7 @@ def wino_fused_conv3d_(x: torch.Tensor, U: torch.Tensor, shift: torch.Tensor, mo
         name, weights = "sp3d_wino_fused", U
     else:
         name, weights = ("sp3d_wino_fused_split64" if O == 64 else "sp3d_wino_fused_split"), U3
-    check(getattr(lib, name)(x.data_ptr(), weights.data_ptr(), y.data_ptr(), shift.data_ptr(), _opt(residual), int(mode),
+    check(getattr(lib, name)(x.data_ptr(), weights.data_ptr(), y.data_ptr(), shift.data_ptr(), _opt(residual), int(mode) | yz,
                              B, X, Y, Z, Cc, O, _stream(x.device)), name)
     return y
 

@@ -479,7 +479,13 @@ __device__ __forceinline__ f32x4 mfma16_bf16(u32x4 a, u32x4 b, f32x4 c)
 // WS = [mid hi lo] records of one point [chunk 2][group 4][output 64].  Channel group kg takes skip chunk kg before the LDS
 // reduction, when the registers of the main loop are free: lane (tl, q) supplies A row = tile tl, channels 16 kg + 4 q .. + 3
 // of voxel (tile, a) - 8 rows, 8 splits and 48 matrix instructions per wave.
-template <int C, int MODE, int NBW, int KS, bool SKIP = false>
+// XD: Winograd in y and z only, the x axis as a plain 3-tap convolution.  The x part of F(2,3) buys nothing in this kernel: its
+// output side is already folded into the accumulation, where the two outputs of an x pair cost six operand triples for
+// four points - exactly what M0 += g0.W0 + g1.W1 + g2.W2, M1 += g1.W0 + g2.W1 + g3.W2 costs on the y,z-transformed values
+// g[0..3] themselves.  So the 36 matrix instructions of a step stay, and the x input transform (16 add/sub), the sign
+// flips of the weights (8 XOR per output block) and one weight record in four leave it: U3 holds 48 points dx*16 + jk
+// (_lib.wino_yz_weights_split: G along y and z, raw along x) instead of 64.
+template <int C, int MODE, int NBW, int KS, bool SKIP = false, bool XD = false>
 __global__ __launch_bounds__(64 * (4 / NBW) * KS) __attribute__((amdgpu_waves_per_eu(NBW <= 2 ? 2 : 1))) void wino_fused16_kernel(const float *__restrict__ x,
                                                                           const unsigned *__restrict__ U3,
                                                                           float *__restrict__ y, const float *__restrict__ shift,
@@ -563,11 +569,12 @@ __global__ __launch_bounds__(64 * (4 / NBW) * KS) __attribute__((amdgpu_waves_pe
         for (int jk = 0; jk < 16; ++jk) {
             const int j = jk >> 2, k = jk & 3;
             // this step's weights: in flight while the operands are built (~1000 cycles)
-            WfB bw[NBW][4];
+            constexpr int NXP = XD ? 3 : 4;         // records per step and output block: x taps (XD) or x points
+            WfB bw[NBW][NXP];
 #pragma unroll
             for (int n = 0; n < NBW; ++n)
 #pragma unroll
-                for (int i = 0; i < 4; ++i) {
+                for (int i = 0; i < NXP; ++i) {
 #if SP3D_W16_ABLATE & 2
                     bw[n][i].mh = u32x4{0x3f803f80u + (unsigned)(jk + n), 0x3f803f80u, 0x3f803f80u + (unsigned)i, 0x3f803f80u};
                     bw[n][i].l = u32x2{0x3f803f80u, 0x3f803f80u};
@@ -612,7 +619,8 @@ __global__ __launch_bounds__(64 * (4 / NBW) * KS) __attribute__((amdgpu_waves_pe
                 float av[4];
 #pragma unroll
                 for (int kk = 0; kk < 4; ++kk)
-                    av[kk] = (i == 1) ? g[1][kk] + g[2][kk] : ((i == 3) ? g[3][kk] - g[1][kk] : g[wf_ta(i)][kk] - g[wf_tb(i)][kk]);
+                    av[kk] = XD ? g[i][kk]
+                                : ((i == 1) ? g[1][kk] + g[2][kk] : ((i == 3) ? g[3][kk] - g[1][kk] : g[wf_ta(i)][kk] - g[wf_tb(i)][kk]));
                 const unsigned hi01 = pack_bf16(av[0], av[1]), hi23 = pack_bf16(av[2], av[3]);
 #if SP3D_W16_ABLATE & 4
                 const unsigned mid01 = hi01, mid23 = hi23, lo01 = hi01, lo23 = hi23;
@@ -623,9 +631,27 @@ __global__ __launch_bounds__(64 * (4 / NBW) * KS) __attribute__((amdgpu_waves_pe
                 const unsigned lo23 = pack_bf16(r2 - bf16_lo(mid23), r3 - bf16_hi(mid23));
 #endif
                 const u32x4 Qhh = {hi01, hi23, hi01, hi23}, Qmm = {mid01, mid23, mid01, mid23}, Qlh = {lo01, lo23, hi01, hi23};
+                if (XD) {
+                    // g[i] is tap i of output x and tap i - 1 of output x + 1: the same split operand against two records
+#pragma unroll
+                    for (int n = 0; n < NBW; ++n)
+#pragma unroll
+                        for (int e = 0; e < 2; ++e) {
+                            const int dx = i - e;
+                            if (dx < 0 || dx > 2) continue;
+                            const WfB &w = bw[n][dx < NXP ? dx : 0];
+                            const u32x4 Bmh = w.mh;
+                            const u32x4 Bhl = {w.mh.z, w.mh.w, w.l.x, w.l.y};
+                            f32x4 &M = e ? M1[n] : M0[n];
+                            M = mfma16_bf16(Qhh, Bmh, M);
+                            M = mfma16_bf16(Qmm, Bmh, M);
+                            M = mfma16_bf16(Qlh, Bhl, M);
+                        }
+                    continue;
+                }
 #pragma unroll
                 for (int n = 0; n < NBW; ++n) {
-                    const WfB &w = bw[n][i];
+                    const WfB &w = bw[n][i < NXP ? i : 0];
                     const u32x4 Bmh = w.mh;
                     const u32x4 Bhl = {w.mh.z, w.mh.w, w.l.x, w.l.y};
 #if SP3D_W16_ABLATE & 1
@@ -865,14 +891,22 @@ extern "C" int sp3d_wino_fused_split64(const float *x, const void *U3, float *y,
                                        int mode, int B, int X, int Y, int Z, int C, int O, void *stream)
 {
     const Conv3Grid g = conv3_grid(B, X, Y, Z, 8, 8, 2);
+    // SP3D_CONV3_WINO_YZ on the mode: U3 holds the 48-point records, the kernel convolves directly along x.  A negative mode
+    // stays negative without the bit, so it is refused as before
+    const bool yz = mode >= 0 && (mode & SP3D_CONV3_WINO_YZ);
+    if (yz) mode &= ~SP3D_CONV3_WINO_YZ;
     const bool supported = O == 64 && (C == 32 || C == 64) && !(reinterpret_cast<uintptr_t>(U3) & 7);
     if (const int rc = wino_fused_check(x, U3, y, shift, residual, mode, B, X, Y, Z, supported, g)) return rc;
-    auto launch = [&](auto c, auto m) {
-        hipLaunchKernelGGL((wino_fused16_kernel<decltype(c)::value, decltype(m)::value, W16_NBW, W16_KS>), dim3((unsigned)g.blocks),
-                           dim3(64 * (4 / W16_NBW) * W16_KS), 0, (hipStream_t)stream, x, reinterpret_cast<const unsigned *>(U3), y,
-                           shift, residual, B, X, Y, Z, g.NBX, g.NBY, g.NBZ, (const float *)nullptr, (const unsigned *)nullptr);
+    auto launch = [&](auto c, auto m, auto xd) {
+        hipLaunchKernelGGL((wino_fused16_kernel<decltype(c)::value, decltype(m)::value, W16_NBW, W16_KS, false, decltype(xd)::value>),
+                           dim3((unsigned)g.blocks), dim3(64 * (4 / W16_NBW) * W16_KS), 0, (hipStream_t)stream, x,
+                           reinterpret_cast<const unsigned *>(U3), y, shift, residual, B, X, Y, Z, g.NBX, g.NBY, g.NBZ,
+                           (const float *)nullptr, (const unsigned *)nullptr);
     };
-    with_mode(mode, [&](auto m) { if (C == 32) launch(int_c<32>{}, m); else launch(int_c<64>{}, m); });
+    with_mode(mode, [&](auto m) {
+        if (yz) { if (C == 32) launch(int_c<32>{}, m, std::true_type{}); else launch(int_c<64>{}, m, std::true_type{}); }
+        else { if (C == 32) launch(int_c<32>{}, m, std::false_type{}); else launch(int_c<64>{}, m, std::false_type{}); }
+    });
     return launch_status();
 }
 
@@ -880,13 +914,19 @@ extern "C" int sp3d_wino_fused_split64_skip(const float *x, const void *U3, floa
                                             const void *WS, int B, int X, int Y, int Z, int C, int O, int CS, void *stream)
 {
     const Conv3Grid g = conv3_grid(B, X, Y, Z, 8, 8, 2);
+    // this entry has no mode: SP3D_CONV3_WINO_YZ rides on the skip width (U3 = the 48-point records; WS is one point either way)
+    const bool yz = CS >= 0 && (CS & SP3D_CONV3_WINO_YZ);
+    if (yz) CS &= ~SP3D_CONV3_WINO_YZ;
     const bool supported = O == 64 && C == 64 && CS == 32 && !((reinterpret_cast<uintptr_t>(U3) | reinterpret_cast<uintptr_t>(WS)) & 7) &&
                            !(reinterpret_cast<uintptr_t>(xs) & 15);
     // (the kernel's 32-bit offsets inside a sample of xs)
     const bool in_range = (int64_t)X * Y * Z * CS <= 0x7fffffff && g.blocks <= 0x7fffffff;
     if (const int rc = conv3_check(B, X, Y, Z, 1, x && U3 && y && shift && xs && WS, supported, in_range)) return rc;
-    hipLaunchKernelGGL((wino_fused16_kernel<64, 1, W16_NBW, W16_KS, true>), dim3((unsigned)g.blocks),
-                       dim3(64 * (4 / W16_NBW) * W16_KS), 0, (hipStream_t)stream, x, reinterpret_cast<const unsigned *>(U3), y,
-                       shift, (const float *)nullptr, B, X, Y, Z, g.NBX, g.NBY, g.NBZ, xs, reinterpret_cast<const unsigned *>(WS));
+    auto launch = [&](auto xd) {
+        hipLaunchKernelGGL((wino_fused16_kernel<64, 1, W16_NBW, W16_KS, true, decltype(xd)::value>), dim3((unsigned)g.blocks),
+                           dim3(64 * (4 / W16_NBW) * W16_KS), 0, (hipStream_t)stream, x, reinterpret_cast<const unsigned *>(U3), y,
+                           shift, (const float *)nullptr, B, X, Y, Z, g.NBX, g.NBY, g.NBZ, xs, reinterpret_cast<const unsigned *>(WS));
+    };
+    if (yz) launch(std::true_type{}); else launch(std::false_type{});
     return launch_status();
 }

@@ -296,6 +296,8 @@ class _Conv(NamedTuple):
     split: Optional[torch.Tensor] = None       # ... in three bf16 pieces (_lib.wino_weights_split): the fused kernels
     direct: Optional[torch.Tensor] = None      # w in three bf16 pieces, 48-byte records: conv3_split_ (_lib.conv_weights_split)
     direct24: Optional[torch.Tensor] = None    # ... in 24-byte blocks: conv3_split128_ (_lib.conv_weights_split24)
+    split_yz: Optional[torch.Tensor] = None    # G along y,z only, raw along x, the records of ``split``: the half-resolution
+                                               # fused kernel's direct-in-x form (_lib.wino_yz_weights_split)
 
 
 class _Res(NamedTuple):
@@ -382,7 +384,9 @@ class _FoldedV2V:
         # full-resolution (16 | 32 -> 32) and quarter-resolution layers (64 | 128 -> 128): direct convolution, three exact pieces
         direct = _lib.conv_weights_split(w) if "conv3_split_" in routes else None
         direct24 = _lib.conv_weights_split24(w) if "conv3_split128_" in routes else None
-        return _Conv(w, shift, u, split, direct, direct24)
+        # half-resolution layers (32 | 64 -> 64): the 48-point records of the fused kernel's y,z form
+        split_yz = _lib.wino_yz_weights_split(w) if split is not None and cout == 64 else None
+        return _Conv(w, shift, u, split, direct, direct24, split_yz)
 
     def _build(self):
         from . import _lib
@@ -433,7 +437,8 @@ class _FoldedV2V:
         if route == "conv3_split_":
             return _lib.conv3_split_(x, c.direct, c.shift, mode, residual, xs=xs, skip_w=skip_w)
         if route == "wino_fused_conv3d_":
-            return _lib.wino_fused_conv3d_(x, c.u, c.shift, mode, residual, c.split if split else None, xs=xs, skip_w=skip_w)
+            return _lib.wino_fused_conv3d_(x, c.u, c.shift, mode, residual, c.split if split else None, xs=xs, skip_w=skip_w,
+                                           U3yz=c.split_yz if split else None)
         assert xs is None and skip_w is None, route
         if route == "conv3_split128_":
             return _lib.conv3_split128_(x, c.direct24, c.shift, mode, residual)

@@ -21,8 +21,9 @@ shift = torch.randn(64, generator=g).to(dev)
 res = torch.randn((B, 64) + S, generator=g).to(dev).contiguous(memory_format=torch.channels_last_3d)
 U = _lib.wino_weights(w)
 U3 = _lib.wino_weights_split(U, 16)
+U3yz = _lib.wino_yz_weights_split(w)        # the y,z form is what runs unless SP3D_WINO_YZ=0
 for _ in range(a.iters):
-    _lib.wino_fused_conv3d_(x, U, shift, 1, None, U3)
-    _lib.wino_fused_conv3d_(x, U, shift, 2, res, U3)
+    _lib.wino_fused_conv3d_(x, U, shift, 1, None, U3, U3yz=U3yz)
+    _lib.wino_fused_conv3d_(x, U, shift, 2, res, U3, U3yz=U3yz)
 torch.cuda.synchronize()
 print("done", a.iters)
