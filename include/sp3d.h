@@ -561,7 +561,15 @@ int sp3d_conv3_split(const float *x, const void *W3, float *y, const float *shif
                      int X, int Y, int Z, int C, int O, void *stream);
 
 /* These two convolutions as the second 3x3x3 convolution of a residual block that changes its channel count, with the
- * block's 1x1x1 skip projection computed on the same accumulators. */
+ * block's 1x1x1 skip projection computed on the same accumulators.
+ *
+ * SP3D_CONV3_POOL2X OR-ed into `CS` of either entry (next to SP3D_CONV3_WINO_YZ where that applies): the MaxPool3d(2,2) of
+ * the result as well, from the accumulators.  `y` then points to ONE buffer of B*X*Y*Z*O + B*(X/2)*(Y/2)*(Z/2)*O floats: the
+ * full result first, the pooled tensor (B,X/2,Y/2,Z/2,O) channels-last directly behind it, bit for bit what
+ * sp3d_maxpool2x_cl makes of the full result (NaN propagates).  Only grids of whole output blocks - X % 16, Y % 8, Z % 4 == 0
+ * for sp3d_conv3_split_skip, X % 8, Y % 8, Z % 2 == 0 for sp3d_wino_fused_split64_skip -, anything else SP3D_EUNSUPPORTED
+ * before any launch.  The other checks and return codes are those of the call without the bit. */
+#define SP3D_CONV3_POOL2X 0x200
 
 /* y = relu(conv3(x) + WS . xs + shift): sp3d_conv3_split (its x, W3, y, shift and its refusals) with the projection of the
  * block's input xs (B,X,Y,Z,CS) channels-last as more K of the same products - the projected tensor never exists.

@@ -30,6 +30,7 @@ HM_ONE_ZSPECTRUM = 0x4000   # sp3d_unproject_fwd[_indexed]: one channel read in 
 SCATTER_AUTO, SCATTER_PER_TAP, SCATTER_MERGE = 0, 2, 3      # include/sp3d.h: per-call scatter choice of unproject_bwd_packed
 SCATTER_WIDE = 0x100        # OR-ed into that choice: 17..32 joints, 32-element pixels, the two-plane mask
 CONV3_WINO_YZ = 0x100       # OR-ed into the mode of sp3d_wino_fused_split64 / the CS of its _skip form: Winograd in y,z, direct in x
+CONV3_POOL2X = 0x200        # OR-ed into the CS of sp3d_conv3_split_skip / sp3d_wino_fused_split64_skip: the 2x max-pooled result behind y
 MAX_VIEWS = 16
 MAX_TOPK = 32
 ABI_VERSION = 3
@@ -520,10 +521,18 @@ def fetch_ring(ring: torch.Tensor, dst: torch.Tensor, counter: torch.Tensor):
           "sp3d_fetch_ring")
 
 
-def maxpool2x(x: torch.Tensor) -> torch.Tensor:
-    """MaxPool3d(2,2) of a channels_last_3d tensor (B,C,X,Y,Z) -> channels_last_3d (B,C,X/2,Y/2,Z/2)"""
-    lib = load()
+def maxpool2x(x: torch.Tensor, have: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """MaxPool3d(2,2) of a channels_last_3d tensor (B,C,X,Y,Z) -> channels_last_3d (B,C,X/2,Y/2,Z/2).  ``have``: the pooled
+    tensor where the kernel that made x has already written it (conv3_split_ / wino_fused_conv3d_ with pool=True): checked
+    against x (shape, device, type, layout) and returned, no launch."""
     B, Cc, X, Y, Z = (int(v) for v in x.shape)
+    if have is not None:
+        if tuple(have.shape) != (B, Cc, X // 2, Y // 2, Z // 2) or have.device != x.device or have.dtype != torch.float32 or \
+                x.dtype != torch.float32 or not have.is_contiguous(memory_format=torch.channels_last_3d):
+            raise Sp3dError(f"maxpool2x: have must be the float32 channels_last_3d ({B}, {Cc}, {X // 2}, {Y // 2}, {Z // 2}) pooled "
+                            f"form of x on {x.device}; got {tuple(have.shape)}, {have.dtype}, {have.device}")
+        return have
+    lib = load()
     y = _empty_cl3d(B, Cc, X // 2, Y // 2, Z // 2, x.device)
     check(lib.sp3d_maxpool2x_cl(x.data_ptr(), y.data_ptr(), B, X, Y, Z, Cc, _stream(x.device)), "sp3d_maxpool2x_cl")
     return y
@@ -1014,30 +1023,74 @@ def _require_skip(xs: torch.Tensor, skip_w: torch.Tensor, x: torch.Tensor, CS: i
                         f"{tuple(skip_w.shape)}, {skip_w.dtype}, {skip_w.device}, contiguous={skip_w.is_contiguous()}")
 
 
+POOL_FOLD_DEFAULT = True
+
+
+def pool_fold_enabled() -> bool:
+    """SP3D_FOLD_POOL=0 keeps the plan's two MaxPool3d(2,2) launches of their own; on, the second conv of front_res and of
+    encoder_res1 writes the pooled tensor from its accumulators where pool_fold_covers"""
+    return env_switch("SP3D_FOLD_POOL", POOL_FOLD_DEFAULT)
+
+
+def pool_fold_covers(route: str, X: int, Y: int, Z: int) -> bool:
+    """the grids on which the kernel behind ``route`` (a name v2v_net.conv3_route gives) has a pooled form: whole output
+    blocks only, 16x8x4 for conv3_split_ (80x80x20, 64^3, 48x48x12; not 40x40x10), 8x8x2 for wino_fused_conv3d_ (40x40x10,
+    32^3; not 20x20x5) - what the C entries refuse otherwise"""
+    X, Y, Z = int(X), int(Y), int(Z)
+    if min(X, Y, Z) <= 0:
+        return False
+    if route == "conv3_split_":
+        return X % 16 == 0 and Y % 8 == 0 and Z % 4 == 0
+    if route == "wino_fused_conv3d_":
+        return X % 8 == 0 and Y % 8 == 0 and Z % 2 == 0
+    return False
+
+
+def _result_pooled(out: Optional[torch.Tensor], B: int, O: int, X: int, Y: int, Z: int, x: torch.Tensor, who: str):
+    """(y, y_pooled) of a pool=True call: channels_last_3d views (B,O,X,Y,Z) and (B,O,X/2,Y/2,Z/2) of ONE float32 buffer of
+    B*X*Y*Z*O + B*(X/2)*(Y/2)*(Z/2)*O elements, the pooled tensor directly behind the full one (include/sp3d.h:
+    SP3D_CONV3_POOL2X) - a fresh buffer, or the caller's dense 1-D ``out`` of exactly that size on x's device"""
+    n, npool = B * X * Y * Z * O, B * (X // 2) * (Y // 2) * (Z // 2) * O
+    if out is None:
+        out = torch.empty(n + npool, dtype=torch.float32, device=x.device)
+    elif out.dim() != 1 or out.numel() != n + npool or out.dtype != torch.float32 or out.device != x.device or not out.is_contiguous():
+        raise Sp3dError(f"{who}: with pool=True out must be a dense 1-D float32 buffer of {n} + {npool} elements on {x.device}, got "
+                        f"{tuple(out.shape)}, {out.dtype}, {out.device}")
+    return (out[:n].view(B, X, Y, Z, O).permute(0, 4, 1, 2, 3), out[n:].view(B, X // 2, Y // 2, Z // 2, O).permute(0, 4, 1, 2, 3))
+
+
 def conv3_split_(x: torch.Tensor, W3: torch.Tensor, shift: torch.Tensor, mode: int,
                  residual: Optional[torch.Tensor] = None, *, xs: Optional[torch.Tensor] = None,
-                 skip_w: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+                 skip_w: Optional[torch.Tensor] = None, pool: bool = False, out: Optional[torch.Tensor] = None):
     """3x3x3 stride-1 'same' conv of channels_last_3d x with the fused epilogue, direct (implicit GEMM) on the bf16 matrix
     pipe with exact three-piece splits; W3 = conv_weights_split(w).  Returns the channels_last_3d result (B,O,X,Y,Z), written
     into ``out`` when given.
     (Round 3's chained form - split activations handed from layer to layer - measured no gain and was removed in round 4.)
     With xs (B,16,X,Y,Z) and skip_w = conv_weights_split of the (32,16,1,1,1) skip weight: relu(conv3(x) + skip_w . xs + shift)
-    in the same kernel (sp3d_conv3_split_skip; mode must be 1 and residual None - the projection is the residual)."""
+    in the same kernel (sp3d_conv3_split_skip; mode must be 1 and residual None - the projection is the residual).
+    pool=True (with the folded skip only, grids of whole 16x8x4 blocks: pool_fold_covers): returns (y, y_pooled), the result and
+    its MaxPool3d(2,2) - bit for bit maxpool2x(y) - as channels_last_3d views of one buffer (``out``: that buffer, 1-D)."""
     lib = load()
     _require_cuda(x, "x")
     B, Cc, X, Y, Z = (int(v) for v in x.shape)
     _require_cl3d_f32(x, "conv3_split_")
     O = int(W3.shape[3])
     dev = x.device
-    y = _result_cl3d(out, B, O, X, Y, Z, x, "conv3_split_")
+    if pool:
+        if xs is None or skip_w is None:
+            raise Sp3dError("conv3_split_: pool=True is a form of the folded skip (xs and skip_w)")
+        y, yp = _result_pooled(out, B, O, X, Y, Z, x, "conv3_split_")
+    else:
+        y = _result_cl3d(out, B, O, X, Y, Z, x, "conv3_split_")
     if xs is not None or skip_w is not None:
         if xs is None or skip_w is None or int(mode) != 1 or residual is not None:
             raise Sp3dError("conv3_split_: the folded skip takes xs AND skip_w, mode 1 and no residual")
         CS = 16
         _require_skip(xs, skip_w, x, CS, CS * O * 6, "conv3_split_")
         check(lib.sp3d_conv3_split_skip(x.data_ptr(), W3.data_ptr(), y.data_ptr(), shift.data_ptr(), xs.data_ptr(),
-                                        skip_w.data_ptr(), B, X, Y, Z, Cc, O, CS, _stream(dev)), "sp3d_conv3_split_skip")
-        return y
+                                        skip_w.data_ptr(), B, X, Y, Z, Cc, O, CS | (CONV3_POOL2X if pool else 0), _stream(dev)),
+              "sp3d_conv3_split_skip")
+        return (y, yp) if pool else y
     if residual is not None:
         residual = _as_cl3d(residual)
     check(lib.sp3d_conv3_split(x.data_ptr(), W3.data_ptr(), y.data_ptr(), shift.data_ptr(), _opt(residual), int(mode),
@@ -1109,20 +1162,27 @@ def wino_conv3d_(x: torch.Tensor, U: torch.Tensor, shift: torch.Tensor, mode: in
 def wino_fused_conv3d_(x: torch.Tensor, U: torch.Tensor, shift: torch.Tensor, mode: int,
                        residual: Optional[torch.Tensor] = None, U3: Optional[torch.Tensor] = None, *,
                        xs: Optional[torch.Tensor] = None, skip_w: Optional[torch.Tensor] = None,
-                       U3yz: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+                       U3yz: Optional[torch.Tensor] = None, pool: bool = False, out: Optional[torch.Tensor] = None):
     """one-launch Winograd 3x3x3 conv (C = 16 | 32 -> O = 32; with U3 also C = 32 | 64 -> O = 64) of channels_last_3d x
     with the fused epilogue; with U3 (wino_weights_split(U, 8 | 16)) the products run as exact three-piece bf16 splits
     on the bf16 matrix pipe.  With U3, xs (B,32,X,Y,Z) and skip_w = wino_weights_split of the (1,32,64) skip weight, chunk 16
     (C = O = 64): relu(conv3(x) + skip_w . xs + shift) in the same kernel (sp3d_wino_fused_split64_skip; mode 1, no residual).
     U3yz (wino_yz_weights_split(w); O = 64, next to U3): the same layer with Winograd in y and z only and the three x taps
     convolved directly - taken instead of U3 unless SP3D_WINO_YZ=0, which runs the U3 form bit for bit.
-    The result is written into ``out`` when given."""
+    The result is written into ``out`` when given.
+    pool=True (with the folded skip only, grids of whole 8x8x2 blocks: pool_fold_covers): returns (y, y_pooled), the result and
+    its MaxPool3d(2,2) - bit for bit maxpool2x(y) - as channels_last_3d views of one buffer (``out``: that buffer, 1-D)."""
     lib = load()
     _require_cuda(x, "x")
     B, Cc, X, Y, Z = (int(v) for v in x.shape)
     _require_cl3d_f32(x, "wino_fused_conv3d_")
     O = int(U.shape[2])
-    y = _result_cl3d(out, B, O, X, Y, Z, x, "wino_fused_conv3d_")
+    if pool:
+        if xs is None or skip_w is None:
+            raise Sp3dError("wino_fused_conv3d_: pool=True is a form of the folded skip (U3, xs and skip_w)")
+        y, yp = _result_pooled(out, B, O, X, Y, Z, x, "wino_fused_conv3d_")
+    else:
+        y = _result_cl3d(out, B, O, X, Y, Z, x, "wino_fused_conv3d_")
     yz = 0
     if U3yz is not None and U3 is not None and O == 64 and wino_yz_enabled():
         # the kernel reads 48 * C * 64 pieces of three bf16 behind this pointer: refuse anything that is not exactly that
@@ -1136,9 +1196,10 @@ def wino_fused_conv3d_(x: torch.Tensor, U: torch.Tensor, shift: torch.Tensor, mo
         CS = 32
         _require_skip(xs, skip_w, x, CS, CS * O * 3, "wino_fused_conv3d_")
         check(lib.sp3d_wino_fused_split64_skip(x.data_ptr(), U3.data_ptr(), y.data_ptr(), shift.data_ptr(), xs.data_ptr(),
-                                               skip_w.data_ptr(), B, X, Y, Z, Cc, O, CS | yz, _stream(x.device)),
+                                               skip_w.data_ptr(), B, X, Y, Z, Cc, O, CS | yz | (CONV3_POOL2X if pool else 0),
+                                               _stream(x.device)),
               "sp3d_wino_fused_split64_skip")
-        return y
+        return (y, yp) if pool else y
     if residual is not None:
         residual = _as_cl3d(residual)
     if U3 is None:

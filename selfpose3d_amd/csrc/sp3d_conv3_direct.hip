@@ -67,7 +67,12 @@ __device__ unsigned long long *g_cd_tl = nullptr;      // [wave 6][item 64][4] s
 // workgroup walks.  A voxel of xs is 64 bytes, one cache line for both chunks and both lane halves: the last (dy,dz) step
 // requests the first value of each row (4 registers - all eight rows held over that step spill: 256 + 72 B of scratch), the
 // rest are cache hits after the step.
-template <int C, int MODE, bool SKIP = false>
+// POOL (with SKIP, MODE 1, grids of whole blocks only - the entry refuses the others): the MaxPool3d(2,2) of the result as
+// well, stored right behind y, (B,X/2,Y/2,Z/2,32) channels-last at y + B*X*Y*Z*32.  In the interior epilogue lane (t, h) owns
+// channel t of voxels x = ox0 + 4 wave + i, y = oy0 + 4 h + (v & 3), z = oz0 + (v >> 2): eight whole 2x2x2 cells, (i >> 1,
+// (v & 3) >> 1, v >> 3).  Each is scanned in the order and with the comparison of maxpool2x_cl_kernel (NaN and -0/+0 come out
+// the same bits); a pooled store instruction writes two 128-byte voxel rows (h = 0, 1).
+template <int C, int MODE, bool SKIP = false, bool POOL = false>
 __global__ __launch_bounds__(64 * (4 + CD_PROD)) __attribute__((amdgpu_waves_per_eu(2, 2)))
 void conv3_split_kernel(const float *__restrict__ x, const unsigned *__restrict__ W3, float *__restrict__ y,
                         const float *__restrict__ shift, const float *__restrict__ res, int B, int X, int Y, int Z, int NBX,
@@ -305,6 +310,34 @@ void conv3_split_kernel(const float *__restrict__ x, const unsigned *__restrict_
                 // against 6-9 k for the transposed form below)
                 const float sh = shift[t];
                 const int64_t obase = ((((int64_t)b * X + ox0 + 4 * wave) * Y + oy0 + 4 * h) * Z + oz0) * O + t;
+                if (POOL) {
+                    static_assert(!POOL || (SKIP && MODE == 1), "the pooled form exists for the folded skip only");
+                    // final values in place of the sums, then the cells: nothing but the accumulators is live here
+#pragma unroll
+                    for (int i = 0; i < 4; ++i)
+#pragma unroll
+                        for (int v = 0; v < 16; ++v) {
+                            acc[i][v] = relu_keep_nan(acc[i][v] + sh);
+                            y[obase + (((int64_t)i * Y + (v & 3)) * Z + (v >> 2)) * O] = acc[i][v];
+                        }
+                    const int XP = X >> 1, YP = Y >> 1, ZP = Z >> 1;
+                    float *yp = y + (int64_t)B * X * Y * Z * O;
+                    const int64_t pbase = ((((int64_t)b * XP + ((ox0 + 4 * wave) >> 1)) * YP + ((oy0 + 4 * h) >> 1)) * ZP + (oz0 >> 1)) * O + t;
+#pragma unroll
+                    for (int ci = 0; ci < 2; ++ci)
+#pragma unroll
+                        for (int cy = 0; cy < 2; ++cy)
+#pragma unroll
+                            for (int cz = 0; cz < 2; ++cz) {
+                                float m = acc[2 * ci][8 * cz + 2 * cy];
+#pragma unroll
+                                for (int s = 1; s < 8; ++s) {                  // s = (dx, dy, dz)
+                                    const float val = acc[2 * ci + (s >> 2)][4 * (2 * cz + (s & 1)) + 2 * cy + ((s >> 1) & 1)];
+                                    m = (val > m || val != val) ? val : m;
+                                }
+                                yp[pbase + (((int64_t)ci * YP + cy) * ZP + cz) * O] = m;
+                            }
+                } else
 #pragma unroll
                 for (int i = 0; i < 4; ++i)
 #pragma unroll
@@ -378,9 +411,9 @@ static int conv3_cu_count(int dev)
     return cu_count[dev];
 }
 
-// launch of conv3_split_kernel<C, MODE, SKIP> behind sp3d_conv3_split and sp3d_conv3_split_skip (the skip term of xs / WS on
-// the accumulators); the arguments are validated
-template <int C, int MODE, bool SKIP>
+// launch of conv3_split_kernel<C, MODE, SKIP, POOL> behind sp3d_conv3_split and sp3d_conv3_split_skip (the skip term of xs / WS
+// on the accumulators; POOL: the pooled tensor behind y); the arguments are validated
+template <int C, int MODE, bool SKIP, bool POOL = false>
 static int conv3_split_launch(const float *x, const void *W3, float *y, const float *shift, const float *residual, const float *xs,
                               const void *WS, int B, int X, int Y, int Z, const Conv3Grid &g, void *stream)
 {
@@ -396,12 +429,12 @@ static int conv3_split_launch(const float *x, const void *W3, float *y, const fl
     static bool attr_dev[64] = {};
     const int slot = (dev < 0 || dev >= 64) ? 63 : dev;
     if (!attr_dev[slot] || slot == 63) {
-        const hipError_t ea = hipFuncSetAttribute(reinterpret_cast<const void *>(conv3_split_kernel<C, MODE, SKIP>),
+        const hipError_t ea = hipFuncSetAttribute(reinterpret_cast<const void *>(conv3_split_kernel<C, MODE, SKIP, POOL>),
                                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (ea != hipSuccess) return (int)ea;
         attr_dev[slot] = true;
     }
-    hipLaunchKernelGGL((conv3_split_kernel<C, MODE, SKIP>), dim3((unsigned)nwg), dim3(64 * (4 + CD_PROD)), lds, (hipStream_t)stream, x,
+    hipLaunchKernelGGL((conv3_split_kernel<C, MODE, SKIP, POOL>), dim3((unsigned)nwg), dim3(64 * (4 + CD_PROD)), lds, (hipStream_t)stream, x,
                        reinterpret_cast<const unsigned *>(W3), y, shift, residual, B, X, Y, Z, g.NBX, g.NBY, g.NBZ, (int)g.blocks, xs,
                        reinterpret_cast<const unsigned *>(WS));
     return launch_status();
@@ -427,11 +460,17 @@ extern "C" int sp3d_conv3_split_skip(const float *x, const void *W3, float *y, c
                                      const void *WS, int B, int X, int Y, int Z, int C, int O, int CS, void *stream)
 {
     const Conv3Grid g = conv3_grid(B, X, Y, Z, CD_BX, CD_BY, CD_BZ);
-    const bool supported = O == 32 && C == 32 && CS == 16 &&
+    // this entry has no mode: SP3D_CONV3_POOL2X rides on the skip width.  The pooled form has no edge-block epilogue: a grid
+    // that is not whole 16x8x4 blocks is refused before any launch
+    const bool pool = CS >= 0 && (CS & SP3D_CONV3_POOL2X);
+    if (pool) CS &= ~SP3D_CONV3_POOL2X;
+    const bool whole = X % CD_BX == 0 && Y % CD_BY == 0 && Z % CD_BZ == 0;
+    const bool supported = O == 32 && C == 32 && CS == 16 && (!pool || whole) &&
                            !((reinterpret_cast<uintptr_t>(W3) | reinterpret_cast<uintptr_t>(WS) | reinterpret_cast<uintptr_t>(xs) |
                               reinterpret_cast<uintptr_t>(y)) & 15);
     const bool in_range = (int64_t)X * Y * Z * C * 2 <= 0x7fffffff && g.blocks <= 0x7fffffff;
     if (const int rc = conv3_check(B, X, Y, Z, 1, x && W3 && y && shift && xs && WS, supported, in_range)) return rc;
+    if (pool) return conv3_split_launch<32, 1, true, true>(x, W3, y, shift, nullptr, xs, WS, B, X, Y, Z, g, stream);
     return conv3_split_launch<32, 1, true>(x, W3, y, shift, nullptr, xs, WS, B, X, Y, Z, g, stream);
 }
 

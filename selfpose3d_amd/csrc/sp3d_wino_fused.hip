@@ -485,7 +485,11 @@ __device__ __forceinline__ f32x4 mfma16_bf16(u32x4 a, u32x4 b, f32x4 c)
 // g[0..3] themselves.  So the 36 matrix instructions of a step stay, and the x input transform (16 add/sub), the sign
 // flips of the weights (8 XOR per output block) and one weight record in four leave it: U3 holds 48 points dx*16 + jk
 // (_lib.wino_yz_weights_split: G along y and z, raw along x) instead of 64.
-template <int C, int MODE, int NBW, int KS, bool SKIP = false, bool XD = false>
+// POOL (with SKIP, MODE 1, grids of whole blocks only - the entry refuses the others): the MaxPool3d(2,2) of the result as
+// well, stored right behind y, (B,X/2,Y/2,Z/2,64) channels-last at y + B*X*Y*Z*64.  acc[a][n][v], a = 0..7, are the eight voxels
+// (a >> 2, (a >> 1) & 1, a & 1) of the 2x2x2 tile at (ox0 + 2 v, oy0 + 2 q, oz0): one pooling cell, scanned over a in the order
+// and with the comparison of maxpool2x_cl_kernel (NaN and -0/+0 come out the same bits); 16 lanes write a 64-byte channel run.
+template <int C, int MODE, int NBW, int KS, bool SKIP = false, bool XD = false, bool POOL = false>
 __global__ __launch_bounds__(64 * (4 / NBW) * KS) __attribute__((amdgpu_waves_per_eu(NBW <= 2 ? 2 : 1))) void wino_fused16_kernel(const float *__restrict__ x,
                                                                           const unsigned *__restrict__ U3,
                                                                           float *__restrict__ y, const float *__restrict__ shift,
@@ -778,6 +782,7 @@ __global__ __launch_bounds__(64 * (4 / NBW) * KS) __attribute__((amdgpu_waves_pe
                     for (int v = 0; v < 4; ++v)
                         rv[a][v] = res[obase + off[v] + (((a >> 2) * Y + ((a >> 1) & 1)) * Z + (a & 1)) * O];
             }
+            float pm[4] = {0.0f, 0.0f, 0.0f, 0.0f};                        // POOL: the running maximum of tile 4 q + v
 #pragma unroll
             for (int a = 0; a < 8; ++a)
 #pragma unroll
@@ -787,7 +792,16 @@ __global__ __launch_bounds__(64 * (4 / NBW) * KS) __attribute__((amdgpu_waves_pe
                     if (MODE >= 1) val = SKIP ? relu_keep_nan(val) : fmaxf(val, 0.0f);
                     if (MODE == 3) val += rv[a][v];
                     y[obase + off[v] + (((a >> 2) * Y + ((a >> 1) & 1)) * Z + (a & 1)) * O] = val;
+                    if (POOL) pm[v] = (a == 0) ? val : ((val > pm[v] || val != val) ? val : pm[v]);
                 }
+            if (POOL) {
+                static_assert(!POOL || (SKIP && MODE == 1), "the pooled form exists for the folded skip only");
+                const int XP = X >> 1, YP = Y >> 1, ZP = Z >> 1;
+                float *yp = y + (int64_t)B * X * Y * Z * O;
+                const int64_t pbase = ((((int64_t)b * XP + (ox0 >> 1)) * YP + (oy0 >> 1) + q) * ZP + (oz0 >> 1)) * O + o;
+#pragma unroll
+                for (int v = 0; v < 4; ++v) yp[pbase + (int64_t)v * YP * ZP * O] = pm[v];
+            }
         }
         return;
     }
@@ -917,16 +931,24 @@ extern "C" int sp3d_wino_fused_split64_skip(const float *x, const void *U3, floa
     // this entry has no mode: SP3D_CONV3_WINO_YZ rides on the skip width (U3 = the 48-point records; WS is one point either way)
     const bool yz = CS >= 0 && (CS & SP3D_CONV3_WINO_YZ);
     if (yz) CS &= ~SP3D_CONV3_WINO_YZ;
-    const bool supported = O == 64 && C == 64 && CS == 32 && !((reinterpret_cast<uintptr_t>(U3) | reinterpret_cast<uintptr_t>(WS)) & 7) &&
+    // ... and so does SP3D_CONV3_POOL2X (the pooled tensor behind y).  The pooled form has no edge-block epilogue: a grid that
+    // is not whole 8x8x2 blocks is refused before any launch
+    const bool pool = CS >= 0 && (CS & SP3D_CONV3_POOL2X);
+    if (pool) CS &= ~SP3D_CONV3_POOL2X;
+    const bool whole = X % 8 == 0 && Y % 8 == 0 && Z % 2 == 0;
+    const bool supported = O == 64 && C == 64 && CS == 32 && (!pool || whole) &&
+                           !((reinterpret_cast<uintptr_t>(U3) | reinterpret_cast<uintptr_t>(WS)) & 7) &&
                            !(reinterpret_cast<uintptr_t>(xs) & 15);
     // (the kernel's 32-bit offsets inside a sample of xs)
     const bool in_range = (int64_t)X * Y * Z * CS <= 0x7fffffff && g.blocks <= 0x7fffffff;
     if (const int rc = conv3_check(B, X, Y, Z, 1, x && U3 && y && shift && xs && WS, supported, in_range)) return rc;
-    auto launch = [&](auto xd) {
-        hipLaunchKernelGGL((wino_fused16_kernel<64, 1, W16_NBW, W16_KS, true, decltype(xd)::value>), dim3((unsigned)g.blocks),
-                           dim3(64 * (4 / W16_NBW) * W16_KS), 0, (hipStream_t)stream, x, reinterpret_cast<const unsigned *>(U3), y,
-                           shift, (const float *)nullptr, B, X, Y, Z, g.NBX, g.NBY, g.NBZ, xs, reinterpret_cast<const unsigned *>(WS));
+    auto launch = [&](auto xd, auto pl) {
+        hipLaunchKernelGGL((wino_fused16_kernel<64, 1, W16_NBW, W16_KS, true, decltype(xd)::value, decltype(pl)::value>),
+                           dim3((unsigned)g.blocks), dim3(64 * (4 / W16_NBW) * W16_KS), 0, (hipStream_t)stream, x,
+                           reinterpret_cast<const unsigned *>(U3), y, shift, (const float *)nullptr, B, X, Y, Z, g.NBX, g.NBY, g.NBZ, xs,
+                           reinterpret_cast<const unsigned *>(WS));
     };
-    if (yz) launch(std::true_type{}); else launch(std::false_type{});
+    if (pool) { if (yz) launch(std::true_type{}, std::true_type{}); else launch(std::false_type{}, std::true_type{}); }
+    else { if (yz) launch(std::true_type{}, std::false_type{}); else launch(std::false_type{}, std::false_type{}); }
     return launch_status();
 }

@@ -310,6 +310,9 @@ class _Res(NamedTuple):
     # weights (_lib.wino_weights_split, chunk 16)
     skip_direct: Optional[torch.Tensor] = None
     skip_split: Optional[torch.Tensor] = None
+    # _tail max-pools this block's output (front_res, encoder_res1): where the skip is folded and _lib.pool_fold_covers, the
+    # second conv writes the pooled tensor too and _pool hands it on without a launch
+    pooled: bool = False
 
 
 class _Up(NamedTuple):
@@ -337,6 +340,7 @@ class _FoldedV2V:
         self.layers = {}           # layer name -> _Conv ("front") | _Res | _Up
         self.spectra = {}          # ("Wf" | "Wz" | "Wty", FFT shape) -> the opening conv's weight spectrum in that form
         self.xpad = {}             # (cin, FFT shape, device) -> zero-padded input buffer of the frequency-domain front
+        self.pooled = None         # (y, y_pooled) of the latest _res that also pooled its output, until the next _pool
 
     def graph_tensors(self):
         """everything a captured graph of this plan's forward may hold an address of (the layers' weights in all their
@@ -407,7 +411,8 @@ class _FoldedV2V:
                     sd = _lib.conv_weights_split(ws)
                 if ws.is_cuda and (co, ci) == (64, 32):
                     sp = _lib.wino_weights_split(ws.reshape(co, ci).t().reshape(1, ci, co).contiguous(), 16)
-            layers[name] = _Res(self._conv3_record(w1, s1), self._conv3_record(w2, s2), ws, sd, sp)
+            layers[name] = _Res(self._conv3_record(w1, s1), self._conv3_record(w2, s2), ws, sd, sp,
+                                pooled=name in ("front_res", "encoder_res1"))
         for name in ("decoder_upsample2", "decoder_upsample1"):
             blk = getattr(ed, name).block
             wT, sT = self._fold(blk[0], blk[1], transposed=True)
@@ -428,18 +433,21 @@ class _FoldedV2V:
                            getattr(n, "wino_split", True), getattr(n, "direct_conv", True),
                            quarter_direct=c.direct24 is not None and _lib.quarter_direct_enabled())
 
-    def _conv3(self, x, c: "_Conv", mode, residual=None, xs=None, skip_w=None):
+    def _conv3(self, x, c: "_Conv", mode, residual=None, xs=None, skip_w=None, pool=False):
         """3x3x3 conv + fused epilogue on the route conv3_route names (weights on the GPU and channels-last x); xs, skip_w:
-        the block input and its projection records for the two kernels that fold the skip (_folded_skip chose them)"""
+        the block input and its projection records for the two kernels that fold the skip (_folded_skip chose them); pool:
+        those kernels' pooled form, (y, y_pooled) instead of y (_pool_fold said the grid has one)"""
         from . import _lib
         route = self._route(x, c)
         split = getattr(self.net, "wino_split", True)
+        # (the keyword only where it is asked for: callers that wrap the entries see the calls they saw before)
+        kw = dict(pool=True) if pool else {}
         if route == "conv3_split_":
-            return _lib.conv3_split_(x, c.direct, c.shift, mode, residual, xs=xs, skip_w=skip_w)
+            return _lib.conv3_split_(x, c.direct, c.shift, mode, residual, xs=xs, skip_w=skip_w, **kw)
         if route == "wino_fused_conv3d_":
             return _lib.wino_fused_conv3d_(x, c.u, c.shift, mode, residual, c.split if split else None, xs=xs, skip_w=skip_w,
-                                           U3yz=c.split_yz if split else None)
-        assert xs is None and skip_w is None, route
+                                           U3yz=c.split_yz if split else None, **kw)
+        assert xs is None and skip_w is None and not pool, route
         if route == "conv3_split128_":
             return _lib.conv3_split128_(x, c.direct24, c.shift, mode, residual)
         if route == "wino_conv3d_":
@@ -460,6 +468,11 @@ class _FoldedV2V:
             return r.skip_split
         return None
 
+    def _pool_fold(self, h, c: "_Conv") -> bool:
+        """the kernel conv c takes on h has a pooled form on this grid (_lib.pool_fold_covers), and SP3D_FOLD_POOL is not 0"""
+        from . import _lib
+        return bool(_lib.pool_fold_enabled() and _lib.pool_fold_covers(self._route(h, c), *h.shape[2:]))
+
     def _res(self, x, name):
         r = self.layers[name]
         h = self._conv3(x, r.c1, 1)
@@ -467,6 +480,11 @@ class _FoldedV2V:
             return self._conv3(h, r.c2, 2, x)
         rec = self._folded_skip(x, h, r)
         if rec is not None:                         # relu(conv3(h) + W . x + shift): neither the GEMM nor its product exists
+            if r.pooled and self._pool_fold(h, r.c2):
+                # ... and its MaxPool3d(2,2) from the same accumulators, kept for the _pool that is handed this very tensor
+                y, yp = self._conv3(h, r.c2, 1, xs=x, skip_w=rec, pool=True)
+                self.pooled = (y, yp)
+                return y
             return self._conv3(h, r.c2, 1, xs=x, skip_w=rec)
         return self._conv3(h, r.c2, 2, self._conv1(x, r.skip))
 
@@ -702,9 +720,12 @@ class _FoldedV2V:
     def _pool(self, x):
         """MaxPool3d(2,2): own channels-last kernel (torch's also computes the arg-max indices: 2.4x the time)"""
         from . import _lib
+        # what the _res before wrote next to its output - only for that very tensor; whatever is stashed is dropped here
+        stash, self.pooled = self.pooled, None
+        have = stash[1] if stash is not None and stash[0] is x else None
         if is_cl(x) and x.is_cuda and x.dtype == torch.float32 and x.shape[1] % 4 == 0 and \
                 all(int(v) % 2 == 0 for v in x.shape[2:]):
-            return _lib.maxpool2x(x)
+            return _lib.maxpool2x(x, have=have) if have is not None else _lib.maxpool2x(x)
         return F.max_pool3d(x, 2, 2)
 
     def _up2x(self, x, name, skip):
