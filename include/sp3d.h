@@ -139,7 +139,24 @@ enum {
      * misaligned `cubes`, for a sample of more than 2^31 bytes, and for the flag on sp3d_unproject_fwd_strided,
      * sp3d_unproject_fwd_train and sp3d_unproject_one_fwd_train; SP3D_EINVAL for Jp < 1 and for a layout byte that is neither
      * SP3D_LAYOUT_PLANAR nor SP3D_LAYOUT_NHWC. */
-    SP3D_HM_ONE_ZSPECTRUM = 0x4000
+    SP3D_HM_ONE_ZSPECTRUM = 0x4000,
+    /* OR-ed into hm_layout of sp3d_unproject_fwd, _fwd_indexed and _fwd_strided, next to EXACTLY ONE of SP3D_OUT_ZSPECTRUM,
+     * SP3D_HM_ONE_CHANNEL and SP3D_HM_ONE_ZSPECTRUM: the heat-maps are bf16 and every result is fp32 ("mixed bf16" through the
+     * fused fronts: half the heat-map bytes, fp32 everywhere behind the unprojection).  A bf16 value is widened exactly
+     * (<< 16) and goes through the fp32 chain of the flag it stands next to, in the same order: the result is bit-identical
+     * to that flag's result on the widened maps.
+     *   with SP3D_OUT_ZSPECTRUM     SP3D_LAYOUT_NHWC, bf16 pixels of Jp == 16 (J <= 16) or Jp == 32 (J <= 32) elements, every
+     *                               other limit as documented there; at Jp == 32 the second channel group starts 16 bf16
+     *                               elements (32 bytes) into the pixel
+     *   with SP3D_HM_ONE_CHANNEL    either layout, J = 1 or 4, dense, strided and channels-last results, every other limit as
+     *                               documented there; hm_views[c] needs 2-byte alignment only, Jp and the strides it implies
+     *                               are in bf16 elements, and "a sample of more than 2^31 bytes" counts 2-byte elements
+     *   with SP3D_HM_ONE_ZSPECTRUM  the same read, with that flag's limits
+     * SP3D_EUNSUPPORTED, before any launch: for the flag on its own; next to SP3D_HM_BF16, SP3D_OUT_BF16 or SP3D_HM_WIDE_MASK;
+     * next to SP3D_OUT_CHANNELS_LAST without SP3D_HM_ONE_CHANNEL; on sp3d_unproject_fwd_train and
+     * sp3d_unproject_one_fwd_train; on sp3d_unproject_fwd_strided next to either spectrum flag.  sp3d_unproject_fwd_zdft has
+     * no layout word and takes fp32 maps only.  SP3D_HM_BF16 itself keeps every refusal it has. */
+    SP3D_HM_BF16_IN = 0x8000
 };
 
 int sp3d_abi_version(void);

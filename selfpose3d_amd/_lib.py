@@ -27,7 +27,8 @@ HM_ONE_CHANNEL = 0x800      # one channel of a wider tensor, read in place (incl
 HM_WIDE_MASK = 0x1000       # sp3d_unproject_fwd_train at Jp = 32: a (2, P, N) pass mask, one plane per channel group
 OUT_ZSPECTRUM = 0x2000      # sp3d_unproject_fwd[_indexed]: the root grid's cubes leave as their z-spectrum (Jp = 16 or 32)
 HM_ONE_ZSPECTRUM = 0x4000   # sp3d_unproject_fwd[_indexed]: one channel read in place, its cubes leave as their z-spectrum (J = 1)
-SCATTER_AUTO, SCATTER_PER_TAP, SCATTER_MERGE = 0, 2, 3      # include/sp3d.h: per-call scatter choice of unproject_bwd_packed
+HM_BF16_IN = 0x8000         # next to OUT_ZSPECTRUM, HM_ONE_CHANNEL or HM_ONE_ZSPECTRUM: the heat-maps are bf16, every result fp32
+SCATTER_AUTO, SCATTER_PER_TAP, SCATTER_MERGE = 0, 2, 3     # include/sp3d.h: per-call scatter choice of unproject_bwd_packed
 SCATTER_WIDE = 0x100        # OR-ed into that choice: 17..32 joints, 32-element pixels, the two-plane mask
 CONV3_WINO_YZ = 0x100       # OR-ed into the mode of sp3d_wino_fused_split64 / the CS of its _skip form: Winograd in y,z, direct in x
 CONV3_POOL2X = 0x200        # OR-ed into the CS of sp3d_conv3_split_skip / sp3d_wino_fused_split64_skip: the 2x max-pooled result behind y
@@ -290,7 +291,8 @@ def unproject_fwd(views: Sequence[torch.Tensor], layout: int, jp: int, cam: torc
     ``sample_of`` (int32, (B,)): output cube p reads heat-map/camera row sample_of[p] (B = #cubes).
     ``out``: a (B,J,X,Y,Z) VIEW of a larger buffer (z contiguous, e.g. the zero-padded FFT input of the opening
     conv): the planar result is written straight into it (sp3d_unproject_fwd_strided).
-    ``one_channel`` (SP3D_HM_ONE_CHANNEL): ``views[c]`` is any fp32 tensor whose ``data_ptr()`` is the wanted channel's first
+    ``one_channel`` (SP3D_HM_ONE_CHANNEL): ``views[c]`` is any fp32 tensor (or bf16: SP3D_HM_BF16_IN, derived from the dtype; the
+    result stays fp32) whose ``data_ptr()`` is the wanted channel's first
     element of view c - a (B,1,h,w) slice of a planar (B,jp,h,w) tensor (``LAYOUT_PLANAR``, ``jp`` = its channel count) or
     of a channels-last (B,h,w,jp) buffer (``LAYOUT_NHWC``, ``jp`` = its pixel stride) - read in place; ``J`` = channels
     written, 1 or 4 (value + three zero channels; channels-last results: 4).
@@ -304,11 +306,15 @@ def unproject_fwd(views: Sequence[torch.Tensor], layout: int, jp: int, cam: torc
     one = HM_ONE_CHANNEL if one_channel else 0
     if one_channel:
         assert pass_mask is None and variant is None and out_dtype == torch.float32 and jp >= 1
-        assert all(v.dtype == torch.float32 for v in views)
+        # bf16 maps (SP3D_HM_BF16_IN): read in place as well - 2-byte elements, fp32 result
+        assert views[0].dtype in (torch.float32, torch.bfloat16) and all(v.dtype == views[0].dtype for v in views)
+        if views[0].dtype == torch.bfloat16:
+            one |= HM_BF16_IN
     if out is not None:
         assert (layout == LAYOUT_NHWC or one_channel) and not channels_last and not want_grids and pass_mask is None and variant is None
         assert tuple(out.shape) == (B, J, X, Y, Z) and out.stride(4) == 1 and out.dtype == out_dtype
-        flags = (HM_BF16 if views[0].dtype == torch.bfloat16 else 0) | (OUT_BF16 if out_dtype == torch.bfloat16 else 0) | one
+        flags = (HM_BF16 if views[0].dtype == torch.bfloat16 and not one_channel else 0) | \
+            (OUT_BF16 if out_dtype == torch.bfloat16 else 0) | one
         st = (C.c_int64 * 4)(*[int(v) for v in out.stride()[:4]])
         rc = lib.sp3d_unproject_fwd_strided(_ptr_array(views), layout | flags, jp, cam.data_ptr(), _opt(sample_of),
                                             centers.data_ptr(), valid.data_ptr(), out.data_ptr(), st, B, V, J, h, w, X, Y, Z,
@@ -319,7 +325,7 @@ def unproject_fwd(views: Sequence[torch.Tensor], layout: int, jp: int, cam: torc
         cubes = _empty_cl3d(B, J, X, Y, Z, dev, out_dtype)
     else:
         cubes = torch.empty((B, J, X, Y, Z), dtype=out_dtype, device=dev)
-    flags = (OUT_CHANNELS_LAST if channels_last else 0) | (HM_BF16 if views[0].dtype == torch.bfloat16 else 0) | \
+    flags = (OUT_CHANNELS_LAST if channels_last else 0) | (HM_BF16 if views[0].dtype == torch.bfloat16 and not one_channel else 0) | \
         (OUT_BF16 if out_dtype == torch.bfloat16 else 0) | one
     grids = torch.empty((B, X * Y * Z, 3), dtype=torch.float32, device=dev) if want_grids else None
     gs = _f3(grid_size)
@@ -634,15 +640,18 @@ def unproject_fwd_zspectrum(views: Sequence[torch.Tensor], jp: int, cam: torch.T
     X, Y, Z = (int(c) for c in cube_size)
     if jp not in (16, 32) or not 1 <= J <= jp:
         raise Sp3dError(f"unproject_fwd_zspectrum: packed pixels of 16 or 32 channels and J <= jp expected, got jp {jp}, J {J}")
+    dt = views[0].dtype         # bf16 maps: SP3D_HM_BF16_IN (the brick-h kernels with the z-spectrum result), fp32 spectrum
     for v in views:
         _require_cuda(v, "heat-map view")
-        if v.dtype != torch.float32 or not v.is_contiguous() or tuple(v.shape) != (batch, h, w, jp):
-            raise Sp3dError(f"unproject_fwd_zspectrum: dense fp32 (B,h,w,{jp}) heat-map views expected")
+        if v.dtype not in (torch.float32, torch.bfloat16) or v.dtype != dt or not v.is_contiguous() or \
+                tuple(v.shape) != (batch, h, w, jp):
+            raise Sp3dError(f"unproject_fwd_zspectrum: dense fp32 or bf16 (B,h,w,{jp}) heat-map views expected")
     if (Z, int(SZ), 16) not in ZDFT_SHAPES or X % 4 or Y % 4:
         raise Sp3dError(f"unproject_fwd_zspectrum: built for (Z, SZ, channels) in {sorted(ZDFT_SHAPES)} and X, Y multiples of 4")
     spec = _result_dense(out, (batch, J, int(SZ) // 2 + 1, X // 4, Y // 4, 16), torch.complex64, cam.device,
                          "unproject_fwd_zspectrum", 128)
-    check(lib.sp3d_unproject_fwd(_ptr_array(views), LAYOUT_NHWC | OUT_ZSPECTRUM, jp, cam.data_ptr(), centers.data_ptr(),
+    flags = LAYOUT_NHWC | OUT_ZSPECTRUM | (HM_BF16_IN if dt == torch.bfloat16 else 0)
+    check(lib.sp3d_unproject_fwd(_ptr_array(views), flags, jp, cam.data_ptr(), centers.data_ptr(),
                                  valid.data_ptr(), spec.data_ptr(), None, batch, len(views), J, h, w, X, Y, Z, _f3(grid_size),
                                  int(img_size[0]), int(img_size[1]), _stream(cam.device)), "sp3d_unproject_fwd (z-spectrum)")
     return spec
@@ -659,13 +668,14 @@ def unproject_one_fwd_zspectrum(views: Sequence[torch.Tensor], layout: int, jp: 
     X, Y, Z = (int(c) for c in cube_size)
     for v in views:
         _require_cuda(v, "heat-map view")
-        if v.dtype != torch.float32:
-            raise Sp3dError("unproject_one_fwd_zspectrum: fp32 heat-map views expected")
+        if v.dtype not in (torch.float32, torch.bfloat16) or v.dtype != views[0].dtype:
+            raise Sp3dError("unproject_one_fwd_zspectrum: fp32 or bf16 heat-map views of one type expected")
     if (Z, int(SZ)) != (20, 28) or X % 4 or Y % 4:
         raise Sp3dError("unproject_one_fwd_zspectrum: built for (Z, SZ) = (20, 28) and X, Y multiples of 4")
     spec = _result_dense(out, (batch, 1, int(SZ) // 2 + 1, X // 4, Y // 4, 16), torch.complex64, cam.device,
                          "unproject_one_fwd_zspectrum", 128)
-    check(lib.sp3d_unproject_fwd_indexed(_ptr_array(views), layout | HM_ONE_ZSPECTRUM, jp, cam.data_ptr(), _opt(sample_of),
+    flags = layout | HM_ONE_ZSPECTRUM | (HM_BF16_IN if views[0].dtype == torch.bfloat16 else 0)
+    check(lib.sp3d_unproject_fwd_indexed(_ptr_array(views), flags, jp, cam.data_ptr(), _opt(sample_of),
                                          centers.data_ptr(), valid.data_ptr(), spec.data_ptr(), None, batch, len(views), 1, h, w,
                                          X, Y, Z, _f3(grid_size), int(img_size[0]), int(img_size[1]), _stream(cam.device)),
           "sp3d_unproject_fwd_indexed (one-channel z-spectrum)")

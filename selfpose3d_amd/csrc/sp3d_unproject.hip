@@ -88,6 +88,7 @@ struct FwdRequest {
     bool one_train;      // one-channel read that also writes the pass mask (sp3d_unproject_one_fwd_train)
     bool wide_mask;      // SP3D_HM_WIDE_MASK: the pass mask has two planes of P * N words, one per channel group of Jp = 32
     bool one_zd;         // SP3D_HM_ONE_ZSPECTRUM: the one-channel read with the z-spectrum result
+    bool hm16;           // SP3D_HM_BF16_IN: bf16 maps into an fp32 result, next to exactly one of zd, one, one_zd
     Geom g;
 };
 
@@ -152,7 +153,7 @@ static int resolve_group(const FwdRequest &rq, const FwdTuning &t, const Geom &g
             return SP3D_EUNSUPPORTED;
         set_launch(L, block_grid ? block_grid : xcd_grid_blocks(g.B, wgs, L.g.xcd_chunk), 64 * zw,
                    (size_t)zw * wlds * sizeof(float) + (size_t)t.ballast * 20480, 4, wgs, nby, nzc, zw);
-        return find_brick_kernel(KernelKey{jp, ps, rq.zd, 0, rq.out_cl, rq.io}, L.fn, L.name);
+        return find_brick_kernel(KernelKey{jp, ps, rq.zd, 0, rq.out_cl, rq.io | (rq.hm16 ? 1 : 0)}, L.fn, L.name);
     }
     if (t.pipe) {    // 64 consecutive voxels per wave
         const int nw = t.one_wave ? 1 : 4;
@@ -173,13 +174,13 @@ static int resolve_one(const FwdRequest &rq, Launch &L)
 {
     Geom &g = L.g;
     if ((rq.layout != SP3D_LAYOUT_PLANAR && rq.layout != SP3D_LAYOUT_NHWC) || rq.Jp < 1) return SP3D_EINVAL;
-    if (rq.io || (g.pass_mask && !rq.one_train)) return SP3D_EUNSUPPORTED;
+    if (rq.io || (g.pass_mask && !rq.one_train) || (rq.hm16 && rq.one_train)) return SP3D_EUNSUPPORTED;
     if (!(g.J == 4 || (g.J == 1 && !rq.out_cl))) return SP3D_EUNSUPPORTED;
     if (g.w < 2 || g.h < 2 || (int64_t)g.h * g.w > (1 << 24)) return SP3D_EUNSUPPORTED;
     if (rq.out_cl && !rq.out_aligned) return SP3D_EUNSUPPORTED;
     const int64_t px = rq.layout == SP3D_LAYOUT_NHWC ? rq.Jp : 1, row = (int64_t)g.w * px;
-    // 24-bit multiplies form the tap offset, a 32-bit byte offset addresses it
-    if (row >= (1 << 24) || (int64_t)g.h * row * 4 > (int64_t)0x7fffffff) return SP3D_EUNSUPPORTED;
+    // 24-bit multiplies form the tap offset, a 32-bit byte offset addresses it (bf16 maps: 2-byte elements)
+    if (row >= (1 << 24) || (int64_t)g.h * row * (rq.hm16 ? 2 : 4) > (int64_t)0x7fffffff) return SP3D_EUNSUPPORTED;
     const int ptiles = (g.N + 63) / 64;
     g.xcd_order = default_xcd_order(g);
     g.xcd_chunk = default_xcd_chunk(g, ptiles);
@@ -187,7 +188,7 @@ static int resolve_one(const FwdRequest &rq, Launch &L)
     const int64_t sample = rq.layout == SP3D_LAYOUT_NHWC ? (int64_t)g.h * row : (int64_t)rq.Jp * g.h * g.w;
     set_launch(L, xcd_grid_blocks(g.B, ptiles, g.xcd_chunk), 64, 0, 3, sample, (int)row, (int)px);
     const int vt = g.V <= 6 ? g.V : (g.V <= 8 ? 8 : (g.V <= 10 ? 10 : (g.V <= 12 ? 12 : 16)));
-    return find_one_kernel(KernelKey{1, 1, vt, vt > 8 ? 8 : 4, rq.out_cl, g.pass_mask ? 4 : 0}, L.fn, L.name);
+    return find_one_kernel(KernelKey{1, 1, vt, vt > 8 ? 8 : 4, rq.out_cl, g.pass_mask ? 4 : (rq.hm16 ? 1 : 0)}, L.fn, L.name);
 }
 
 // SP3D_HM_ONE_ZSPECTRUM (include/sp3d.h): the one-channel read with the z-spectrum result of the brick ZD form at J = 1,
@@ -201,8 +202,8 @@ static int resolve_one_zd(const FwdRequest &rq, Launch &L)
     if (g.J != 1 || g.Z != ZDZ || (g.X % BR) || (g.Y % BR) || !g.dense) return SP3D_EUNSUPPORTED;
     if (g.w < 2 || g.h < 2 || (int64_t)g.h * g.w > (1 << 24)) return SP3D_EUNSUPPORTED;
     const int64_t px = rq.layout == SP3D_LAYOUT_NHWC ? rq.Jp : 1, row = (int64_t)g.w * px;
-    // 24-bit multiplies form the tap offset, a 32-bit byte offset addresses it
-    if (row >= (1 << 24) || (int64_t)g.h * row * 4 > (int64_t)0x7fffffff) return SP3D_EUNSUPPORTED;
+    // 24-bit multiplies form the tap offset, a 32-bit byte offset addresses it (bf16 maps: 2-byte elements)
+    if (row >= (1 << 24) || (int64_t)g.h * row * (rq.hm16 ? 2 : 4) > (int64_t)0x7fffffff) return SP3D_EUNSUPPORTED;
     const int nby = g.Y / BR, tiles = (g.X / BR) * nby;
     set_xcd_fields(g, tiles);
     set_brick_fields(g, tiles, nby);
@@ -210,7 +211,7 @@ static int resolve_one_zd(const FwdRequest &rq, Launch &L)
     set_launch(L, (unsigned)(g.B * tiles), 64 * (ZDZ / BR), (size_t)16 * ZDZ * sizeof(float), 3, sample, (int)row, (int)px);
     L.grids = false;
     const int vt = g.V <= 6 ? g.V : (g.V <= 8 ? 8 : (g.V <= 10 ? 10 : (g.V <= 12 ? 12 : 16)));
-    return find_one_zd_kernel(KernelKey{1, 1, vt, vt > 8 ? 8 : 4, false, 8}, L.fn, L.name);
+    return find_one_zd_kernel(KernelKey{1, 1, vt, vt > 8 ? 8 : 4, false, rq.hm16 ? 9 : 8}, L.fn, L.name);
 }
 
 // Jp = 32 (17..32 joints: the 17 COCO joints of the Shelf / Campus configurations).  A packed fp32 pixel is exactly one
@@ -236,6 +237,9 @@ static int resolve_fwd(const FwdRequest &rq, FwdTuning t, Launch (&plan)[SP3D_PL
     L = Launch{};
     L.g = rq.g; L.grid_y = 1; L.grids = !rq.zd;      // a z-spectrum launch writes no grids (its entries take none)
     if (rq.one_zd) return resolve_one_zd(rq, L);
+    // bf16 maps into an fp32 result (SP3D_HM_BF16_IN): a form of the z-spectrum result and of the one-channel read, of nothing
+    // else - not of the bf16 storage pair, not of the two-plane mask, channels-last only from the one-channel kernel
+    if (rq.hm16 && (!(rq.zd || rq.one) || rq.io || rq.wide_mask || (rq.out_cl && !rq.one))) return SP3D_EUNSUPPORTED;
     // the two-plane mask belongs to the Jp = 32 training forward with a planar fp32 result, and to nothing else
     if (rq.wide_mask && (rq.one || !rq.g.pass_mask || rq.layout != SP3D_LAYOUT_NHWC || rq.Jp != WIDE_PS || rq.out_cl || rq.io))
         return SP3D_EUNSUPPORTED;
@@ -276,11 +280,11 @@ static int resolve_fwd(const FwdRequest &rq, FwdTuning t, Launch (&plan)[SP3D_PL
         L1 = L;
         gg.J = g.J - 16;
         if (g.pass_mask) gg.pass_mask = g.pass_mask + (size_t)g.B * g.N;
-        L1.view_off = 16 * ((rq.io & 1) ? 2 : 4);
+        L1.view_off = 16 * (((rq.io & 1) || rq.hm16) ? 2 : 4);
         L1.out_off = rq.zd ? (size_t)16 * (ZDSZ / 2 + 1) * (g.X / BR) * (g.Y / BR) * 16 * 8
                            : (size_t)16 * g.sJ * ((rq.io & 2) ? 2 : 4);
         L1.grids = false;
-        return resolve_group(rq, t, gg, rq.io ? 16 : (gg.J + 3) / 4 * 4, WIDE_PS, L1);
+        return resolve_group(rq, t, gg, (rq.io || rq.hm16) ? 16 : (gg.J + 3) / 4 * 4, WIDE_PS, L1);
     }
     if (rq.Jp < g.J || (rq.Jp & 3) || rq.Jp > 16) return SP3D_EUNSUPPORTED;
     if (rq.out_cl && (g.J & 3)) return SP3D_EUNSUPPORTED;        // channels-last rows must be 16-B multiples
@@ -321,6 +325,7 @@ static int fwd_request(FwdRequest &rq, int hm_layout, int Jp, bool ptrs, int B, 
     rq.wide_mask = (hm_layout & SP3D_HM_WIDE_MASK) != 0;
     rq.zd = (hm_layout & SP3D_OUT_ZSPECTRUM) != 0;
     rq.one_zd = (hm_layout & SP3D_HM_ONE_ZSPECTRUM) != 0;
+    rq.hm16 = (hm_layout & SP3D_HM_BF16_IN) != 0;
     rq.out_aligned = true; rq.one_train = false;
     return SP3D_OK;
 }
@@ -491,7 +496,7 @@ extern "C" int sp3d_unproject_fwd_plan(int entry, int hm_layout, int Jp, const i
     if (!names || !fields || !tuning || !records) return SP3D_ENULL;
     if (entry < SP3D_PLAN_INDEXED || entry > SP3D_PLAN_ONE_TRAIN) return SP3D_EINVAL;
     const float grid_size[3] = {1.0f, 1.0f, 1.0f};
-    if (entry == SP3D_PLAN_ZDFT) hm_layout = SP3D_LAYOUT_NHWC | (hm_layout & (SP3D_HM_WIDE_MASK | SP3D_HM_ONE_ZSPECTRUM));     // the entry has no layout word; the flags are kept to be refused
+    if (entry == SP3D_PLAN_ZDFT) hm_layout = SP3D_LAYOUT_NHWC | (hm_layout & (SP3D_HM_WIDE_MASK | SP3D_HM_ONE_ZSPECTRUM | SP3D_HM_BF16_IN));     // the entry has no layout word; the flags are kept to be refused
     if (entry == SP3D_PLAN_TUNING) hm_layout = SP3D_LAYOUT_NHWC | ((variant & SP3D_TUNING_CHANNELS_LAST) ? SP3D_OUT_CHANNELS_LAST : 0);
     if (entry == SP3D_PLAN_ONE_TRAIN) hm_layout |= SP3D_HM_ONE_CHANNEL;
     FwdRequest rq;
@@ -500,7 +505,8 @@ extern "C" int sp3d_unproject_fwd_plan(int entry, int hm_layout, int Jp, const i
     if (rc) return rc;
     // SP3D_OUT_ZSPECTRUM belongs to the indexed entry alone; sp3d_unproject_fwd_zdft keeps its own Jp == 16
     if ((rq.zd || rq.one_zd) && entry != SP3D_PLAN_INDEXED) return SP3D_EUNSUPPORTED;
-    if (entry == SP3D_PLAN_ZDFT && Jp != 16) return SP3D_EUNSUPPORTED;
+    if (entry == SP3D_PLAN_ZDFT && (Jp != 16 || rq.hm16)) return SP3D_EUNSUPPORTED;
+    if ((entry == SP3D_PLAN_TRAIN || entry == SP3D_PLAN_ONE_TRAIN) && rq.hm16) return SP3D_EUNSUPPORTED;     // as the two entries answer
     rq.one_train = entry == SP3D_PLAN_ONE_TRAIN;
     if (entry == SP3D_PLAN_TRAIN || rq.one_train) rq.g.pass_mask = reinterpret_cast<uint16_t *>(records);    // "there is one": never dereferenced
     rq.zd = rq.zd || entry == SP3D_PLAN_ZDFT;
@@ -537,7 +543,7 @@ extern "C" int sp3d_unproject_fwd_train(const float *const *hm_views, int hm_lay
     const int rc = fwd_request(rq, hm_layout, Jp, cam && centers && valid && cubes && pass_mask, P, V, J, h, w,
                                X, Y, Z, grid_size, W_in, H_in);
     if (rc) return rc;
-    if (rq.layout != SP3D_LAYOUT_NHWC || rq.io || rq.one || rq.zd || rq.one_zd || w < 2 || h < 2) return SP3D_EUNSUPPORTED;
+    if (rq.layout != SP3D_LAYOUT_NHWC || rq.io || rq.one || rq.zd || rq.one_zd || rq.hm16 || w < 2 || h < 2) return SP3D_EUNSUPPORTED;
     rq.g.sample_of = sample_of;
     rq.g.pass_mask = pass_mask;
     return run_fwd(rq, default_tuning(rq.g, rq.out_cl), hm_views, cam, centers, valid, cubes, grids, stream);
@@ -555,7 +561,7 @@ extern "C" int sp3d_unproject_one_fwd_train(const float *const *hm_views, int hm
     const int rc = fwd_request(rq, hm_layout | SP3D_HM_ONE_CHANNEL, Jp, cam && centers && valid && cubes && pass_mask, P, V,
                                J, h, w, X, Y, Z, grid_size, W_in, H_in);
     if (rc) return rc;
-    if (rq.zd || rq.one_zd) return SP3D_EUNSUPPORTED;
+    if (rq.zd || rq.one_zd || rq.hm16) return SP3D_EUNSUPPORTED;
     rq.one_train = true;
     rq.g.sample_of = sample_of;
     rq.g.pass_mask = pass_mask;

@@ -320,8 +320,15 @@ __device__ __forceinline__ void pipe_views_h(const Views &hm, const float *__res
     }
 }
 
-template <bool OUTCL, typename TO, int PS = 16>
-__global__ __launch_bounds__(512, SP3D_BRICK_MINW) void unproject_brick_h_kernel(Views hm, const float *__restrict__ cam,
+// ZD (SP3D_HM_BF16_IN next to SP3D_OUT_ZSPECTRUM): the z-spectrum epilogue of unproject_brick_kernel<..., ZD> behind this
+// kernel's gather.  After the view loop a wave's (16 x 64) tile lies in LDS indexed by the brick-local voxel number - the
+// layout the fp32 kernel leaves - so the epilogue is that kernel's: thread -> (column, channel), zdft_real<ZDZ, ZDSZ>, the
+// store address from g.sB, the `dead` zero fill for a sample that `valid` skips.  It is written out a second time, as
+// unproject_one_zd_kernel's gather is: as one function both kernels call it changed the instructions of all five fp32 ZD
+// instantiations (compared per kernel in the build's assembly), and those are shipped as they are.  Launch shape and LDS are
+// the fp32 ZD launch's.  Every ZD = false instantiation is unchanged.
+template <bool OUTCL, typename TO, int PS = 16, bool ZD = false>
+__global__ __launch_bounds__(512, ZD ? SP3D_ZD_MINW : SP3D_BRICK_MINW) void unproject_brick_h_kernel(Views hm, const float *__restrict__ cam,
                                                                   const float *__restrict__ centers,
                                                                   const uint8_t *__restrict__ valid,
                                                                   float *__restrict__ cubes, float *__restrict__ grids,
@@ -350,7 +357,8 @@ __global__ __launch_bounds__(512, SP3D_BRICK_MINW) void unproject_brick_h_kernel
     const int n = (min(vx, g.X - 1) * g.Y + min(vy, g.Y - 1)) * g.Z + min(vz, g.Z - 1);
     const int g32 = lane >> 1, q = lane & 1;
 
-    if (!valid[b]) { // skipped sample: zeros (project_layer.py:48,51,54)
+    const bool dead = ZD && !valid[b];      // ZD: a skipped sample's workgroups still emit their (all-zero) spectrum lines
+    if (!ZD && !valid[b]) { // skipped sample: zeros (project_layer.py:48,51,54)
         if (inb) {
             const size_t zo = (size_t)vx * g.sX + (size_t)vy * g.sY + vz;
             for (int j = 0; j < g.J; ++j)
@@ -364,7 +372,9 @@ __global__ __launch_bounds__(512, SP3D_BRICK_MINW) void unproject_brick_h_kernel
         return;
     }
 
-    if (z0 < g.Z) {
+    if (dead) {
+        for (int i = lane; i < JP * WOSTR; i += 64) ws[i] = 0.0f;
+    } else if (z0 < g.Z) {
         const float x = linspace_step(g.Lx, g.stepx, g.X, min(vx, g.X - 1)) + centers[3 * b + 0];
         const float y = linspace_step(g.Ly, g.stepy, g.Y, min(vy, g.Y - 1)) + centers[3 * b + 1];
         const float z = linspace_step(g.Lz, g.stepz, g.Z, min(vz, g.Z - 1)) + centers[3 * b + 2];
@@ -430,6 +440,26 @@ __global__ __launch_bounds__(512, SP3D_BRICK_MINW) void unproject_brick_h_kernel
     }
     if (OUTCL) return;
     __syncthreads();
+    if constexpr (ZD) {
+        // the ZD epilogue of unproject_brick_kernel, statement for statement: thread -> (column pos = 4 * lx + ly of the tile,
+        // channel c), one 128-byte line per (c, kz); a channel group of Jp = 32 leaves through `c >= g.J` and g.sB as there
+        constexpr int K = ZDSZ / 2 + 1;
+        const int pos = tid & 15, c = tid >> 4;
+        if (c >= g.J) return;
+        float v[ZDZ];
+#pragma unroll
+        for (int wz = 0; wz < ZDZ / BR; ++wz) {
+            const float4 q4 = *reinterpret_cast<const float4 *>(bsmem + wz * WLDS + c * WOSTR + pos * 4);
+            v[4 * wz] = q4.x; v[4 * wz + 1] = q4.y; v[4 * wz + 2] = q4.z; v[4 * wz + 3] = q4.w;
+        }
+        float2 *o = reinterpret_cast<float2 *>(cubes) + (size_t)b * (size_t)g.sB + (((size_t)c * K) * (size_t)g.bk_nxy + (size_t)t) * 16 + pos;
+        const size_t kstride = (size_t)g.bk_nxy * 16;
+        float re[K], im[K];
+        zdft_real<ZDZ, ZDSZ>(v, re, im);
+#pragma unroll
+        for (int k = 0; k < K; ++k) o[(size_t)k * kstride] = make_float2(re[k], im[k]);
+        return;
+    }
     // workgroup store of the (J, 4, 4, 4*zw) block: thread -> (channel phase jj, column, brick of the stack); the LDS tile
     // is indexed by the voxel's brick-local number lx*16 + ly*4 + lz, as the fp32 kernel's (slot*16 + g16)
     const float rzw = 1.0f / (float)zw;
@@ -458,6 +488,17 @@ __global__ __launch_bounds__(512, SP3D_BRICK_MINW) void unproject_brick_h_kernel
 // bf16 heat-maps: two lanes per pixel, 16 channels
 #define SP3D_BRICK_H(CL_, TO_, PS_) \
     SP3D_ROW(BrickFn, (KernelKey{16, PS_, false, 0, CL_, 1 | io_of<float, TO_>()}), unproject_brick_h_kernel, CL_, TO_, PS_)
+// bf16 maps with the z-spectrum result (SP3D_HM_BF16_IN next to SP3D_OUT_ZSPECTRUM): 13..16 joints at PS = 16, both channel
+// groups of a 32-element pixel at PS = 32 (group 1 has width 16 as well, its g.J = J - 16 channels picked by the epilogue).
+// A table of its own, for the reason given below; planned by tests/test_bf16_front_host.py, run by tests/test_gpu_bf16_front.py.
+#define SP3D_BRICK_H_ZD(PS_) \
+    SP3D_ROW(BrickFn, (KernelKey{16, PS_, true, 0, false, 1}), unproject_brick_h_kernel, false, float, PS_, true)
+static int find_brick_h_zspectrum_kernel(const KernelKey &key, const void *&fn, const char *&name)
+{
+    SP3D_BRICK_H_ZD(16) SP3D_BRICK_H_ZD(32)
+    return SP3D_EUNSUPPORTED;
+}
+
 // Jp = 32 channel groups with the z-spectrum result (SP3D_OUT_ZSPECTRUM): group 0 at JP = 16, group 1 at ceil4(J - 16).
 // The rows are a table of their own behind find_brick_kernel: the row census of tests/test_fwd_option_sweep_reference.py counts
 // the rows of find_brick_kernel that its sweep of cube-writing options reaches; these write no cubes, and each of them is
@@ -466,7 +507,7 @@ static int find_brick_zspectrum32_kernel(const KernelKey &key, const void *&fn, 
 {
     SP3D_BRICK(16, false, float, float, true, 32) SP3D_BRICK(4, false, float, float, true, 32)
     SP3D_BRICK(8, false, float, float, true, 32) SP3D_BRICK(12, false, float, float, true, 32)
-    return SP3D_EUNSUPPORTED;
+    return find_brick_h_zspectrum_kernel(key, fn, name);
 }
 
 int find_brick_kernel(const KernelKey &key, const void *&fn, const char *&name)

@@ -34,7 +34,26 @@ namespace sp3d {
 // (an unseen voxel passes, a NaN-zeroed one does not, a cube that `valid` skips gets zeros).  One 2-byte store per lane,
 // 128 contiguous bytes per wave.  The MASK = false instantiations are the kernels of the inference path, unchanged.
 // ------------------------------------------------------------------------------------------
-template <int VT, int CS, bool OUTCL, bool MASK = false>
+// TI (SP3D_HM_BF16_IN: TI = bf16_t): the element type of the heat-maps.  A bf16 tap is one 2-byte load (s_sample, s_row and
+// s_px stay element counts, the byte offset is (y0 * s_row + x0 * s_px) << 1), kept as loaded while the chunk's taps are in
+// flight and widened exactly (<< 16) where the interpolation consumes it: the same fp32 chain in the same order, so the
+// result has the bits of the TI = float kernel on the widened maps.  An odd channel of a bf16 (B,15,h,w) tensor or of a 16- or
+// 32-channel bf16 pixel is 2-byte aligned only and is read in place like any other.  TI = float is what it was.
+template <typename TI> struct OneTap;
+template <> struct OneTap<float> {
+    using raw = float;
+    static constexpr int SHIFT = 2;
+    __device__ __forceinline__ static raw load(const char *p) { return *reinterpret_cast<const float *>(p); }
+    __device__ __forceinline__ static float value(raw r) { return r; }
+};
+template <> struct OneTap<bf16_t> {
+    using raw = uint32_t;
+    static constexpr int SHIFT = 1;
+    __device__ __forceinline__ static raw load(const char *p) { return (uint32_t)*reinterpret_cast<const uint16_t *>(p); }
+    __device__ __forceinline__ static float value(raw r) { return __uint_as_float(r << 16); }
+};
+
+template <int VT, int CS, bool OUTCL, bool MASK = false, typename TI = float>
 __global__ __launch_bounds__(64) void unproject_one_kernel(Views hm, const float *__restrict__ cam,
                                                            const float *__restrict__ centers,
                                                            const uint8_t *__restrict__ valid, float *__restrict__ cubes,
@@ -72,8 +91,8 @@ __global__ __launch_bounds__(64) void unproject_one_kernel(Views hm, const float
         uint32_t have = 0;                          // wave-uniform: views with a record (some voxel of the wave sees them)
         uint32_t off[VT];                           // byte offset of the 2x2 block inside the sample's image
         float w00[VT], w10[VT], w01[VT], w11[VT];
-        float t00[VT], t10[VT], t01[VT], t11[VT];
-        const size_t pxb = (size_t)s_px * sizeof(float), rowb = (size_t)s_row * sizeof(float);
+        typename OneTap<TI>::raw t00[VT], t10[VT], t01[VT], t11[VT];
+        const size_t pxb = (size_t)s_px * sizeof(TI), rowb = (size_t)s_row * sizeof(TI);
 #pragma unroll
         for (int ch = 0; ch < NCH; ++ch) {
 #pragma unroll
@@ -89,7 +108,7 @@ __global__ __launch_bounds__(64) void unproject_one_kernel(Views hm, const float
                     const unsigned long long um = st.bm & ~st.nm;
                     if (go && um != 0ull) {         // else: no voxel of this wave sees camera c
                         const RecPk r = make_record_pk(lane_of(um), st.i, g.w, g.h);
-                        off[c] = (__umul24((unsigned)r.y0, (unsigned)s_row) + __umul24((unsigned)r.x0, (unsigned)s_px)) << 2;
+                        off[c] = (__umul24((unsigned)r.y0, (unsigned)s_row) + __umul24((unsigned)r.x0, (unsigned)s_px)) << OneTap<TI>::SHIFT;
                         w00[c] = r.wt.x; w10[c] = r.wt.y; w01[c] = r.wb.x; w11[c] = r.wb.y;
                         have |= 1u << c;
                     }
@@ -102,12 +121,12 @@ __global__ __launch_bounds__(64) void unproject_one_kernel(Views hm, const float
             // the interpolation consumes them (loads return in order).
 #pragma unroll
             for (int c = min((ch + 1) * CS, VT) - 1; c >= ch * CS; --c) {
-                const char *vb = reinterpret_cast<const char *>((c < g.V ? hm.p[c] : hm.p[0]) + (ptrdiff_t)bs * s_sample);
+                const char *vb = reinterpret_cast<const char *>(reinterpret_cast<const TI *>(c < g.V ? hm.p[c] : hm.p[0]) + (ptrdiff_t)bs * s_sample);
                 const char *vb2 = vb + rowb;
-                t11[c] = *reinterpret_cast<const float *>(vb2 + pxb + off[c]);
-                t01[c] = *reinterpret_cast<const float *>(vb2 + off[c]);
-                t10[c] = *reinterpret_cast<const float *>(vb + pxb + off[c]);
-                t00[c] = *reinterpret_cast<const float *>(vb + off[c]);
+                t11[c] = OneTap<TI>::load(vb2 + pxb + off[c]);
+                t01[c] = OneTap<TI>::load(vb2 + off[c]);
+                t10[c] = OneTap<TI>::load(vb + pxb + off[c]);
+                t00[c] = OneTap<TI>::load(vb + off[c]);
             }
             __builtin_amdgcn_sched_barrier(0);
         }
@@ -115,10 +134,10 @@ __global__ __launch_bounds__(64) void unproject_one_kernel(Views hm, const float
 #pragma unroll
         for (int c = 0; c < VT; ++c) {
             // ATen's bilinear chain: fma(se, wse, fma(sw, wsw, fma(ne, wne, nw * wnw)))
-            float v = t00[c] * w00[c];
-            v = fmaf(t10[c], w10[c], v);
-            v = fmaf(t01[c], w01[c], v);
-            v = fmaf(t11[c], w11[c], v);
+            float v = OneTap<TI>::value(t00[c]) * w00[c];
+            v = fmaf(OneTap<TI>::value(t10[c]), w10[c], v);
+            v = fmaf(OneTap<TI>::value(t01[c]), w01[c], v);
+            v = fmaf(OneTap<TI>::value(t11[c]), w11[c], v);
             const float a = acc + v;
             acc = ((have >> c) & 1u) ? a : acc;     // wave-uniform, as the pipelined kernels skip such a view
         }
@@ -168,7 +187,7 @@ __global__ __launch_bounds__(64) void unproject_one_kernel(Views hm, const float
 // blockIdx -> (sample, tile): the grid is exactly P * tiles workgroups; block bid runs on XCD bid % 8, and XCD x takes the
 // x-th eighth of the (sample, tile) sequence (tiles are x-major: a slab of the volume of one or two samples per XCD).
 // ------------------------------------------------------------------------------------------
-template <int VT, int CS>
+template <int VT, int CS, typename TI = float>
 __global__ __launch_bounds__(64 * (ZDZ / BR)) void unproject_one_zd_kernel(Views hm, const float *__restrict__ cam,
                                                                           const float *__restrict__ centers,
                                                                           const uint8_t *__restrict__ valid,
@@ -208,8 +227,8 @@ __global__ __launch_bounds__(64 * (ZDZ / BR)) void unproject_one_zd_kernel(Views
         uint32_t have = 0;                          // wave-uniform: views with a record (some voxel of the wave sees them)
         uint32_t off[VT];                           // byte offset of the 2x2 block inside the sample's image
         float w00[VT], w10[VT], w01[VT], w11[VT];
-        float t00[VT], t10[VT], t01[VT], t11[VT];
-        const size_t pxb = (size_t)s_px * sizeof(float), rowb = (size_t)s_row * sizeof(float);
+        typename OneTap<TI>::raw t00[VT], t10[VT], t01[VT], t11[VT];
+        const size_t pxb = (size_t)s_px * sizeof(TI), rowb = (size_t)s_row * sizeof(TI);
 #pragma unroll
         for (int ch = 0; ch < NCH; ++ch) {
 #pragma unroll
@@ -225,7 +244,7 @@ __global__ __launch_bounds__(64 * (ZDZ / BR)) void unproject_one_zd_kernel(Views
                     const unsigned long long um = st.bm & ~st.nm;
                     if (go && um != 0ull) {         // else: no voxel of this wave sees camera c
                         const RecPk r = make_record_pk(lane_of(um), st.i, g.w, g.h);
-                        off[c] = (__umul24((unsigned)r.y0, (unsigned)s_row) + __umul24((unsigned)r.x0, (unsigned)s_px)) << 2;
+                        off[c] = (__umul24((unsigned)r.y0, (unsigned)s_row) + __umul24((unsigned)r.x0, (unsigned)s_px)) << OneTap<TI>::SHIFT;
                         w00[c] = r.wt.x; w10[c] = r.wt.y; w01[c] = r.wb.x; w11[c] = r.wb.y;
                         have |= 1u << c;
                     }
@@ -236,12 +255,12 @@ __global__ __launch_bounds__(64 * (ZDZ / BR)) void unproject_one_zd_kernel(Views
             // branch between the loads, in the reverse of the order the interpolation consumes them
 #pragma unroll
             for (int c = min((ch + 1) * CS, VT) - 1; c >= ch * CS; --c) {
-                const char *vb = reinterpret_cast<const char *>((c < g.V ? hm.p[c] : hm.p[0]) + (ptrdiff_t)bs * s_sample);
+                const char *vb = reinterpret_cast<const char *>(reinterpret_cast<const TI *>(c < g.V ? hm.p[c] : hm.p[0]) + (ptrdiff_t)bs * s_sample);
                 const char *vb2 = vb + rowb;
-                t11[c] = *reinterpret_cast<const float *>(vb2 + pxb + off[c]);
-                t01[c] = *reinterpret_cast<const float *>(vb2 + off[c]);
-                t10[c] = *reinterpret_cast<const float *>(vb + pxb + off[c]);
-                t00[c] = *reinterpret_cast<const float *>(vb + off[c]);
+                t11[c] = OneTap<TI>::load(vb2 + pxb + off[c]);
+                t01[c] = OneTap<TI>::load(vb2 + off[c]);
+                t10[c] = OneTap<TI>::load(vb + pxb + off[c]);
+                t00[c] = OneTap<TI>::load(vb + off[c]);
             }
             __builtin_amdgcn_sched_barrier(0);
         }
@@ -249,10 +268,10 @@ __global__ __launch_bounds__(64 * (ZDZ / BR)) void unproject_one_zd_kernel(Views
 #pragma unroll
         for (int c = 0; c < VT; ++c) {
             // ATen's bilinear chain: fma(se, wse, fma(sw, wsw, fma(ne, wne, nw * wnw)))
-            float v = t00[c] * w00[c];
-            v = fmaf(t10[c], w10[c], v);
-            v = fmaf(t01[c], w01[c], v);
-            v = fmaf(t11[c], w11[c], v);
+            float v = OneTap<TI>::value(t00[c]) * w00[c];
+            v = fmaf(OneTap<TI>::value(t10[c]), w10[c], v);
+            v = fmaf(OneTap<TI>::value(t01[c]), w01[c], v);
+            v = fmaf(OneTap<TI>::value(t11[c]), w11[c], v);
             const float a = acc + v;
             acc = ((have >> c) & 1u) ? a : acc;     // wave-uniform, as the pipelined kernels skip such a view
         }
@@ -361,20 +380,40 @@ __global__ __launch_bounds__(64) void unproject_one_bwd_kernel(const float *__re
     SP3D_ROW(OneFn, (KernelKey{1, 1, VT_, CS_, true, 0}), unproject_one_kernel, VT_, CS_, true) \
     SP3D_ROW(OneFn, (KernelKey{1, 1, VT_, CS_, false, 4}), unproject_one_kernel, VT_, CS_, false, true) \
     SP3D_ROW(OneFn, (KernelKey{1, 1, VT_, CS_, true, 4}), unproject_one_kernel, VT_, CS_, true, true)
+// bf16 maps (SP3D_HM_BF16_IN): the same ladder, planar and channels-last results, no pass mask; key.io = 1.  Tables of their
+// own behind the fp32 ones, as find_brick_zspectrum32_kernel is behind find_brick_kernel
+#define SP3D_ONE_H(VT_, CS_) SP3D_ROW(OneFn, (KernelKey{1, 1, VT_, CS_, false, 1}), unproject_one_kernel, VT_, CS_, false, false, bf16_t) \
+    SP3D_ROW(OneFn, (KernelKey{1, 1, VT_, CS_, true, 1}), unproject_one_kernel, VT_, CS_, true, false, bf16_t)
+static int find_one_h_kernel(const KernelKey &key, const void *&fn, const char *&name)
+{
+    SP3D_ONE_H(1, 4) SP3D_ONE_H(2, 4) SP3D_ONE_H(3, 4) SP3D_ONE_H(4, 4) SP3D_ONE_H(5, 4) SP3D_ONE_H(6, 4) SP3D_ONE_H(8, 4)
+    SP3D_ONE_H(10, 8) SP3D_ONE_H(12, 8) SP3D_ONE_H(16, 8)
+    return SP3D_EUNSUPPORTED;
+}
+
 int find_one_kernel(const KernelKey &key, const void *&fn, const char *&name)
 {
     SP3D_ONE(1, 4) SP3D_ONE(2, 4) SP3D_ONE(3, 4) SP3D_ONE(4, 4) SP3D_ONE(5, 4) SP3D_ONE(6, 4) SP3D_ONE(8, 4) SP3D_ONE(10, 8)
     SP3D_ONE(12, 8) SP3D_ONE(16, 8)
-    return SP3D_EUNSUPPORTED;
+    return find_one_h_kernel(key, fn, name);
 }
 
 // the z-spectrum form (SP3D_HM_ONE_ZSPECTRUM): the same view slots and chunks; key.io = 8
 #define SP3D_ONE_ZD(VT_, CS_) SP3D_ROW(OneFn, (KernelKey{1, 1, VT_, CS_, false, 8}), unproject_one_zd_kernel, VT_, CS_)
+// ... and with bf16 maps (SP3D_HM_BF16_IN next to it); key.io = 9
+#define SP3D_ONE_ZD_H(VT_, CS_) SP3D_ROW(OneFn, (KernelKey{1, 1, VT_, CS_, false, 9}), unproject_one_zd_kernel, VT_, CS_, bf16_t)
+static int find_one_zd_h_kernel(const KernelKey &key, const void *&fn, const char *&name)
+{
+    SP3D_ONE_ZD_H(1, 4) SP3D_ONE_ZD_H(2, 4) SP3D_ONE_ZD_H(3, 4) SP3D_ONE_ZD_H(4, 4) SP3D_ONE_ZD_H(5, 4) SP3D_ONE_ZD_H(6, 4)
+    SP3D_ONE_ZD_H(8, 4) SP3D_ONE_ZD_H(10, 8) SP3D_ONE_ZD_H(12, 8) SP3D_ONE_ZD_H(16, 8)
+    return SP3D_EUNSUPPORTED;
+}
+
 int find_one_zd_kernel(const KernelKey &key, const void *&fn, const char *&name)
 {
     SP3D_ONE_ZD(1, 4) SP3D_ONE_ZD(2, 4) SP3D_ONE_ZD(3, 4) SP3D_ONE_ZD(4, 4) SP3D_ONE_ZD(5, 4) SP3D_ONE_ZD(6, 4) SP3D_ONE_ZD(8, 4)
     SP3D_ONE_ZD(10, 8) SP3D_ONE_ZD(12, 8) SP3D_ONE_ZD(16, 8)
-    return SP3D_EUNSUPPORTED;
+    return find_one_zd_h_kernel(key, fn, name);
 }
 
 } // namespace sp3d

@@ -56,15 +56,17 @@ class ProposalLayer(nn.Module):
 def one_front_route(net, hms) -> bool:
     """the ROOTNET_ROOTHM root net ``net`` (CuboidProposalNet or CuboidProposalNetSoft) takes its one-channel list ``hms``
     through ``ProjectLayer.get_voxel_zspectrum`` -> ``TiledZSpectrum`` -> V2V: both switches on (``ProjectLayer.one_zspectrum``,
-    ``V2VNet.one_front``; SP3D_ONE_FRONT=1), inference without grad on the GPU, fp32 storage, a list that
-    ``one_channel_source`` classifies, and a net whose opening conv starts from the spectrum (``V2VNet.wants_zspectrum``)"""
+    ``V2VNet.one_front``; SP3D_ONE_FRONT=1), inference without grad on the GPU, fp32 storage or ``ProjectLayer.bf16_maps``
+    (then bf16 tensors classify too), a list that ``one_channel_source`` classifies, and a net whose opening conv starts from
+    the spectrum (``V2VNet.wants_zspectrum``)"""
     from .project_layer import one_channel_source
     pl, v2v = net.project_layer, net.v2v_net
     if not (net.rootnet_roothm and pl.one_zspectrum and getattr(v2v, "one_front", False) and not torch.is_grad_enabled()):
         return False
-    if not (hms[0].is_cuda and hms[0].shape[1] == 1 and pl.io_dtype == torch.float32 and pl.mode in ("auto", "nhwc")):
+    if not (hms[0].is_cuda and hms[0].shape[1] == 1 and (pl.io_dtype == torch.float32 or pl.bf16_maps) and pl.mode in ("auto", "nhwc")):
         return False
-    return one_channel_source(hms) is not None and v2v.wants_zspectrum(*net.cube_size, 1) is not None
+    dtype = torch.bfloat16 if (pl.bf16_maps and hms[0].dtype == torch.bfloat16) else torch.float32
+    return one_channel_source(hms, dtype) is not None and v2v.wants_zspectrum(*net.cube_size, 1) is not None
 
 
 class CuboidProposalNet(nn.Module):
@@ -84,6 +86,11 @@ class CuboidProposalNet(nn.Module):
         """run the V2V stack in torch.channels_last_3d (MIOpen NDHWC kernels, no internal transposes)"""
         self.channels_last = bool(on)
         self.v2v_net.to(memory_format=torch.channels_last_3d if on else torch.contiguous_format)
+        return self
+
+    def use_bf16_heatmaps(self, on: bool = True):
+        """read the heat-maps as bf16 and keep every result fp32 (``ProjectLayer.bf16_maps``); no effect under autograd"""
+        self.project_layer.bf16_maps = bool(on)
         return self
 
     def forward(self, all_heatmaps, meta, flip_xcoords=None):
@@ -106,7 +113,7 @@ class CuboidProposalNet(nn.Module):
         # ... and, opt-in (SP3D_ONE_FRONT=1), for the one channel of ROOTNET_ROOTHM, read where it lies: one launch
         one = one_front_route(self, hms)
         sz = self.v2v_net.wants_zspectrum(*self.cube_size, hms[0].shape[1]) if cl16 or wide or one else None
-        if sz is not None and self.project_layer.io_dtype == torch.float32 and (jp == 16 or wide or one) \
+        if sz is not None and (self.project_layer.io_dtype == torch.float32 or self.project_layer.bf16_maps) and (jp == 16 or wide or one) \
                 and self.project_layer.mode in ("auto", "nhwc"):
             from .v2v_net import TiledZSpectrum
             spec = self.project_layer.get_voxel_zspectrum(hms, meta, self.grid_size, [self.grid_center], self.cube_size, sz,

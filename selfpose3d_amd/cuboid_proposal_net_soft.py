@@ -63,6 +63,11 @@ class CuboidProposalNetSoft(nn.Module):
         self.v2v_net.to(memory_format=torch.channels_last_3d if on else torch.contiguous_format)
         return self
 
+    def use_bf16_heatmaps(self, on: bool = True):
+        """read the heat-maps as bf16 and keep every result fp32 (``ProjectLayer.bf16_maps``); no effect under autograd"""
+        self.project_layer.bf16_maps = bool(on)
+        return self
+
     # -- shared: heat-maps -> root cubes ---------------------------------------------------------------
     def _root_cubes(self, hms, meta, flip_xcoords, one_front=False):
         # opt-in (SP3D_ONE_FRONT=1), ROOTNET_ROOTHM inference: the one channel read where it lies, its z-spectrum straight into

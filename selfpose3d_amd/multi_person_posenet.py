@@ -45,6 +45,16 @@ class MultiPersonPoseNet(nn.Module):
             pose_resnet.set_backbone_memory_format(self.backbone, on)
         return self
 
+    def use_bf16_heatmaps(self, on: bool = True):
+        """mixed-bf16 inference: the backbone hands its heat-maps over as bf16 (``PoseResNet.bf16_heatmaps``), the root and
+        pose nets read them as bf16 and keep every result fp32 (``ProjectLayer.bf16_maps``); no effect under autograd"""
+        if not self.train_only_2d:
+            self.root_net.use_bf16_heatmaps(on)
+            self.pose_net.use_bf16_heatmaps(on)
+        if isinstance(self.backbone, pose_resnet.PoseResNet):
+            self.backbone.bf16_heatmaps = bool(on)
+        return self
+
     def heatmaps(self, views, input_heatmaps):
         if views is None:
             return input_heatmaps

@@ -77,6 +77,17 @@ class MultiPersonPoseNetSSV(nn.Module):
                 pose_resnet.set_backbone_memory_format(net, on)
         return self
 
+    def use_bf16_heatmaps(self, on: bool = True):
+        """mixed-bf16 inference: the backbone hands its heat-maps over as bf16 (``PoseResNet.bf16_heatmaps``), the root and
+        pose nets read them as bf16 and keep every result fp32 (``ProjectLayer.bf16_maps``); no effect under autograd"""
+        for name in ("root_net", "pose_net"):
+            if hasattr(self, name):
+                getattr(self, name).use_bf16_heatmaps(on)
+        net = getattr(self.backbone, "backbone", self.backbone)     # PoseResAttnNet wraps its PoseResNet
+        if isinstance(net, pose_resnet.PoseResNet):
+            net.bf16_heatmaps = bool(on)
+        return self
+
     def _heatmaps(self, views, input_heatmaps):
         if views is None:
             return input_heatmaps

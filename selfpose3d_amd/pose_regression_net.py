@@ -43,6 +43,12 @@ class PoseRegressionNet(nn.Module):
         self.v2v_net.to(memory_format=torch.channels_last_3d if on else torch.contiguous_format)
         return self
 
+    def use_bf16_heatmaps(self, on: bool = True):
+        """read the heat-maps as bf16 and keep the person cubes fp32 (``ProjectLayer.bf16_maps``) in all three forwards; no
+        effect under autograd"""
+        self.project_layer.bf16_maps = bool(on)
+        return self
+
     @torch.no_grad()
     def forward_batched(self, all_heatmaps, meta, grid_centers, flip_xcoords=None, max_cubes_per_call: int = 8):
         """All person proposals of a batch at once (inference): grid_centers (B,K,5) -> pred (B,K,J,3).

@@ -134,6 +134,10 @@ _SPEC = {18: (BasicBlock, (2, 2, 2, 2)), 34: (BasicBlock, (3, 4, 6, 3)), 50: (Bo
 
 class PoseResNet(nn.Module):
     batch_views_in_training = True      # forward_views in train mode: one pass with per-view BatchNorm statistics (False: V calls)
+    # opt-in (the model classes' ``use_bf16_heatmaps()``): ``forward_views`` hands its channels-last buffer over as bf16 - half
+    # the heat-map bytes for ``ProjectLayer.bf16_maps`` to read.  Eval mode without grad on the GPU only; the cast is one torch
+    # pass over the buffer, not fused into the 1x1 head
+    bf16_heatmaps = False
 
     def __init__(self, cfg, num_layers=None):
         super().__init__()
@@ -256,6 +260,8 @@ class PoseResNet(nn.Module):
             bias = None if bias is None else torch.cat([bias, bias.new_zeros(jp - J)], 0)
         y = F.conv2d(feat, wgt, bias, fl.stride, fl.padding).contiguous(memory_format=torch.channels_last)
         packed = y.permute(0, 2, 3, 1).view(V, B, y.shape[2], y.shape[3], jp)
+        if self.bf16_heatmaps and not torch.is_grad_enabled() and jp in (16, 32) and packed.dtype == torch.float32:
+            packed = packed.to(torch.bfloat16)          # round to nearest even, one pass; the views below are bf16 tensors
         return nhwc_heatmap_views(packed, J)
 
 

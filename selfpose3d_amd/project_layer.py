@@ -92,8 +92,9 @@ def _packed_source(hms: Sequence[torch.Tensor], jp: int, dtype: torch.dtype):
     return base
 
 
-def one_channel_source(hms: Sequence[torch.Tensor]):
-    """``list[V] of (B,1,h,w)`` fp32 tensors that each are ONE channel of a wider tensor -> ``(layout, Jp)`` as the
+def one_channel_source(hms: Sequence[torch.Tensor], dtype: torch.dtype = torch.float32):
+    """``list[V] of (B,1,h,w)`` tensors of ``dtype`` (fp32; bf16 for ``ProjectLayer.bf16_maps``, whose byte limits count 2-byte
+    elements) that each are ONE channel of a wider tensor -> ``(layout, Jp)`` as the
     one-channel kernel addresses it (``SP3D_HM_ONE_CHANNEL``, include/sp3d.h), else ``None``.  Decided from shapes, dtypes
     and strides alone (no device access; CPU tensors classify the same way):
 
@@ -109,8 +110,9 @@ def one_channel_source(hms: Sequence[torch.Tensor]):
     if len(hms) == 0:
         return None
     first = None
+    esize = 2 if dtype == torch.bfloat16 else 4
     for t in hms:
-        if t.dim() != 4 or t.dtype != torch.float32 or t.shape != hms[0].shape:
+        if t.dim() != 4 or t.dtype != dtype or t.shape != hms[0].shape:
             return None
         B, J, h, w = t.shape
         if J != 1 or B < 1 or h < 2 or w < 2 or h * w > (1 << 24):
@@ -130,7 +132,7 @@ def one_channel_source(hms: Sequence[torch.Tensor]):
                 return None
             # the limits resolve_one (csrc/sp3d_unproject.hip, the host plan) answers SP3D_EUNSUPPORTED for - 32-bit byte offsets, 24-bit
             # multiplies - so that such a buffer keeps the packed path instead of raising
-            if h * w * sW * 4 > 0x7fffffff or w * sW >= (1 << 24):
+            if h * w * sW * esize > 0x7fffffff or w * sW >= (1 << 24):
                 return None
             form = (_lib.LAYOUT_NHWC, sW)
         if first is None:
@@ -321,6 +323,50 @@ class ProjectLayer(nn.Module):
         # of the one channel (SP3D_HM_ONE_ZSPECTRUM) - instead of raising.  Off until tools/bench_roothm_front.py has recorded
         # that the ROOTNET_ROOTHM root net is faster with it
         self.one_zspectrum = _lib.env_switch("SP3D_ONE_FRONT", False)
+        # opt-in (SP3D_BF16_MAPS=1 / ``bf16_maps = True``; the model classes' ``use_bf16_heatmaps()``): the heat-maps are kept and
+        # read as bf16, every result is fp32 ("mixed bf16", BASELINE configs[4], through the same fused fronts as fp32 maps:
+        # SP3D_HM_BF16_IN).  bf16 producers are read in place, fp32 producers are rounded by the re-tiling pass.  Inference only:
+        # a heat-map gradient ignores the switch, and a request no bf16 kernel covers widens the maps and takes the fp32 path.
+        # Not to be combined with ``io_dtype`` (bf16 cubes), which keeps its meaning and its refusals.
+        self.bf16_maps = _lib.env_switch("SP3D_BF16_MAPS", False)
+
+    def _bf16_maps_on(self, heatmaps) -> bool:
+        """``bf16_maps`` applies to this call: the switch is on and no heat-map gradient is wanted"""
+        if not self.bf16_maps:
+            return False
+        if self.io_dtype != torch.float32:
+            raise _lib.Sp3dError("ProjectLayer: bf16_maps (bf16 maps, fp32 results) and io_dtype (bf16 maps and cubes) exclude each other")
+        return not (torch.is_grad_enabled() and any(x.requires_grad for x in heatmaps))
+
+    def _bf16_packed(self, heatmaps, jp: int) -> torch.Tensor:
+        """the bf16 (V,B,h,w,jp) buffer of these maps: the producer's own, or one re-tiling pass (which rounds fp32 maps)"""
+        source = _packed_source(heatmaps, jp, torch.bfloat16)
+        if source is not None:
+            return source.detach()
+        if self.cache_packs:
+            return packed_heatmaps(heatmaps, jp, torch.bfloat16)
+        return _lib.pack_heatmaps([x.detach() for x in heatmaps], jp=jp, out_dtype=torch.bfloat16)
+
+    def _get_voxel_bf16(self, heatmaps, cam, centers, valid, grid_size, cube_size, want_grids, pad_channels, channels_last,
+                        sample_of, out):
+        """``get_voxel`` with ``bf16_maps`` on the NHWC path, no autograd: (cubes, grids) in fp32, or None when no bf16 kernel
+        covers the request (the caller then widens the maps and takes the fp32 path)."""
+        _, J, h, w = heatmaps[0].shape
+        P = int(centers.shape[0])
+        if J == 1:
+            one = one_channel_source(heatmaps, torch.bfloat16) if self.one_channel else None
+            if one is None:
+                return None
+            return _lib.unproject_fwd([x.detach() for x in heatmaps], one[0], one[1], cam, centers, valid, P, 4 if pad_channels else 1,
+                                      h, w, cube_size, grid_size, self.img_size, want_grids, channels_last=channels_last,
+                                      sample_of=sample_of, out=out, one_channel=True)
+        jp = self.jp_for(J)
+        if jp not in (16, 32) or J > 32:
+            return None
+        packed = self._bf16_packed(heatmaps, jp)
+        return _lib.unproject_fwd([packed[c] for c in range(len(heatmaps))], _lib.LAYOUT_NHWC, jp, cam, centers, valid, P,
+                                  jp if pad_channels else J, h, w, cube_size, grid_size, self.img_size, want_grids,
+                                  channels_last=channels_last, sample_of=sample_of, out_dtype=torch.float32, out=out)
 
     @contextlib.contextmanager
     def static_camera_table(self, table: torch.Tensor):
@@ -445,6 +491,15 @@ class ProjectLayer(nn.Module):
             channels_last = False
         if out is not None and (mode != "nhwc" or want_grids or pad_channels or channels_last):
             raise _lib.Sp3dError("get_voxel(out=...): planar NHWC-path result without grids only")
+        if self._bf16_maps_on(heatmaps):
+            got = self._get_voxel_bf16(heatmaps, cam, centers, valid, [float(v) for v in grid_size], [int(v) for v in cube_size],
+                                       bool(want_grids), bool(pad_channels), bool(channels_last), sample_of, out) \
+                if mode == "nhwc" else None
+            if got is not None:
+                return got[0], (got[1] if want_grids else None)
+            # no bf16 kernel covers this request (fewer than 13 joints on the packed path, the planar kernel above 32 joints or
+            # for a one-pixel map): the right answer from the fp32 path on the widened maps
+            heatmaps = [x.float() if x.dtype == torch.bfloat16 else x for x in heatmaps]
         cubes, grids = _UnprojectFn.apply(self, cam, centers, valid, [float(v) for v in grid_size],
                                           [int(v) for v in cube_size], bool(want_grids), mode, bool(pad_channels),
                                           bool(channels_last), sample_of, out, *heatmaps)
@@ -457,7 +512,9 @@ class ProjectLayer(nn.Module):
         4 x 4-tiled layout ``_lib.cfft2d_88_tiled`` reads.  Same reference semantics (project_layer.py:42-102).
         13..16 joints; 17..32 with ``wide_zspectrum``; with ``one_zspectrum`` a ``list[V] of (B,1,h,w)`` that
         ``one_channel_source`` classifies (a slice of a planar tensor, a slice of the (V,B,h,w,16|32) buffer of
-        ``PoseResNet.forward_views``, a contiguous (B,1,h,w)), read in place."""
+        ``PoseResNet.forward_views``, a contiguous (B,1,h,w)), read in place.  With ``bf16_maps`` the same three routes read
+        bf16 maps (SP3D_HM_BF16_IN: a bf16 producer's buffer or tensors in place, fp32 producers rounded by the re-tiling
+        pass); the spectrum is fp32 and bit-identical to the fp32 route's on the widened maps."""
         if torch.is_grad_enabled() and any(h.requires_grad for h in heatmaps):
             raise _lib.Sp3dError("get_voxel_zspectrum is an inference path (no autograd); use get_voxel")
         device = heatmaps[0].device
@@ -470,7 +527,9 @@ class ProjectLayer(nn.Module):
         wide = self.wide_zspectrum and jp == 32 and J <= 32
         # one channel of a wider tensor (the ROOTNET_ROOTHM root nets): strides are looked at only here, behind every refusal
         # that shapes alone decide
-        one = one_channel_source(heatmaps) if (self.one_zspectrum and J == 1 and self.io_dtype == torch.float32 and w >= 2
+        bf16 = self._bf16_maps_on(heatmaps)
+        one_dt = torch.bfloat16 if (bf16 and heatmaps[0].dtype == torch.bfloat16) else torch.float32
+        one = one_channel_source(heatmaps, one_dt) if (self.one_zspectrum and J == 1 and self.io_dtype == torch.float32 and w >= 2
                                                and h >= 2 and self.mode in ("auto", "nhwc")) else None
         if one is None and (self.io_dtype != torch.float32 or not (jp == 16 or wide) or self.mode not in ("auto", "nhwc")
                             or w < 2 or h < 2):
@@ -481,6 +540,10 @@ class ProjectLayer(nn.Module):
             return _lib.unproject_one_fwd_zspectrum([x.detach() for x in heatmaps], one[0], one[1], cam, centers, valid, B, h, w,
                                                     [int(v) for v in cube_size], [float(v) for v in grid_size], self.img_size,
                                                     int(SZ))
+        if bf16:    # 13..32 joints from bf16 pixels: the brick-h kernels with the z-spectrum result, one or two launches
+            packed = self._bf16_packed(heatmaps, jp)
+            return _lib.unproject_fwd_zspectrum([packed[c] for c in range(len(heatmaps))], jp, cam, centers, valid, B, J, h, w,
+                                                [int(v) for v in cube_size], [float(v) for v in grid_size], self.img_size, int(SZ))
         source = _packed_source(heatmaps, jp, torch.float32)
         if source is not None:
             packed = source.detach()

@@ -22,6 +22,9 @@ def main():
     ap.add_argument("--max-iters", type=int, default=None)
     ap.add_argument("--random-init", action="store_true",
                     help="validate untrained weights when no checkpoint exists (plumbing checks only)")
+    ap.add_argument("--bf16-heatmaps", action="store_true",
+                    help="mixed bf16 (BASELINE configs[4]): the backbone hands its heat-maps over as bf16, the root and pose nets "
+                         "read them as bf16 and keep every result fp32 (use_bf16_heatmaps; GPU only)")
     args, _ = ap.parse_known_args()
     cfg, rank, world, device, out = setup(args.cfg, "validate")
     loader = make_loader(cfg, args.frames, int(cfg.TEST.BATCH_SIZE), rank, world, seed=2, shuffle=False)
@@ -40,6 +43,10 @@ def main():
         raise ValueError(f"Check the model file for testing! ({test_file})")    # reference tools/validate_3d.py:91-92
     if device.type == "cuda":
         model.use_channels_last(True)
+    if args.bf16_heatmaps:
+        if device.type != "cuda":
+            raise SystemExit("--bf16-heatmaps: the bf16 heat-map kernels run on the GPU only")
+        model.use_bf16_heatmaps(True)
     validate_3d(cfg, model, loader, 0, out, with_ssv=args.with_ssv, device=device, max_iters=args.max_iters)
     if world > 1:
         torch.distributed.barrier()
