@@ -5,12 +5,14 @@ and :13-83 (``ProposalLayer``); checkpoint keys ``v2v_net.*`` are identical.
 """
 from __future__ import annotations
 
+from typing import NamedTuple, Optional
+
 import torch
 import torch.nn as nn
 
-from .project_layer import ProjectLayer, nhwc_direct_ok
+from .project_layer import ProjectLayer
 from .proposal import nms_with_locations
-from .v2v_net import V2VNet
+from .v2v_net import TiledZSpectrum, V2VNet
 
 
 class ProposalLayer(nn.Module):
@@ -53,20 +55,35 @@ class ProposalLayer(nn.Module):
         return grid_centers
 
 
-def one_front_route(net, hms) -> bool:
-    """the ROOTNET_ROOTHM root net ``net`` (CuboidProposalNet or CuboidProposalNetSoft) takes its one-channel list ``hms``
-    through ``ProjectLayer.get_voxel_zspectrum`` -> ``TiledZSpectrum`` -> V2V: both switches on (``ProjectLayer.one_zspectrum``,
-    ``V2VNet.one_front``; SP3D_ONE_FRONT=1), inference without grad on the GPU, fp32 storage or ``ProjectLayer.bf16_maps``
-    (then bf16 tensors classify too), a list that ``one_channel_source`` classifies, and a net whose opening conv starts from
-    the spectrum (``V2VNet.wants_zspectrum``)"""
-    from .project_layer import one_channel_source
+class Front(NamedTuple):
+    """the call a net makes for its V2V input: ``get_voxel_zspectrum(..., SZ=sz)`` -> ``TiledZSpectrum`` when ``sz`` is set, else
+    ``get_voxel(..., want_grids=False, pad_channels, channels_last)`` - with ``out``, into the opening conv's input view"""
+    sz: Optional[int]
+    pad_channels: bool
+    channels_last: bool
+    out: bool
+
+
+def front_rule(net, hms, fronts=()) -> Front:
+    """How ``net`` (``project_layer``, ``v2v_net``, ``cube_size``, ``channels_last``; ``rootnet_roothm`` where it has one) takes
+    the heat-map list ``hms`` to its V2V net.  ``fronts``: the fused z-spectrum fronts this caller takes - "zdft" (13..16
+    joints; and, where the spectrum is not wanted, channels-last 16-channel cubes for the HIP z pass), "wide" (17..32,
+    SP3D_WIDE_FRONT=1), "one" (the one channel of ROOTNET_ROOTHM, SP3D_ONE_FRONT=1).  Whether the layer delivers a front is
+    ``ProjectLayer.spectrum_route``'s answer and whether the opening conv starts from it ``V2VNet.wants_zspectrum``'s, so
+    the nets and the layer cannot disagree; ``out`` is ``ProjectLayer.takes_out``'s."""
     pl, v2v = net.project_layer, net.v2v_net
-    if not (net.rootnet_roothm and pl.one_zspectrum and getattr(v2v, "one_front", False) and not torch.is_grad_enabled()):
-        return False
-    if not (hms[0].is_cuda and hms[0].shape[1] == 1 and (pl.io_dtype == torch.float32 or pl.bf16_maps) and pl.mode in ("auto", "nhwc")):
-        return False
-    dtype = torch.bfloat16 if (pl.bf16_maps and hms[0].dtype == torch.bfloat16) else torch.float32
-    return one_channel_source(hms, dtype) is not None and v2v.wants_zspectrum(*net.cube_size, 1) is not None
+    planar = v2v.wants_planar_input() and hms[0].is_cuda      # FFT opening conv (inference, no grad): plain J-channel cubes
+    direct = planar and pl.takes_out(hms)                      # ... which the kernel writes into that conv's padded input buffer
+    route = pl.spectrum_route(hms) if direct and fronts else None
+    if route is not None:
+        # ... or not at all: the kernel emits the z-spectrum of the cubes, which is what the opening conv computes first
+        front = "one" if route.read == "one" else ("wide" if route.jp == 32 else "zdft")
+        if front in fronts and (front != "one" or getattr(net, "rootnet_roothm", False)):
+            sz = v2v.wants_zspectrum(*net.cube_size, hms[0].shape[1])
+            if sz is not None:
+                return Front(sz, False, False, False)
+    cl16 = direct and "zdft" in fronts and v2v.wants_channels_last_cubes(*net.cube_size)
+    return Front(None, cl16 or not planar, cl16 or (net.channels_last and not planar), direct and not cl16)
 
 
 class CuboidProposalNet(nn.Module):
@@ -98,32 +115,15 @@ class CuboidProposalNet(nn.Module):
             hms = [a[:, self.root_id:self.root_id + 1] for a in all_heatmaps]      # a view: read in place with ProjectLayer.one_channel, copied otherwise
         else:
             hms = all_heatmaps
-        planar = self.v2v_net.wants_planar_input() and hms[0].is_cuda      # FFT opening conv: plain J-channel cubes
-        # ... which the unprojection kernel writes straight into that conv's zero-padded input buffer
-        direct = planar and nhwc_direct_ok(hms, self.project_layer) and not torch.is_grad_enabled()
-        # ... on this grid as channels-last 16-channel cubes (its z pass is a HIP kernel that reads them as they are),
-        cl16 = direct and self.v2v_net.wants_channels_last_cubes(*self.cube_size)
-        # ... otherwise straight into that conv's zero-padded planar input buffer
-        # ... or, round 6, not at all: the kernel keeps a 4 x 4 bundle of z columns in LDS and emits their z-spectrum, which
-        # is what the opening conv computes from the cubes first (sp3d_unproject_fwd_zdft; bit-identical, one launch and
-        # 2 x 32.8 MB of HBM traffic less at B = 4)
-        # ... and, opt-in (SP3D_WIDE_FRONT=1), at 17..32 joints too: one launch per channel group of the 32-float pixel
-        jp = self.project_layer.jp_for(hms[0].shape[1])
-        wide = direct and jp == 32 and self.project_layer.wide_zspectrum and getattr(self.v2v_net, "wide_front", False)
-        # ... and, opt-in (SP3D_ONE_FRONT=1), for the one channel of ROOTNET_ROOTHM, read where it lies: one launch
-        one = one_front_route(self, hms)
-        sz = self.v2v_net.wants_zspectrum(*self.cube_size, hms[0].shape[1]) if cl16 or wide or one else None
-        if sz is not None and (self.project_layer.io_dtype == torch.float32 or self.project_layer.bf16_maps) and (jp == 16 or wide or one) \
-                and self.project_layer.mode in ("auto", "nhwc"):
-            from .v2v_net import TiledZSpectrum
-            spec = self.project_layer.get_voxel_zspectrum(hms, meta, self.grid_size, [self.grid_center], self.cube_size, sz,
+        front = front_rule(self, hms, fronts=("zdft", "wide", "one"))
+        if front.sz is not None:
+            spec = self.project_layer.get_voxel_zspectrum(hms, meta, self.grid_size, [self.grid_center], self.cube_size, front.sz,
                                                           flip_xcoords=flip_xcoords)
-            root_cubes = self.v2v_net(TiledZSpectrum(spec, *self.cube_size, sz)).squeeze(1)
+            root_cubes = self.v2v_net(TiledZSpectrum(spec, *self.cube_size, front.sz)).squeeze(1)
             return root_cubes, self.proposal_layer(root_cubes, meta)
-        out = self.v2v_net.input_view(hms[0].shape[0], *self.cube_size, hms[0].device) if direct and not cl16 else None
+        out = self.v2v_net.input_view(hms[0].shape[0], *self.cube_size, hms[0].device) if front.out else None
         cubes, _ = self.project_layer.get_voxel(hms, meta, self.grid_size, [self.grid_center], self.cube_size,
-                                                flip_xcoords=flip_xcoords, want_grids=False,
-                                                pad_channels=cl16 or not planar,
-                                                channels_last=cl16 or (self.channels_last and not planar), out=out)
+                                                flip_xcoords=flip_xcoords, want_grids=False, pad_channels=front.pad_channels,
+                                                channels_last=front.channels_last, out=out)
         root_cubes = self.v2v_net(cubes).squeeze(1)
         return root_cubes, self.proposal_layer(root_cubes, meta)

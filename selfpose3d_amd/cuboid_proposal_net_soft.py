@@ -16,9 +16,9 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from .cuboid_proposal_net import ProposalLayer
-from .project_layer import ProjectLayer, nhwc_direct_ok
-from .v2v_net import V2VNet
+from .cuboid_proposal_net import ProposalLayer, front_rule
+from .project_layer import ProjectLayer
+from .v2v_net import TiledZSpectrum, V2VNet
 
 
 class ProposalLayerSoft(ProposalLayer):
@@ -69,22 +69,18 @@ class CuboidProposalNetSoft(nn.Module):
         return self
 
     # -- shared: heat-maps -> root cubes ---------------------------------------------------------------
-    def _root_cubes(self, hms, meta, flip_xcoords, one_front=False):
-        # opt-in (SP3D_ONE_FRONT=1), ROOTNET_ROOTHM inference: the one channel read where it lies, its z-spectrum straight into
-        # the opening conv (cuboid_proposal_net.one_front_route); anything else runs the code below as before
-        from .cuboid_proposal_net import one_front_route
-        if one_front and one_front_route(self, hms):     # (the synthetic-root branch never asks)
-            from .v2v_net import TiledZSpectrum
-            sz = self.v2v_net.wants_zspectrum(*self.cube_size, 1)
-            spec = self.project_layer.get_voxel_zspectrum(hms, meta, self.grid_size, [self.grid_center], self.cube_size, sz,
+    def _root_cubes(self, hms, meta, flip_xcoords, fronts=()):
+        # of the fused z-spectrum fronts this net takes the one-channel one alone (get_grid_centres; the synthetic-root branch
+        # none): historical - it was added for the ROOTNET_ROOTHM nets only, the other two were never measured here
+        front = front_rule(self, hms, fronts)
+        if front.sz is not None:
+            spec = self.project_layer.get_voxel_zspectrum(hms, meta, self.grid_size, [self.grid_center], self.cube_size, front.sz,
                                                           flip_xcoords=flip_xcoords)
-            return self.v2v_net(TiledZSpectrum(spec, *self.cube_size, sz)).squeeze(1)
-        planar = self.v2v_net.wants_planar_input() and hms[0].is_cuda      # FFT opening conv: plain J-channel cubes
-        out = self.v2v_net.input_view(hms[0].shape[0], *self.cube_size, hms[0].device) \
-            if planar and nhwc_direct_ok(hms, self.project_layer) and not torch.is_grad_enabled() else None
+            return self.v2v_net(TiledZSpectrum(spec, *self.cube_size, front.sz)).squeeze(1)
+        out = self.v2v_net.input_view(hms[0].shape[0], *self.cube_size, hms[0].device) if front.out else None
         cubes, _ = self.project_layer.get_voxel(hms, meta, self.grid_size, [self.grid_center], self.cube_size,
-                                                flip_xcoords=flip_xcoords, want_grids=False, pad_channels=not planar,
-                                                channels_last=self.channels_last and not planar, out=out)
+                                                flip_xcoords=flip_xcoords, want_grids=False, pad_channels=front.pad_channels,
+                                                channels_last=front.channels_last, out=out)
         return self.v2v_net(cubes).squeeze(1)
 
     def get_grid_centres(self, all_heatmaps, meta, flip_xcoords=None):
@@ -92,7 +88,7 @@ class CuboidProposalNetSoft(nn.Module):
             hms = [a[:, self.root_id:self.root_id + 1] for a in all_heatmaps]      # a view: read in place with ProjectLayer.one_channel, copied otherwise
         else:
             hms = all_heatmaps
-        root_cubes = self._root_cubes(hms, meta, flip_xcoords, one_front=True)
+        root_cubes = self._root_cubes(hms, meta, flip_xcoords, fronts=("one",))
         return root_cubes, self.proposal_layer(root_cubes, meta, None)
 
     # -- synthetic-root branch (training) ---------------------------------------------------------------

@@ -11,7 +11,8 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import _lib
-from .project_layer import ProjectLayer, nhwc_direct_ok
+from .cuboid_proposal_net import front_rule
+from .project_layer import ProjectLayer
 from .v2v_net import V2VNet
 
 
@@ -69,9 +70,8 @@ class PoseRegressionNet(nn.Module):
         bi, ki = pairs[:, 0], pairs[:, 1]
         centers = grid_centers[bi, ki, :3].contiguous()
         flip = None if flip_xcoords is None else flip_xcoords
-        planar = self.v2v_net.wants_planar_input()                       # FFT opening conv: plain J-channel cubes
-        direct = self.v2v_net.input_chunk_views(P, max_cubes_per_call, *self.cube_size, device) \
-            if planar and nhwc_direct_ok(all_heatmaps, self.project_layer) else None
+        front = front_rule(self, all_heatmaps)                           # FFT opening conv: plain J-channel cubes
+        direct = self.v2v_net.input_chunk_views(P, max_cubes_per_call, *self.cube_size, device) if front.out else None
         if direct is not None:
             # the kernel writes every cube straight into the zero-padded input buffer of the FFT opening conv
             whole, chunks = direct
@@ -86,8 +86,8 @@ class PoseRegressionNet(nn.Module):
             pred[bi, ki] = torch.cat(outs, 0)
             return pred
         cubes, _ = self.project_layer.get_voxel(all_heatmaps, meta, self.grid_size, centers, self.cube_size,
-                                                flip_xcoords=flip, want_grids=False, pad_channels=not planar,
-                                                channels_last=self.channels_last and not planar, sample_of=bi)
+                                                flip_xcoords=flip, want_grids=False, pad_channels=front.pad_channels,
+                                                channels_last=front.channels_last, sample_of=bi)
         outs = []
         for s0 in range(0, P, max_cubes_per_call):
             chunk = cubes[s0:s0 + max_cubes_per_call]
@@ -98,7 +98,7 @@ class PoseRegressionNet(nn.Module):
             m = 1 << (n - 1).bit_length()
             if m != n:
                 chunk = torch.cat([chunk, chunk[-1:].expand(m - n, -1, -1, -1, -1)], 0)
-                if self.channels_last and not planar:
+                if front.channels_last:
                     chunk = chunk.contiguous(memory_format=torch.channels_last_3d)
             y = self.v2v_net(chunk)[:n]
             outs.append(_lib.soft_argmax_grid(y, cen, self.grid_size, self.cube_size, self.soft_argmax_layer.beta))

@@ -13,7 +13,8 @@ tensors must live on the GPU and libsp3d.so must be built, otherwise this raises
 from __future__ import annotations
 
 import contextlib
-from typing import Sequence
+import weakref
+from typing import NamedTuple, Sequence
 
 import numpy as np
 import torch
@@ -31,7 +32,6 @@ _PACK_CACHE: "list[tuple]" = []
 
 
 def packed_heatmaps(hms: Sequence[torch.Tensor], jp: int, dtype: torch.dtype = torch.float32) -> torch.Tensor:
-    import weakref
     if any(h.is_inference() for h in hms):      # inference tensors carry no version counter: nothing to key on
         return _lib.pack_heatmaps([x.detach() for x in hms], jp=jp, out_dtype=dtype)
     for refs, versions, cjp, packed in _PACK_CACHE:
@@ -64,17 +64,6 @@ def nhwc_heatmap_views(packed: torch.Tensor, num_joints: int) -> "list[torch.Ten
         t._sp3d_packed = (packed, c)
         views.append(t)
     return views
-
-
-def nhwc_direct_ok(hms: Sequence[torch.Tensor], layer: "ProjectLayer" = None) -> bool:
-    """``layer`` (mode "auto" or "nhwc") takes these heat-maps through the NHWC kernels, so that a producer may hand it an
-    ``out`` buffer (``get_voxel(out=...)``): up to 16 joints, and 17..32 joints when no heat-map gradient is requested"""
-    if layer is not None and layer.mode == "planar":
-        return False
-    J = int(hms[0].shape[1])
-    if J <= 16:
-        return True
-    return J <= 32 and not (torch.is_grad_enabled() and any(h.requires_grad for h in hms))
 
 
 def _packed_source(hms: Sequence[torch.Tensor], jp: int, dtype: torch.dtype):
@@ -158,98 +147,91 @@ def unproject_path(J: int, grad_hm: bool, h: int, w: int, mode: str, wide_grad: 
     return mode
 
 
+class Route(NamedTuple):
+    """How one ``ProjectLayer`` call becomes a ``_lib`` call.  ``ProjectLayer.route`` fills it from the
+    heat-maps' shapes, strides and dtypes, the gradient request, the layer's switches and the requested result; the
+    launchers below read the record and nothing else."""
+    read: str                       # "planar" | "packed": (V,B,h,w,jp), see _packed_maps | "one": one channel where it lies
+    layout: int                     # the _lib.LAYOUT_* the kernel is told
+    jp: int                         # packed: channel stride; one: the stride one_channel_source classified; planar: 0
+    elem: torch.dtype               # element type the kernel reads
+    write: str                      # "cubes" | "zdft" | "zspectrum" | "one_zspectrum"
+    J: int                          # channels the kernel writes
+    channels_last: bool = False
+    out: bool = False               # the caller's ``out`` receives the cubes
+    backward: str = "none"          # "none" | "planar" | "mask16" | "mask2x16" (17..32 joints) | "one"
+    autograd: bool = False          # the call goes through _UnprojectFn
+    widen: bool = False             # bf16 maps are widened first: ``bf16_maps`` on a request no bf16 kernel covers
+
+
+def _fp32_maps(hms):
+    return [x if (x.is_contiguous() and x.dtype == torch.float32) else x.contiguous().float() for x in hms]
+
+
+def _packed_maps(layer, heatmaps, jp: int, dtype: torch.dtype, fp32_copies: bool = False) -> torch.Tensor:
+    """the ``dtype`` (V,B,h,w,jp) buffer of these maps: the producer's own (no re-tiling pass), else the cached pack, else a
+    fresh pack (which rounds fp32 maps for a bf16 buffer; ``fp32_copies``: from contiguous fp32 copies, as the autograd
+    path always packed)"""
+    source = _packed_source(heatmaps, jp, dtype)
+    if source is not None:
+        return source.detach()
+    if layer.cache_packs:
+        return packed_heatmaps(heatmaps, jp, dtype)
+    hms = [x.detach() for x in heatmaps]
+    return _lib.pack_heatmaps(_fp32_maps(hms) if fp32_copies else hms, jp=jp, out_dtype=dtype)
+
+
+def _launch_cubes(layer, route, cam, centers, valid, grid_size, cube_size, want_grids, sample_of, out, heatmaps):
+    """the forward launch of a cubes route -> (cubes, grids | None, pass mask | None, the maps a planar backward reads)"""
+    _, _, h, w = heatmaps[0].shape
+    P = int(centers.shape[0])                 # number of output cubes (== batch unless `sample_of` is given)
+    X, Y, Z = cube_size
+    hms = [x.detach() for x in heatmaps]
+    # when a gradient will be asked for, the kernel also emits the clamp pass mask: the backward then scatters without
+    # re-reading any heat-map (17..32 joints: one 16-bit plane per channel group)
+    planes = {"mask16": (), "mask2x16": (2,), "one": ()}.get(route.backward)
+    mask = None if planes is None else torch.empty(planes + (P, X * Y * Z), dtype=torch.int16, device=cam.device)
+    geom = (cam, centers, valid, P, route.J, h, w, cube_size, grid_size, layer.img_size)
+    saved = ()
+    if route.read == "one" and mask is None:
+        # one channel of a wider tensor, read where it lies: no slice copy, no re-tiling pass, no pack-cache entry
+        cubes, grids = _lib.unproject_fwd(hms, route.layout, route.jp, *geom, want_grids, channels_last=route.channels_last,
+                                          sample_of=sample_of, out=out, one_channel=True)
+    elif route.read == "one":
+        cubes, grids = _lib.unproject_one_fwd_train(hms, route.layout, route.jp, *geom, mask, want_grids,
+                                                    channels_last=route.channels_last, sample_of=sample_of)
+    elif route.read == "packed":
+        fp32 = route.elem == torch.float32
+        packed = _packed_maps(layer, heatmaps, route.jp, route.elem, fp32_copies=fp32 and route.autograd)
+        # pad_channels (route.J == jp): the padded channels are zero in `packed`, the extra output channels exact zeros
+        cubes, grids = _lib.unproject_fwd([packed[c] for c in range(len(hms))], _lib.LAYOUT_NHWC, route.jp, *geom, want_grids,
+                                          channels_last=route.channels_last, sample_of=sample_of, out_dtype=layer.io_dtype,
+                                          pass_mask=mask, out=out, wide_mask=route.backward == "mask2x16")
+        if route.backward == "planar":
+            saved = _fp32_maps(hms) if fp32 and _packed_source(heatmaps, route.jp, route.elem) is None else hms
+    else:
+        saved = hms = _fp32_maps(hms)
+        cubes, grids = _lib.unproject_fwd(hms, _lib.LAYOUT_PLANAR, 0, *geom, want_grids, sample_of=sample_of)
+    return cubes, grids, mask, saved
+
+
 class _UnprojectFn(torch.autograd.Function):
     """autograd seam: gradient flows to the heat-maps only."""
 
     @staticmethod
-    def forward(ctx, layer, cam, centers, valid, grid_size, cube_size, want_grids, mode, pad_channels, channels_last,
-                sample_of, out, *heatmaps):
-        _, J, h, w = heatmaps[0].shape
-        B = int(centers.shape[0])                 # number of output cubes (== batch unless `sample_of` is given)
-        hms = [x.detach() for x in heatmaps]
-        io = layer.io_dtype
-        # one channel of a wider tensor (the root-joint map of the ROOTNET_ROOTHM root nets): read where it lies by the
-        # one-channel kernel - no slice copy, no re-tiling pass, no pack-cache entry.  Under this switch a heat-map gradient
-        # keeps the packed path below (its backward needs the pass mask); one_channel_grad is the switch for that case.
-        one = one_channel_source(hms) if (layer.one_channel and mode == "nhwc" and io == torch.float32 and J == 1
-                                          and not any(ctx.needs_input_grad[12:])) else None
-        if one is not None:
-            cubes, grids = _lib.unproject_fwd(hms, one[0], one[1], cam, centers, valid, B, 4 if pad_channels else 1, h, w,
-                                              cube_size, grid_size, layer.img_size, want_grids, channels_last=channels_last,
-                                              sample_of=sample_of, out=out, one_channel=True)
-            # nothing is saved for backward: no input of this call requires a gradient, so backward() is never entered
-            if grids is None:
-                grids = torch.empty(0, device=cubes.device)
-            ctx.mark_non_differentiable(grids)
-            return cubes, grids
-        # the same channel WITH a heat-map gradient (the root net's unprojection in the root-net and pose-net training stages),
-        # behind a switch of its own: the one-channel training forward writes the pass mask, backward() scatters the one
-        # channel into dense (V,B,h,w) planes - no slice copy, no re-tiling pass, no pack-cache entry, no pad channels
-        one_grad = one_channel_source(hms) if (layer.one_channel_grad and mode == "nhwc" and io == torch.float32 and J == 1
-                                               and any(ctx.needs_input_grad[12:])) else None
-        ctx.one_bwd = None
-        if one_grad is not None:
-            X, Y, Z = cube_size
-            mask = torch.empty((B, X * Y * Z), dtype=torch.int16, device=cam.device)
-            cubes, grids = _lib.unproject_one_fwd_train(hms, one_grad[0], one_grad[1], cam, centers, valid, B,
-                                                        4 if pad_channels else 1, h, w, cube_size, grid_size, layer.img_size,
-                                                        mask, want_grids, channels_last=channels_last, sample_of=sample_of)
-            ctx.packed_bwd = None
-            ctx.one_bwd = (mask, int(heatmaps[0].shape[0]), len(hms), h, w)
-            ctx.wide = False                      # the classifier answers for fp32 heat-maps only
-            ctx.layer = layer
-            ctx.geom = (tuple(grid_size), tuple(cube_size))
-            ctx.sample_of = sample_of
-            ctx.save_for_backward(cam, centers, valid)        # the one-channel backward reads no heat-map
-            if grids is None:
-                grids = torch.empty(0, device=cubes.device)
-            ctx.mark_non_differentiable(grids)
-            return cubes, grids
-        source = _packed_source(heatmaps, layer.jp_for(J), io) if mode == "nhwc" else None
-        if io == torch.float32 and source is None:
-            hms = [x if (x.is_contiguous() and x.dtype == torch.float32) else x.contiguous().float() for x in hms]
-        if mode == "nhwc":
-            if source is not None:
-                packed = source.detach()          # producer already emits (V,B,h,w,jp): no re-tiling pass
-            elif layer.cache_packs:
-                packed = packed_heatmaps(heatmaps, layer.jp_for(J), io)
-            else:
-                packed = _lib.pack_heatmaps(hms, jp=layer.jp_for(J), out_dtype=io)
-            jp = packed.shape[-1]
-            views = [packed[c] for c in range(len(hms))]
-            # when a gradient will be asked for, let the kernel also emit the clamp pass mask: the backward
-            # then runs the line-coalesced scatter without re-reading any heat-map
-            need_grad = io == torch.float32 and any(ctx.needs_input_grad[12:]) and w >= 2 and h >= 2 and \
-                (jp <= 16 or (jp == 32 and layer.wide_grad))
-            # 17..32 joints under ``wide_grad``: one 16-bit mask plane per channel group, read back by the wide scatter
-            two_planes = need_grad and jp == 32
-            X, Y, Z = cube_size
-            mask = torch.empty(((2,) if two_planes else ()) + (B, X * Y * Z), dtype=torch.int16, device=cam.device) if need_grad else None
-            # pad_channels: run the kernel over all jp channels - the padded ones are zero in `packed`,
-            # so the extra output channels are exact zeros at no extra cost
-            cubes, grids = _lib.unproject_fwd(views, _lib.LAYOUT_NHWC, jp, cam, centers, valid, B,
-                                              jp if pad_channels else J, h, w, cube_size, grid_size, layer.img_size,
-                                              want_grids, channels_last=channels_last, sample_of=sample_of,
-                                              out_dtype=io, pass_mask=mask, out=None if need_grad else out, wide_mask=two_planes)
-            ctx.packed_bwd = (mask, jp, int(heatmaps[0].shape[0]), len(hms), J, h, w) if need_grad else None
-            ctx.two_planes = two_planes
-        else:
-            ctx.packed_bwd = None
-            cubes, grids = _lib.unproject_fwd(hms, _lib.LAYOUT_PLANAR, 0, cam, centers, valid, B, J, h, w, cube_size,
-                                              grid_size, layer.img_size, want_grids, sample_of=sample_of)
+    def forward(ctx, layer, route, cam, centers, valid, grid_size, cube_size, want_grids, sample_of, out, *heatmaps):
+        cubes, grids, mask, saved = _launch_cubes(layer, route, cam, centers, valid, grid_size, cube_size, want_grids, sample_of,
+                                                  out, heatmaps)
         # float64 callers (the mixed-precision pins of tests/test_gpu_reference_pins_r3.py: a float64 model around THIS fp32
         # path): the kernels compute and store fp32, the results travel on in the caller's type
         ctx.wide = heatmaps[0].dtype == torch.float64
         if ctx.wide:
             cubes = cubes.double()
             grids = grids.double() if grids is not None else None
-        ctx.layer = layer
+        ctx.layer, ctx.route, ctx.mask, ctx.sample_of = layer, route, mask, sample_of
+        ctx.dims = (int(heatmaps[0].shape[0]), len(heatmaps)) + tuple(int(v) for v in heatmaps[0].shape[1:])
         ctx.geom = (tuple(grid_size), tuple(cube_size))
-        ctx.sample_of = sample_of
-        if ctx.packed_bwd is not None:
-            ctx.save_for_backward(cam, centers, valid)        # the packed backward reads no heat-map
-        else:
-            ctx.save_for_backward(cam, centers, valid, *hms)
+        ctx.save_for_backward(cam, centers, valid, *saved)        # the masked backwards read no heat-map
         if grids is None:
             grids = torch.empty(0, device=cubes.device)
         ctx.mark_non_differentiable(grids)
@@ -259,26 +241,24 @@ class _UnprojectFn(torch.autograd.Function):
     def backward(ctx, grad_cubes, _grad_grids):
         cam, centers, valid, *hms = ctx.saved_tensors
         grid_size, cube_size = ctx.geom
+        route, layer = ctx.route, ctx.layer
+        batch, nv, J, h, w = ctx.dims
         if ctx.wide:
             grad_cubes = grad_cubes.float()
             wide = lambda gs: tuple(x.double() for x in gs)
         else:
             wide = tuple
-        if ctx.one_bwd is not None:
-            mask, batch, nv, h, w = ctx.one_bwd
-            grads = _lib.unproject_one_bwd(cam, centers, valid, grad_cubes, mask, batch, nv, h, w, cube_size, grid_size,
-                                           ctx.layer.img_size, sample_of=ctx.sample_of,
-                                           deterministic=ctx.layer.deterministic_backward)
-            return (None,) * 12 + wide(grads)
-        if ctx.packed_bwd is not None:
-            mask, jp, batch, nv, J, h, w = ctx.packed_bwd
-            grads = _lib.unproject_bwd_packed(cam, centers, valid, grad_cubes, mask, batch, nv, J, jp, h, w, cube_size,
-                                              grid_size, ctx.layer.img_size, sample_of=ctx.sample_of,
-                                              deterministic=ctx.layer.deterministic_backward, wide=ctx.two_planes)
-            return (None,) * 12 + wide(grads)
-        grads = _lib.unproject_bwd(hms, cam, centers, valid, grad_cubes, cube_size, grid_size, ctx.layer.img_size,
-                                   sample_of=ctx.sample_of)
-        return (None,) * 12 + wide(grads)
+        if route.backward == "one":
+            grads = _lib.unproject_one_bwd(cam, centers, valid, grad_cubes, ctx.mask, batch, nv, h, w, cube_size, grid_size,
+                                           layer.img_size, sample_of=ctx.sample_of, deterministic=layer.deterministic_backward)
+        elif route.backward in ("mask16", "mask2x16"):
+            grads = _lib.unproject_bwd_packed(cam, centers, valid, grad_cubes, ctx.mask, batch, nv, J, route.jp, h, w, cube_size,
+                                              grid_size, layer.img_size, sample_of=ctx.sample_of,
+                                              deterministic=layer.deterministic_backward, wide=route.backward == "mask2x16")
+        else:
+            grads = _lib.unproject_bwd(hms, cam, centers, valid, grad_cubes, cube_size, grid_size, layer.img_size,
+                                       sample_of=ctx.sample_of)
+        return (None,) * 10 + wide(grads)
 
 
 class ProjectLayer(nn.Module):
@@ -298,6 +278,7 @@ class ProjectLayer(nn.Module):
         self._cam_key = None
         self._cam_dev = None
         self._static_cam = None       # see static_camera_table()
+        self._cam_ring, self._cam_slot = [], 0     # pinned staging buffers of camera_table()
         # gradient scatter in 64-bit fixed point (bit-identical run to run) instead of fp32 atomics; SP3D_BWD_DETERMINISTIC=1
         self.deterministic_backward = _lib.env_switch("SP3D_BWD_DETERMINISTIC", False)
         # opt-in (SP3D_ONE_CHANNEL=1 / ``one_channel = True``): a (B,1,h,w) heat-map list that is one channel of a wider
@@ -330,43 +311,95 @@ class ProjectLayer(nn.Module):
         # Not to be combined with ``io_dtype`` (bf16 cubes), which keeps its meaning and its refusals.
         self.bf16_maps = _lib.env_switch("SP3D_BF16_MAPS", False)
 
-    def _bf16_maps_on(self, heatmaps) -> bool:
-        """``bf16_maps`` applies to this call: the switch is on and no heat-map gradient is wanted"""
-        if not self.bf16_maps:
-            return False
-        if self.io_dtype != torch.float32:
-            raise _lib.Sp3dError("ProjectLayer: bf16_maps (bf16 maps, fp32 results) and io_dtype (bf16 maps and cubes) exclude each other")
-        return not (torch.is_grad_enabled() and any(x.requires_grad for x in heatmaps))
-
-    def _bf16_packed(self, heatmaps, jp: int) -> torch.Tensor:
-        """the bf16 (V,B,h,w,jp) buffer of these maps: the producer's own, or one re-tiling pass (which rounds fp32 maps)"""
-        source = _packed_source(heatmaps, jp, torch.bfloat16)
-        if source is not None:
-            return source.detach()
-        if self.cache_packs:
-            return packed_heatmaps(heatmaps, jp, torch.bfloat16)
-        return _lib.pack_heatmaps([x.detach() for x in heatmaps], jp=jp, out_dtype=torch.bfloat16)
-
-    def _get_voxel_bf16(self, heatmaps, cam, centers, valid, grid_size, cube_size, want_grids, pad_channels, channels_last,
-                        sample_of, out):
-        """``get_voxel`` with ``bf16_maps`` on the NHWC path, no autograd: (cubes, grids) in fp32, or None when no bf16 kernel
-        covers the request (the caller then widens the maps and takes the fp32 path)."""
+    # -- the route: one pure decision (no device access; CPU tensors classify the same way) --------------
+    def route(self, heatmaps, SZ=None, want_grids=True, pad_channels=False, channels_last=False, out=False) -> Route:
+        """The ``Route`` of ``get_voxel(heatmaps, ..., want_grids, pad_channels, channels_last, out=<given>)`` or, with ``SZ``,
+        of ``get_voxel_zspectrum(heatmaps, ..., SZ)`` (which has refused a heat-map gradient before it asks), or the
+        ``Sp3dError`` that call raises.  ``sample_of`` changes no route.  DESIGN.md §4.0a is this function as a table."""
+        fp32 = self.io_dtype == torch.float32
+        if SZ is not None:
+            if self.bf16_maps and not fp32:
+                raise _lib.Sp3dError("ProjectLayer: bf16_maps (bf16 maps, fp32 results) and io_dtype (bf16 maps and cubes) exclude each other")
+            route = self.spectrum_route(heatmaps)
+            if route is None:
+                raise _lib.Sp3dError("get_voxel_zspectrum: fp32 NHWC path with 13..16 joints only")
+            return route
         _, J, h, w = heatmaps[0].shape
-        P = int(centers.shape[0])
-        if J == 1:
-            one = one_channel_source(heatmaps, torch.bfloat16) if self.one_channel else None
-            if one is None:
-                return None
-            return _lib.unproject_fwd([x.detach() for x in heatmaps], one[0], one[1], cam, centers, valid, P, 4 if pad_channels else 1,
-                                      h, w, cube_size, grid_size, self.img_size, want_grids, channels_last=channels_last,
-                                      sample_of=sample_of, out=out, one_channel=True)
+        grad_hm = torch.is_grad_enabled() and any(x.requires_grad for x in heatmaps)
+        path = unproject_path(J, grad_hm, h, w, self.mode, self.wide_grad and fp32)
         jp = self.jp_for(J)
-        if jp not in (16, 32) or J > 32:
+        bricks = jp in (16, 32) and J <= 32           # 13..32 joints: what the kernels that read bf16 pixels cover
+        if not fp32 and (path != "nhwc" or not bricks):
+            raise _lib.Sp3dError("bf16 storage needs the NHWC path with 13..32 joints")
+        if path != "nhwc" or J > 16:
+            pad_channels = channels_last = False
+        if channels_last and not pad_channels and (J & 3):
+            channels_last = False
+        # the pass mask of a wanted gradient: the masked training forwards write fresh cubes only
+        masked = path == "nhwc" and fp32 and grad_hm and w >= 2 and h >= 2 and (jp <= 16 or (jp == 32 and self.wide_grad))
+        one_grad = path == "nhwc" and fp32 and grad_hm and J == 1 and self.one_channel_grad and one_channel_source(heatmaps)
+        if out and (path != "nhwc" or want_grids or pad_channels or channels_last or masked or one_grad):
+            raise _lib.Sp3dError("get_voxel(out=...): planar NHWC-path result without grids only")
+        if self.bf16_maps and not fp32:
+            raise _lib.Sp3dError("ProjectLayer: bf16_maps (bf16 maps, fp32 results) and io_dtype (bf16 maps and cubes) exclude each other")
+        if path == "planar":
+            return Route("planar", _lib.LAYOUT_PLANAR, 0, torch.float32, "cubes", J, backward="planar" if grad_hm else "none",
+                         autograd=True, widen=self.bf16_maps and not grad_hm and heatmaps[0].dtype == torch.bfloat16)
+        J_one = 4 if pad_channels else 1              # the one-channel kernels: the value + three zero channels
+        widen, probe = False, heatmaps
+        if self.bf16_maps and not grad_hm:            # bf16 pixels in, fp32 cubes out, no autograd
+            one = one_channel_source(heatmaps, torch.bfloat16) if (J == 1 and self.one_channel) else None
+            if one:
+                return Route("one", one[0], one[1], torch.bfloat16, "cubes", J_one, channels_last, out)
+            if J != 1 and bricks:
+                return Route("packed", _lib.LAYOUT_NHWC, jp, torch.bfloat16, "cubes", jp if pad_channels else J, channels_last, out)
+            # no bf16 kernel covers the request (fewer than 13 joints on the packed path): the fp32 routes below on the widened
+            # maps - whose strides are what widening will give them, asked of meta tensors
+            widen = heatmaps[0].dtype == torch.bfloat16
+            if widen and J == 1 and self.one_channel:
+                probe = [torch.empty_strided(tuple(x.shape), x.stride(), dtype=x.dtype, device="meta").float() for x in heatmaps]
+        if one_grad:
+            return Route("one", one_grad[0], one_grad[1], torch.float32, "cubes", J_one, channels_last, backward="one", autograd=True)
+        one = one_channel_source(probe) if (fp32 and J == 1 and self.one_channel and not grad_hm) else None
+        if one:
+            return Route("one", one[0], one[1], torch.float32, "cubes", J_one, channels_last, out, autograd=True, widen=widen)
+        backward = ("mask2x16" if jp == 32 else "mask16") if masked else ("planar" if grad_hm else "none")
+        return Route("packed", _lib.LAYOUT_NHWC, jp, self.io_dtype, "cubes", jp if pad_channels else J, channels_last, out, backward,
+                     autograd=True, widen=widen)
+
+    def spectrum_route(self, heatmaps):
+        """the ``Route`` of ``get_voxel_zspectrum`` for these maps (inference: no gradient is looked at), or None where it
+        refuses: 13..16 joints, 17..32 with ``wide_zspectrum``, one channel in place with ``one_zspectrum``; fp32 storage"""
+        _, J, h, w = heatmaps[0].shape
+        if self.io_dtype != torch.float32 or self.mode not in ("auto", "nhwc") or w < 2 or h < 2:
             return None
-        packed = self._bf16_packed(heatmaps, jp)
-        return _lib.unproject_fwd([packed[c] for c in range(len(heatmaps))], _lib.LAYOUT_NHWC, jp, cam, centers, valid, P,
-                                  jp if pad_channels else J, h, w, cube_size, grid_size, self.img_size, want_grids,
-                                  channels_last=channels_last, sample_of=sample_of, out_dtype=torch.float32, out=out)
+        if J == 1 and self.one_zspectrum:     # strides are looked at only here, behind every refusal that shapes alone decide
+            dtype = torch.bfloat16 if (self.bf16_maps and heatmaps[0].dtype == torch.bfloat16) else torch.float32
+            one = one_channel_source(heatmaps, dtype)
+            if one:
+                return Route("one", one[0], one[1], dtype, "one_zspectrum", 1)
+        jp = self.jp_for(J)
+        if jp == 16 or (jp == 32 and J <= 32 and self.wide_zspectrum):
+            # bf16 pixels and 17..32 joints: the brick kernels with the z-spectrum result, one launch per channel group
+            if self.bf16_maps:
+                return Route("packed", _lib.LAYOUT_NHWC, jp, torch.bfloat16, "zspectrum", J)
+            return Route("packed", _lib.LAYOUT_NHWC, jp, torch.float32, "zspectrum" if jp == 32 else "zdft", J)
+        return None
+
+    def takes_out(self, heatmaps) -> bool:
+        """``get_voxel(heatmaps, ..., want_grids=False, out=...)`` writes into an ``out`` buffer: whoever owns one asks here"""
+        try:
+            return self.route(heatmaps, want_grids=False, out=True).out
+        except _lib.Sp3dError:
+            return False
+
+    def _require_maps(self, heatmaps):
+        if not heatmaps[0].is_cuda:
+            raise _lib.Sp3dError("ProjectLayer: heat-maps must be on the GPU (no CPU fallback)")
+        _, _, h, w = heatmaps[0].shape
+        if [w, h] != self.heatmap_size:
+            # the reference samples with cfg HEATMAP_SIZE (project_layer.py:50) whatever the tensor says
+            raise _lib.Sp3dError(f"heat-map tensor is {w}x{h} but cfg.NETWORK.HEATMAP_SIZE is {self.heatmap_size}")
 
     @contextlib.contextmanager
     def static_camera_table(self, table: torch.Tensor):
@@ -397,8 +430,7 @@ class ProjectLayer(nn.Module):
         if key != self._cam_key:
             tab = torch.from_numpy(pack_cameras(meta, batch, self.img_size, flip_xcoords))
             if device.type == "cuda":
-                ring = self.__dict__.setdefault("_cam_ring", [])
-                slot = self.__dict__.get("_cam_slot", 0)
+                ring, slot = self._cam_ring, self._cam_slot
                 if len(ring) < 4 or ring[slot][0].shape != tab.shape:
                     entry = [torch.empty_like(tab).pin_memory(), torch.cuda.Event()]
                     if len(ring) < 4:
@@ -413,7 +445,7 @@ class ProjectLayer(nn.Module):
                 dev_tab = torch.empty(tab.shape, dtype=torch.float32, device=device)
                 dev_tab.copy_(pinned, non_blocking=True)
                 ev.record(torch.cuda.current_stream(device))
-                self.__dict__["_cam_slot"] = (slot + 1) % 4
+                self._cam_slot = (slot + 1) % 4
                 self._cam_dev = dev_tab
             else:
                 self._cam_dev = tab.to(device)
@@ -464,13 +496,9 @@ class ProjectLayer(nn.Module):
         ``sample_of`` (int (P,)) with ``grid_center`` (P,5|3): P cubes, cube p read from sample
         sample_of[p] (all person proposals of a batch in one launch); ``out``: a (P,J,X,Y,Z) view of a larger buffer
         (z contiguous) that receives the planar result directly - no grids, inference only."""
-        device = heatmaps[0].device
-        if not heatmaps[0].is_cuda:
-            raise _lib.Sp3dError("ProjectLayer: heat-maps must be on the GPU (no CPU fallback)")
-        B, J, h, w = heatmaps[0].shape
-        if [w, h] != self.heatmap_size:
-            # the reference samples with cfg HEATMAP_SIZE (project_layer.py:50) whatever the tensor says
-            raise _lib.Sp3dError(f"heat-map tensor is {w}x{h} but cfg.NETWORK.HEATMAP_SIZE is {self.heatmap_size}")
+        self._require_maps(heatmaps)
+        route = self.route(heatmaps, None, bool(want_grids), bool(pad_channels), bool(channels_last), out is not None)
+        device, B = heatmaps[0].device, heatmaps[0].shape[0]
         cam = self.camera_table(meta, B, flip_xcoords, device)
         if sample_of is not None:
             sample_of = sample_of.to(device=device, dtype=torch.int32).contiguous()
@@ -481,28 +509,14 @@ class ProjectLayer(nn.Module):
             cube_size = [cube_size] * 3
         if isinstance(grid_size, (int, float)):
             grid_size = [grid_size] * 3
-        grad_hm = torch.is_grad_enabled() and any(x.requires_grad for x in heatmaps)
-        mode = unproject_path(J, grad_hm, h, w, self.mode, self.wide_grad and self.io_dtype == torch.float32)
-        if self.io_dtype != torch.float32 and (mode != "nhwc" or self.jp_for(J) not in (16, 32) or J > 32):
-            raise _lib.Sp3dError("bf16 storage needs the NHWC path with 13..32 joints")
-        if mode != "nhwc" or J > 16:
-            pad_channels = channels_last = False
-        if channels_last and not pad_channels and (J & 3):
-            channels_last = False
-        if out is not None and (mode != "nhwc" or want_grids or pad_channels or channels_last):
-            raise _lib.Sp3dError("get_voxel(out=...): planar NHWC-path result without grids only")
-        if self._bf16_maps_on(heatmaps):
-            got = self._get_voxel_bf16(heatmaps, cam, centers, valid, [float(v) for v in grid_size], [int(v) for v in cube_size],
-                                       bool(want_grids), bool(pad_channels), bool(channels_last), sample_of, out) \
-                if mode == "nhwc" else None
-            if got is not None:
-                return got[0], (got[1] if want_grids else None)
-            # no bf16 kernel covers this request (fewer than 13 joints on the packed path, the planar kernel above 32 joints or
-            # for a one-pixel map): the right answer from the fp32 path on the widened maps
+        if route.widen:      # the right answer from the fp32 path on the widened maps
             heatmaps = [x.float() if x.dtype == torch.bfloat16 else x for x in heatmaps]
-        cubes, grids = _UnprojectFn.apply(self, cam, centers, valid, [float(v) for v in grid_size],
-                                          [int(v) for v in cube_size], bool(want_grids), mode, bool(pad_channels),
-                                          bool(channels_last), sample_of, out, *heatmaps)
+        args = (self, route, cam, centers, valid, [float(v) for v in grid_size], [int(v) for v in cube_size], bool(want_grids),
+                sample_of, out)
+        if route.autograd:
+            cubes, grids = _UnprojectFn.apply(*args, *heatmaps)
+        else:
+            cubes, grids, _, _ = _launch_cubes(*args, heatmaps)
         return cubes, (grids if want_grids else None)
 
     def get_voxel_zspectrum(self, heatmaps, meta, grid_size, grid_center, cube_size, SZ: int, flip_xcoords=None):
@@ -517,45 +531,19 @@ class ProjectLayer(nn.Module):
         pass); the spectrum is fp32 and bit-identical to the fp32 route's on the widened maps."""
         if torch.is_grad_enabled() and any(h.requires_grad for h in heatmaps):
             raise _lib.Sp3dError("get_voxel_zspectrum is an inference path (no autograd); use get_voxel")
+        self._require_maps(heatmaps)
+        route = self.route(heatmaps, SZ)
         device = heatmaps[0].device
-        if not heatmaps[0].is_cuda:
-            raise _lib.Sp3dError("ProjectLayer: heat-maps must be on the GPU (no CPU fallback)")
         B, J, h, w = heatmaps[0].shape
-        if [w, h] != self.heatmap_size:
-            raise _lib.Sp3dError(f"heat-map tensor is {w}x{h} but cfg.NETWORK.HEATMAP_SIZE is {self.heatmap_size}")
-        jp = self.jp_for(J)
-        wide = self.wide_zspectrum and jp == 32 and J <= 32
-        # one channel of a wider tensor (the ROOTNET_ROOTHM root nets): strides are looked at only here, behind every refusal
-        # that shapes alone decide
-        bf16 = self._bf16_maps_on(heatmaps)
-        one_dt = torch.bfloat16 if (bf16 and heatmaps[0].dtype == torch.bfloat16) else torch.float32
-        one = one_channel_source(heatmaps, one_dt) if (self.one_zspectrum and J == 1 and self.io_dtype == torch.float32 and w >= 2
-                                               and h >= 2 and self.mode in ("auto", "nhwc")) else None
-        if one is None and (self.io_dtype != torch.float32 or not (jp == 16 or wide) or self.mode not in ("auto", "nhwc")
-                            or w < 2 or h < 2):
-            raise _lib.Sp3dError("get_voxel_zspectrum: fp32 NHWC path with 13..16 joints only")
         cam = self.camera_table(meta, B, flip_xcoords, device)
         centers, valid = self.centers_valid(grid_center, B, device)
-        if one is not None:     # read where it lies: no slice copy, no re-tiling pass, no pack-cache entry
-            return _lib.unproject_one_fwd_zspectrum([x.detach() for x in heatmaps], one[0], one[1], cam, centers, valid, B, h, w,
-                                                    [int(v) for v in cube_size], [float(v) for v in grid_size], self.img_size,
-                                                    int(SZ))
-        if bf16:    # 13..32 joints from bf16 pixels: the brick-h kernels with the z-spectrum result, one or two launches
-            packed = self._bf16_packed(heatmaps, jp)
-            return _lib.unproject_fwd_zspectrum([packed[c] for c in range(len(heatmaps))], jp, cam, centers, valid, B, J, h, w,
-                                                [int(v) for v in cube_size], [float(v) for v in grid_size], self.img_size, int(SZ))
-        source = _packed_source(heatmaps, jp, torch.float32)
-        if source is not None:
-            packed = source.detach()
-        elif self.cache_packs:
-            packed = packed_heatmaps(heatmaps, jp, torch.float32)
-        else:
-            packed = _lib.pack_heatmaps([x.detach() for x in heatmaps], jp=jp)
-        if wide:    # 17..32 joints: one launch per channel group into one spectrum (SP3D_OUT_ZSPECTRUM)
-            return _lib.unproject_fwd_zspectrum([packed[c] for c in range(len(heatmaps))], 32, cam, centers, valid, B, J, h, w,
-                                                [int(v) for v in cube_size], [float(v) for v in grid_size], self.img_size, int(SZ))
-        return _lib.unproject_fwd_zdft([packed[c] for c in range(len(heatmaps))], 16, cam, centers, valid, B, J, h, w,
-                                       [int(v) for v in cube_size], [float(v) for v in grid_size], self.img_size, int(SZ))
+        geom = (cam, centers, valid, B)
+        tail = (h, w, [int(v) for v in cube_size], [float(v) for v in grid_size], self.img_size, int(SZ))
+        if route.read == "one":     # read where it lies: no slice copy, no re-tiling pass, no pack-cache entry
+            return _lib.unproject_one_fwd_zspectrum([x.detach() for x in heatmaps], route.layout, route.jp, *geom, *tail)
+        packed = _packed_maps(self, heatmaps, route.jp, route.elem)
+        launch = _lib.unproject_fwd_zdft if route.write == "zdft" else _lib.unproject_fwd_zspectrum
+        return launch([packed[c] for c in range(len(heatmaps))], route.jp, *geom, J, *tail)
 
     def forward(self, heatmaps, meta, grid_size, grid_center, cube_size, flip_xcoords=None):
         return self.get_voxel(heatmaps, meta, grid_size, grid_center, cube_size, flip_xcoords=flip_xcoords)
