@@ -156,7 +156,26 @@ enum {
      * next to SP3D_OUT_CHANNELS_LAST without SP3D_HM_ONE_CHANNEL; on sp3d_unproject_fwd_train and
      * sp3d_unproject_one_fwd_train; on sp3d_unproject_fwd_strided next to either spectrum flag.  sp3d_unproject_fwd_zdft has
      * no layout word and takes fp32 maps only.  SP3D_HM_BF16 itself keeps every refusal it has. */
-    SP3D_HM_BF16_IN = 0x8000
+    SP3D_HM_BF16_IN = 0x8000,
+    /* OR-ed into hm_layout of sp3d_unproject_fwd_train and sp3d_unproject_one_fwd_train ONLY: the heat-maps are bf16, every
+     * result (cubes, grids) is fp32 and the pass mask keeps its format, so either backward reads it - training through bf16
+     * heat-maps without a widened copy.  A bf16 value is widened exactly (<< 16) and goes through the fp32 chain of the fp32
+     * training forward in the same order: cubes, grids and pass-mask words are bit-identical to that entry's results on the
+     * widened maps.
+     *   sp3d_unproject_fwd_train      SP3D_LAYOUT_NHWC, bf16 pixels of Jp == 16 elements, J <= 16: every result form the fp32
+     *                                 training forward takes at Jp = 16 (planar, SP3D_OUT_CHANNELS_LAST with J % 4 == 0), with
+     *                                 or without sample_of and grids.  With SP3D_HM_WIDE_MASK: Jp == 32, 1 <= J <= 32, planar
+     *                                 results, the two channel-group launches documented there; group 1's views start 16 bf16
+     *                                 elements (32 bytes) into the pixel
+     *   sp3d_unproject_one_fwd_train  either layout, J = 1 or 4, a channels-last result at J = 4; hm_views[c] needs 2-byte
+     *                                 alignment only, Jp and the strides it implies are in bf16 elements, and "a sample of more
+     *                                 than 2^31 bytes" counts 2-byte elements
+     * SP3D_EUNSUPPORTED, before any launch: on sp3d_unproject_fwd, _fwd_indexed and _fwd_strided; next to SP3D_HM_BF16,
+     * SP3D_OUT_BF16, SP3D_HM_BF16_IN, SP3D_OUT_ZSPECTRUM or SP3D_HM_ONE_ZSPECTRUM; on sp3d_unproject_fwd_train with
+     * SP3D_LAYOUT_PLANAR, with Jp in 4/8/12, with Jp == 32 without SP3D_HM_WIDE_MASK, or with SP3D_HM_ONE_CHANNEL; for
+     * heat-maps narrower or lower than 2 pixels or of more than 2^24 pixels.  sp3d_unproject_fwd_zdft has no layout word.
+     * Everything refused without the flag stays refused with the same code. */
+    SP3D_HM_BF16_TRAIN = 0x10000
 };
 
 int sp3d_abi_version(void);
@@ -260,6 +279,8 @@ int sp3d_unproject_bwd_indexed(const float *const *hm_views, const float *cam, c
  * are the words of a cube that `valid` skips.  sp3d_unproject_bwd_packed then needs no
  * heat-maps: it accumulates into grad_packed (V,B,h,w,Jp) fp32 channels-last, ZERO-FILLED by the caller,
  * so that one atomic instruction covers whole 64-byte pixels (15x the L2 atomic rate of planar scatter).
+ * With SP3D_HM_BF16_TRAIN in hm_layout the heat-maps are bf16 pixels of Jp == 16 (or 32 with SP3D_HM_WIDE_MASK) elements:
+ * same cubes, grids and mask words as on the widened maps (see the flag).
  */
 int sp3d_unproject_fwd_train(const float *const *hm_views, int hm_layout, int Jp, const float *cam,
                              const int32_t *sample_of, const float *centers, const uint8_t *valid, float *cubes,
@@ -325,6 +346,8 @@ int sp3d_fixed_to_float(const int64_t *acc, float *out, const float *scale, int6
  * heat-maps narrower or lower than 2 pixels or of more than 2^24 pixels, a sample of more than 2^31 bytes; SP3D_EINVAL for
  * Jp < 1, V > SP3D_MAX_VIEWS, an unknown layout byte; SP3D_ENULL for a missing pointer (grids may be NULL).
  * sp3d_unproject_fwd_train itself keeps refusing SP3D_HM_ONE_CHANNEL.
+ * With SP3D_HM_BF16_TRAIN in hm_layout the one channel is read from bf16 tensors (2-byte taps, 2-byte alignment, Jp in bf16
+ * elements, the 2^31-byte limit counted in 2-byte elements): same cubes, grids and mask words as on the widened maps.
  */
 int sp3d_unproject_one_fwd_train(const float *const *hm_views, int hm_layout, int Jp, const float *cam,
                                  const int32_t *sample_of, const float *centers, const uint8_t *valid, float *cubes,

@@ -28,6 +28,7 @@ HM_WIDE_MASK = 0x1000       # sp3d_unproject_fwd_train at Jp = 32: a (2, P, N) p
 OUT_ZSPECTRUM = 0x2000      # sp3d_unproject_fwd[_indexed]: the root grid's cubes leave as their z-spectrum (Jp = 16 or 32)
 HM_ONE_ZSPECTRUM = 0x4000   # sp3d_unproject_fwd[_indexed]: one channel read in place, its cubes leave as their z-spectrum (J = 1)
 HM_BF16_IN = 0x8000         # next to OUT_ZSPECTRUM, HM_ONE_CHANNEL or HM_ONE_ZSPECTRUM: the heat-maps are bf16, every result fp32
+HM_BF16_TRAIN = 0x10000     # sp3d_unproject_fwd_train / sp3d_unproject_one_fwd_train: the heat-maps are bf16; fp32 results, the same pass mask
 SCATTER_AUTO, SCATTER_PER_TAP, SCATTER_MERGE = 0, 2, 3     # include/sp3d.h: per-call scatter choice of unproject_bwd_packed
 SCATTER_WIDE = 0x100        # OR-ed into that choice: 17..32 joints, 32-element pixels, the two-plane mask
 CONV3_WINO_YZ = 0x100       # OR-ed into the mode of sp3d_wino_fused_split64 / the CS of its _skip form: Winograd in y,z, direct in x
@@ -297,7 +298,9 @@ def unproject_fwd(views: Sequence[torch.Tensor], layout: int, jp: int, cam: torc
     of a channels-last (B,h,w,jp) buffer (``LAYOUT_NHWC``, ``jp`` = its pixel stride) - read in place; ``J`` = channels
     written, 1 or 4 (value + three zero channels; channels-last results: 4).
     ``wide_mask`` (SP3D_HM_WIDE_MASK, with ``pass_mask`` at ``jp`` = 32 only): ``pass_mask`` is a contiguous (2, B, X*Y*Z)
-    int16 tensor, plane 0 for channels 0-15 and plane 1 for channels 16..J-1."""
+    int16 tensor, plane 0 for channels 0-15 and plane 1 for channels 16..J-1.
+    bf16 ``views`` with a ``pass_mask`` (SP3D_HM_BF16_TRAIN, derived from the dtype; ``out_dtype`` stays fp32): bf16 pixels of
+    ``jp`` = 16, or 32 with ``wide_mask``; cubes, grids and mask words are those of the call on the widened views."""
     lib = load()
     dev = cam.device
     _require_cam(cam)
@@ -325,8 +328,11 @@ def unproject_fwd(views: Sequence[torch.Tensor], layout: int, jp: int, cam: torc
         cubes = _empty_cl3d(B, J, X, Y, Z, dev, out_dtype)
     else:
         cubes = torch.empty((B, J, X, Y, Z), dtype=out_dtype, device=dev)
-    flags = (OUT_CHANNELS_LAST if channels_last else 0) | (HM_BF16 if views[0].dtype == torch.bfloat16 and not one_channel else 0) | \
-        (OUT_BF16 if out_dtype == torch.bfloat16 else 0) | one
+    bf16_in = views[0].dtype == torch.bfloat16 and not one_channel
+    if pass_mask is not None and not all(v.dtype == views[0].dtype for v in views):
+        raise Sp3dError("unproject_fwd(pass_mask=...): bf16 views or fp32 views expected, not a mixture")
+    flags = (OUT_CHANNELS_LAST if channels_last else 0) | (OUT_BF16 if out_dtype == torch.bfloat16 else 0) | one | \
+        ((HM_BF16 if pass_mask is None else HM_BF16_TRAIN) if bf16_in else 0)
     grids = torch.empty((B, X * Y * Z, 3), dtype=torch.float32, device=dev) if want_grids else None
     gs = _f3(grid_size)
     if wide_mask:
@@ -747,9 +753,11 @@ def channel_shift_act_(y: torch.Tensor, shift: torch.Tensor, mode: int, residual
 def unproject_bwd_packed(cam, centers, valid, grad_cubes: torch.Tensor, pass_mask: torch.Tensor, batch: int,
                          num_views: int, J: int, jp: int, h: int, w: int, cube_size, grid_size, img_size,
                          sample_of: Optional[torch.Tensor] = None, deterministic: bool = False, return_packed: bool = False,
-                         scatter: int = SCATTER_AUTO, wide: bool = False):
+                         scatter: int = SCATTER_AUTO, wide: bool = False, out_dtype: torch.dtype = torch.float32):
     """line-coalesced scatter: -> list[V] of (B,J,h,w) gradient views into one (V,B,h,w,jp) channels-last buffer
     (``return_packed``: that buffer itself, pad channels zero).
+    ``out_dtype`` = torch.bfloat16: the fp32 buffer (the atomics' sums, or the converted fixed-point sums) is rounded ONCE as a
+    whole, by one dense pass, and the views returned are views of that bf16 buffer.
     ``deterministic``: accumulate in 64-bit fixed point (integer atomics): bit-identical run to run.
     ``scatter``: SCATTER_AUTO (by voxel pitch) / SCATTER_PER_TAP / SCATTER_MERGE - a per-call choice (include/sp3d.h).
     ``wide`` (SP3D_SCATTER_WIDE): 17..32 joints; ``jp`` must be 32, ``pass_mask`` the (2, P, X*Y*Z) mask of
@@ -784,6 +792,8 @@ def unproject_bwd_packed(cam, centers, valid, grad_cubes: torch.Tensor, pass_mas
                                            J, jp, h, w, X, Y, Z, _f3(grid_size), int(img_size[0]), int(img_size[1]),
                                            int(scatter), _stream(dev))
         check(rc, "sp3d_unproject_bwd_packed")
+    if out_dtype != torch.float32:
+        packed = packed.to(out_dtype)
     return packed if return_packed else [packed[c].permute(0, 3, 1, 2)[:, :J] for c in range(num_views)]
 
 
@@ -793,18 +803,19 @@ def unproject_one_fwd_train(views: Sequence[torch.Tensor], layout: int, jp: int,
                             sample_of: Optional[torch.Tensor] = None):
     """one-channel training forward (sp3d_unproject_one_fwd_train): ``views``, ``layout`` and ``jp`` as ``unproject_fwd`` takes
     them with ``one_channel=True``; ``J`` = channels written, 1 or 4 (channels-last: 4).  Also fills ``pass_mask`` ((B, X*Y*Z)
-    int16, bit 0) for ``unproject_one_bwd``.  -> (cubes, grids | None)"""
+    int16, bit 0) for ``unproject_one_bwd``.  bf16 views (all of them: SP3D_HM_BF16_TRAIN, derived from the dtype) are read in
+    place with 2-byte taps, ``jp`` counting bf16 elements; the results stay fp32.  -> (cubes, grids | None)"""
     lib = load()
     dev = cam.device
     _require_cam(cam)
     X, Y, Z = (int(c) for c in cube_size)
-    if not all(v.dtype == torch.float32 and v.is_cuda for v in views):
-        raise Sp3dError("unproject_one_fwd_train: fp32 heat-map views on the GPU expected")
+    if views[0].dtype not in (torch.float32, torch.bfloat16) or not all(v.dtype == views[0].dtype and v.is_cuda for v in views):
+        raise Sp3dError("unproject_one_fwd_train: fp32 heat-map views or bf16 heat-map views (not a mixture) on the GPU expected")
     if pass_mask.dtype != torch.int16 or not pass_mask.is_contiguous() or pass_mask.numel() != B * X * Y * Z:
         raise Sp3dError("unproject_one_fwd_train: pass_mask must be a contiguous int16 (B, X*Y*Z) tensor")
     cubes = _empty_cl3d(B, J, X, Y, Z, dev) if channels_last else torch.empty((B, J, X, Y, Z), dtype=torch.float32, device=dev)
     grids = torch.empty((B, X * Y * Z, 3), dtype=torch.float32, device=dev) if want_grids else None
-    flags = HM_ONE_CHANNEL | (OUT_CHANNELS_LAST if channels_last else 0)
+    flags = HM_ONE_CHANNEL | (OUT_CHANNELS_LAST if channels_last else 0) | (HM_BF16_TRAIN if views[0].dtype == torch.bfloat16 else 0)
     rc = lib.sp3d_unproject_one_fwd_train(_ptr_array(views), layout | flags, jp, cam.data_ptr(), _opt(sample_of),
                                           centers.data_ptr(), valid.data_ptr(), cubes.data_ptr(), _opt(grids),
                                           pass_mask.data_ptr(), B, len(views), J, h, w, X, Y, Z, _f3(grid_size),
@@ -821,6 +832,28 @@ def unproject_one_bwd(cam, centers, valid, grad_cubes: torch.Tensor, pass_mask: 
     else (channels-last, another dtype, a view) is reduced to channel 0 first.
     ``deterministic``: 64-bit fixed point with integer atomics, scale = 2^(40 - ceil(log2 max|g|)) of that channel, as
     ``unproject_bwd_packed`` builds it: bit-identical run to run, and to channel 0 of the packed deterministic scatter."""
+    out = _unproject_one_bwd_dense(cam, centers, valid, grad_cubes, pass_mask, batch, num_views, h, w, cube_size, grid_size, img_size,
+                                   sample_of, deterministic)
+    return [out[c].unsqueeze(1) for c in range(num_views)]
+
+
+def unproject_one_bwd_rounded(cam, centers, valid, grad_cubes: torch.Tensor, pass_mask: torch.Tensor, batch: int, num_views: int,
+                              h: int, w: int, cube_size, grid_size, img_size, sample_of: Optional[torch.Tensor] = None,
+                              deterministic: bool = False, out_dtype: torch.dtype = torch.bfloat16):
+    """``unproject_one_bwd`` with a gradient of ``out_dtype``: the dense fp32 (V,B,h,w) buffer (the atomics' sums, or the
+    converted fixed-point sums) is rounded ONCE as a whole, by one dense pass, and the (B,1,h,w) views returned are views of the
+    rounded buffer - what a bf16 heat-map wants, with nothing left for the autograd engine to cast.  (A function of its own:
+    the parameter list of ``unproject_one_bwd`` is pinned.)"""
+    out = _unproject_one_bwd_dense(cam, centers, valid, grad_cubes, pass_mask, batch, num_views, h, w, cube_size, grid_size, img_size,
+                                   sample_of, deterministic)
+    if out_dtype != torch.float32:
+        out = out.to(out_dtype)
+    return [out[c].unsqueeze(1) for c in range(num_views)]
+
+
+def _unproject_one_bwd_dense(cam, centers, valid, grad_cubes, pass_mask, batch, num_views, h, w, cube_size, grid_size, img_size,
+                             sample_of, deterministic) -> torch.Tensor:
+    """the scatter of ``unproject_one_bwd`` -> its dense fp32 (V,B,h,w) buffer"""
     lib = load()
     dev = cam.device
     _require_cam(cam)
@@ -850,7 +883,7 @@ def unproject_one_bwd(cam, centers, valid, grad_cubes: torch.Tensor, pass_mask: 
                                         stride, pass_mask.data_ptr(), out.data_ptr(), int(batch), P, num_views, h, w, X, Y, Z,
                                         _f3(grid_size), int(img_size[0]), int(img_size[1]), _stream(dev))
         check(rc, "sp3d_unproject_one_bwd")
-    return [out[c].unsqueeze(1) for c in range(num_views)]
+    return out
 
 
 def gaussian_target_3d(roots: torch.Tensor, gx: torch.Tensor, gy: torch.Tensor, gz: torch.Tensor, sigma: float):

@@ -38,7 +38,8 @@ int sp3d_unproject_fwd_variant(const float *const *hm_views, int Jp, const float
  *                hm_layout is planned for _INDEXED and refused for the other entries, as the entry points refuse it; _ZDFT
  *                refuses Jp != 16 as sp3d_unproject_fwd_zdft does.  SP3D_HM_ONE_ZSPECTRUM likewise: planned for _INDEXED (one
  *                launch of unproject_one_zd_kernel, P * (X/4) * (Y/4) workgroups of 320 threads, 1280 bytes of LDS), refused
- *                for every other entry
+ *                for every other entry.  SP3D_HM_BF16_TRAIN (bf16 maps into the training forwards) is planned for _TRAIN and
+ *                _ONE_TRAIN - the bf16-tap kernels with the geometry of the fp32 plan - and refused for every other entry
  *   names        SP3D_PLAN_NAME bytes per launch: the kernel with its template arguments, as a kernel trace prints it
  *                without namespaces and parameter list
  *   fields       SP3D_PLAN_FIELDS int32 per launch: workgroups, workgroup size, dynamic LDS bytes, number of kernel

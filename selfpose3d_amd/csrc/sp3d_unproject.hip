@@ -89,6 +89,7 @@ struct FwdRequest {
     bool wide_mask;      // SP3D_HM_WIDE_MASK: the pass mask has two planes of P * N words, one per channel group of Jp = 32
     bool one_zd;         // SP3D_HM_ONE_ZSPECTRUM: the one-channel read with the z-spectrum result
     bool hm16;           // SP3D_HM_BF16_IN: bf16 maps into an fp32 result, next to exactly one of zd, one, one_zd
+    bool hm16_train;     // SP3D_HM_BF16_TRAIN: bf16 maps into the fp32 results and the pass mask of the two training forwards
     Geom g;
 };
 
@@ -132,6 +133,7 @@ static int default_xcd_order(const Geom &g) { return g.B <= 2 ? 1 : 0; }
 static int resolve_group(const FwdRequest &rq, const FwdTuning &t, const Geom &g, int jp, int ps, Launch &L)
 {
     const int wlds = jp * WOSTR > WREC ? jp * WOSTR : WREC;      // per-wave LDS floats of the pipe and brick kernels
+    const int io = rq.io | ((rq.hm16 || rq.hm16_train) ? 1 : 0);  // bf16 taps: the storage flag, or either mixed flag (fp32 results)
     L.g = g;
     if (t.brick) {   // 4x4x4 voxels per wave, a z-stack of `zw` bricks per workgroup
         const int nbx = (g.X + BR - 1) / BR, nby = (g.Y + BR - 1) / BR, nwz = (g.Z + BR - 1) / BR;
@@ -153,14 +155,14 @@ static int resolve_group(const FwdRequest &rq, const FwdTuning &t, const Geom &g
             return SP3D_EUNSUPPORTED;
         set_launch(L, block_grid ? block_grid : xcd_grid_blocks(g.B, wgs, L.g.xcd_chunk), 64 * zw,
                    (size_t)zw * wlds * sizeof(float) + (size_t)t.ballast * 20480, 4, wgs, nby, nzc, zw);
-        return find_brick_kernel(KernelKey{jp, ps, rq.zd, 0, rq.out_cl, rq.io | (rq.hm16 ? 1 : 0)}, L.fn, L.name);
+        return find_brick_kernel(KernelKey{jp, ps, rq.zd, 0, rq.out_cl, io}, L.fn, L.name);
     }
     if (t.pipe) {    // 64 consecutive voxels per wave
         const int nw = t.one_wave ? 1 : 4;
         const int ptiles = (g.N + 64 * nw - 1) / (64 * nw), ptotal = ptiles * g.B;
         set_xcd_fields(L.g, ptiles);
         set_launch(L, t.no_xcd_map ? ptotal : xcd_grid_blocks(g.B, ptiles, g.xcd_chunk), 64 * nw, 0, 2, ptiles, ptotal);
-        return find_pipe_kernel(KernelKey{jp, ps, !t.no_xcd_map, nw, rq.out_cl, rq.io}, L.fn, L.name);
+        return find_pipe_kernel(KernelKey{jp, ps, !t.no_xcd_map, nw, rq.out_cl, io}, L.fn, L.name);
     }
     const int tiles = (g.N + TILE - 1) / TILE, total = tiles * g.B;
     set_launch(L, t.no_xcd_map ? total : xcd_grid_blocks(g.B, tiles, g.xcd_chunk), TILE,
@@ -180,7 +182,7 @@ static int resolve_one(const FwdRequest &rq, Launch &L)
     if (rq.out_cl && !rq.out_aligned) return SP3D_EUNSUPPORTED;
     const int64_t px = rq.layout == SP3D_LAYOUT_NHWC ? rq.Jp : 1, row = (int64_t)g.w * px;
     // 24-bit multiplies form the tap offset, a 32-bit byte offset addresses it (bf16 maps: 2-byte elements)
-    if (row >= (1 << 24) || (int64_t)g.h * row * (rq.hm16 ? 2 : 4) > (int64_t)0x7fffffff) return SP3D_EUNSUPPORTED;
+    if (row >= (1 << 24) || (int64_t)g.h * row * ((rq.hm16 || rq.hm16_train) ? 2 : 4) > (int64_t)0x7fffffff) return SP3D_EUNSUPPORTED;
     const int ptiles = (g.N + 63) / 64;
     g.xcd_order = default_xcd_order(g);
     g.xcd_chunk = default_xcd_chunk(g, ptiles);
@@ -188,7 +190,7 @@ static int resolve_one(const FwdRequest &rq, Launch &L)
     const int64_t sample = rq.layout == SP3D_LAYOUT_NHWC ? (int64_t)g.h * row : (int64_t)rq.Jp * g.h * g.w;
     set_launch(L, xcd_grid_blocks(g.B, ptiles, g.xcd_chunk), 64, 0, 3, sample, (int)row, (int)px);
     const int vt = g.V <= 6 ? g.V : (g.V <= 8 ? 8 : (g.V <= 10 ? 10 : (g.V <= 12 ? 12 : 16)));
-    return find_one_kernel(KernelKey{1, 1, vt, vt > 8 ? 8 : 4, rq.out_cl, g.pass_mask ? 4 : (rq.hm16 ? 1 : 0)}, L.fn, L.name);
+    return find_one_kernel(KernelKey{1, 1, vt, vt > 8 ? 8 : 4, rq.out_cl, g.pass_mask ? (rq.hm16_train ? 5 : 4) : (rq.hm16 ? 1 : 0)}, L.fn, L.name);
 }
 
 // SP3D_HM_ONE_ZSPECTRUM (include/sp3d.h): the one-channel read with the z-spectrum result of the brick ZD form at J = 1,
@@ -236,6 +238,15 @@ static int resolve_fwd(const FwdRequest &rq, FwdTuning t, Launch (&plan)[SP3D_PL
     Launch &L = plan[0];
     L = Launch{};
     L.g = rq.g; L.grid_y = 1; L.grids = !rq.zd;      // a z-spectrum launch writes no grids (its entries take none)
+    // bf16 maps into a training forward (SP3D_HM_BF16_TRAIN): a form of the two entries that write a pass mask and of nothing
+    // else - not of the bf16 storage pair, of the inference flag or of either spectrum; packed pixels of 16 elements, or of 32
+    // with the two-plane mask, on the kernels that clamp a 2x2 block; the one-channel read has resolve_one's limits
+    if (rq.hm16_train) {
+        if (!rq.g.pass_mask || rq.io || rq.hm16 || rq.zd || rq.one_zd) return SP3D_EUNSUPPORTED;
+        if (!rq.one && (rq.layout == SP3D_LAYOUT_PLANAR || (rq.layout == SP3D_LAYOUT_NHWC && rq.Jp != (rq.wide_mask ? WIDE_PS : 16)) ||
+                        rq.g.w < 2 || rq.g.h < 2 || (int64_t)rq.g.h * rq.g.w > (1 << 24)))
+            return SP3D_EUNSUPPORTED;
+    }
     if (rq.one_zd) return resolve_one_zd(rq, L);
     // bf16 maps into an fp32 result (SP3D_HM_BF16_IN): a form of the z-spectrum result and of the one-channel read, of nothing
     // else - not of the bf16 storage pair, not of the two-plane mask, channels-last only from the one-channel kernel
@@ -268,7 +279,7 @@ static int resolve_fwd(const FwdRequest &rq, FwdTuning t, Launch (&plan)[SP3D_PL
     }
     if (tile_only) t.pipe = t.brick = 0;
     if (t.brick) t.pipe = 1;
-    if (rq.io) t.one_wave = 1;                 // bf16 storage: one wave per workgroup only
+    if (rq.io || rq.hm16_train) t.one_wave = 1;    // bf16 taps: one wave per workgroup only
     if (rq.Jp == WIDE_PS) {
         if (g.J > WIDE_PS || rq.out_cl || (g.pass_mask && !rq.wide_mask) || tile_only) return SP3D_EUNSUPPORTED;
         if (memcmp(&asked, &pipe, sizeof(t)) && memcmp(&asked, &stacks, sizeof(t))) return SP3D_EUNSUPPORTED;
@@ -280,11 +291,11 @@ static int resolve_fwd(const FwdRequest &rq, FwdTuning t, Launch (&plan)[SP3D_PL
         L1 = L;
         gg.J = g.J - 16;
         if (g.pass_mask) gg.pass_mask = g.pass_mask + (size_t)g.B * g.N;
-        L1.view_off = 16 * (((rq.io & 1) || rq.hm16) ? 2 : 4);
+        L1.view_off = 16 * (((rq.io & 1) || rq.hm16 || rq.hm16_train) ? 2 : 4);
         L1.out_off = rq.zd ? (size_t)16 * (ZDSZ / 2 + 1) * (g.X / BR) * (g.Y / BR) * 16 * 8
                            : (size_t)16 * g.sJ * ((rq.io & 2) ? 2 : 4);
         L1.grids = false;
-        return resolve_group(rq, t, gg, (rq.io || rq.hm16) ? 16 : (gg.J + 3) / 4 * 4, WIDE_PS, L1);
+        return resolve_group(rq, t, gg, (rq.io || rq.hm16 || rq.hm16_train) ? 16 : (gg.J + 3) / 4 * 4, WIDE_PS, L1);
     }
     if (rq.Jp < g.J || (rq.Jp & 3) || rq.Jp > 16) return SP3D_EUNSUPPORTED;
     if (rq.out_cl && (g.J & 3)) return SP3D_EUNSUPPORTED;        // channels-last rows must be 16-B multiples
@@ -326,6 +337,7 @@ static int fwd_request(FwdRequest &rq, int hm_layout, int Jp, bool ptrs, int B, 
     rq.zd = (hm_layout & SP3D_OUT_ZSPECTRUM) != 0;
     rq.one_zd = (hm_layout & SP3D_HM_ONE_ZSPECTRUM) != 0;
     rq.hm16 = (hm_layout & SP3D_HM_BF16_IN) != 0;
+    rq.hm16_train = (hm_layout & SP3D_HM_BF16_TRAIN) != 0;
     rq.out_aligned = true; rq.one_train = false;
     return SP3D_OK;
 }
@@ -496,6 +508,7 @@ extern "C" int sp3d_unproject_fwd_plan(int entry, int hm_layout, int Jp, const i
     if (!names || !fields || !tuning || !records) return SP3D_ENULL;
     if (entry < SP3D_PLAN_INDEXED || entry > SP3D_PLAN_ONE_TRAIN) return SP3D_EINVAL;
     const float grid_size[3] = {1.0f, 1.0f, 1.0f};
+    const bool hm16_train = (hm_layout & SP3D_HM_BF16_TRAIN) != 0;       // as asked: two entries below rewrite the word
     if (entry == SP3D_PLAN_ZDFT) hm_layout = SP3D_LAYOUT_NHWC | (hm_layout & (SP3D_HM_WIDE_MASK | SP3D_HM_ONE_ZSPECTRUM | SP3D_HM_BF16_IN));     // the entry has no layout word; the flags are kept to be refused
     if (entry == SP3D_PLAN_TUNING) hm_layout = SP3D_LAYOUT_NHWC | ((variant & SP3D_TUNING_CHANNELS_LAST) ? SP3D_OUT_CHANNELS_LAST : 0);
     if (entry == SP3D_PLAN_ONE_TRAIN) hm_layout |= SP3D_HM_ONE_CHANNEL;
@@ -507,6 +520,7 @@ extern "C" int sp3d_unproject_fwd_plan(int entry, int hm_layout, int Jp, const i
     if ((rq.zd || rq.one_zd) && entry != SP3D_PLAN_INDEXED) return SP3D_EUNSUPPORTED;
     if (entry == SP3D_PLAN_ZDFT && (Jp != 16 || rq.hm16)) return SP3D_EUNSUPPORTED;
     if ((entry == SP3D_PLAN_TRAIN || entry == SP3D_PLAN_ONE_TRAIN) && rq.hm16) return SP3D_EUNSUPPORTED;     // as the two entries answer
+    if (hm16_train && entry != SP3D_PLAN_TRAIN && entry != SP3D_PLAN_ONE_TRAIN) return SP3D_EUNSUPPORTED;   // no pass mask, no such form
     rq.one_train = entry == SP3D_PLAN_ONE_TRAIN;
     if (entry == SP3D_PLAN_TRAIN || rq.one_train) rq.g.pass_mask = reinterpret_cast<uint16_t *>(records);    // "there is one": never dereferenced
     rq.zd = rq.zd || entry == SP3D_PLAN_ZDFT;
@@ -532,7 +546,8 @@ extern "C" int sp3d_unproject_fwd_plan(int entry, int hm_layout, int Jp, const i
 }
 
 // forward with the gradient pass mask (uint16 per voxel, bit j = channel j passes gradient) for
-// sp3d_unproject_bwd_packed.  NHWC fp32 input only (the pipelined kernel).
+// sp3d_unproject_bwd_packed.  NHWC input only (the pipelined kernels): fp32 pixels, or bf16 pixels with SP3D_HM_BF16_TRAIN
+// (resolve_fwd holds that flag's refusals).
 extern "C" int sp3d_unproject_fwd_train(const float *const *hm_views, int hm_layout, int Jp, const float *cam,
                                         const int32_t *sample_of, const float *centers, const uint8_t *valid,
                                         float *cubes, float *grids, uint16_t *pass_mask, int P, int V, int J, int h,
@@ -550,7 +565,7 @@ extern "C" int sp3d_unproject_fwd_train(const float *const *hm_views, int hm_lay
 }
 
 // One-channel training forward: sp3d_unproject_fwd_indexed with SP3D_HM_ONE_CHANNEL (implied) + the pass mask at J = 1, in
-// the words of sp3d_unproject_fwd_train.  The refusals are resolve_one's.
+// the words of sp3d_unproject_fwd_train.  The refusals are resolve_one's; SP3D_HM_BF16_TRAIN reads 2-byte taps.
 extern "C" int sp3d_unproject_one_fwd_train(const float *const *hm_views, int hm_layout, int Jp, const float *cam,
                                             const int32_t *sample_of, const float *centers, const uint8_t *valid,
                                             float *cubes, float *grids, uint16_t *pass_mask, int P, int V, int J, int h,

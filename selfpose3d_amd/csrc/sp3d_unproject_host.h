@@ -86,7 +86,7 @@ inline int load_views(Views &v, const float *const *hm_views, int V)
 struct KernelKey {
     int jp, ps;          // channels gathered; channels between pixels
     int a, b;            // tile: XCD map, unroll; pipe: XCD map, waves; brick: z-spectrum, 0; one-channel: views, chunk; else 0, 0
-    int cl, io;          // channels-last result; FwdRequest::io (one-channel: 4 = the kernel that also writes the pass mask, 8 = the z-spectrum form)
+    int cl, io;          // channels-last result; FwdRequest::io (one-channel: 4 = the kernel that also writes the pass mask, 5 = that kernel with bf16 taps, 8 = the z-spectrum form)
 };
 using PackFn = void (*)(Views, float *, int, int, int);
 using PlanarFn = void (*)(Views, const float *, const float *, const uint8_t *, float *, float *, Geom);

@@ -39,6 +39,8 @@ namespace sp3d {
 // flight and widened exactly (<< 16) where the interpolation consumes it: the same fp32 chain in the same order, so the
 // result has the bits of the TI = float kernel on the widened maps.  An odd channel of a bf16 (B,15,h,w) tensor or of a 16- or
 // 32-channel bf16 pixel is 2-byte aligned only and is read in place like any other.  TI = float is what it was.
+// MASK with TI = bf16_t (SP3D_HM_BF16_TRAIN on sp3d_unproject_one_fwd_train): both of the above in one instantiation - the
+// mask word comes from the same fuse_pre value, so the words are the fp32 MASK kernel's on the widened maps.
 template <typename TI> struct OneTap;
 template <> struct OneTap<float> {
     using raw = float;
@@ -391,10 +393,23 @@ static int find_one_h_kernel(const KernelKey &key, const void *&fn, const char *
     return SP3D_EUNSUPPORTED;
 }
 
+// bf16 maps into the training forward (SP3D_HM_BF16_TRAIN on sp3d_unproject_one_fwd_train): the MASK = true kernels with 2-byte
+// taps, planar and channels-last results; key.io = 5 (the pass mask's 4 + bf16 taps).  Behind the inference rows, as they are
+// behind the fp32 ones; planned by tests/test_bf16_train_host.py, run by tests/test_gpu_bf16_train.py.
+#define SP3D_ONE_H_TRAIN(VT_, CS_) SP3D_ROW(OneFn, (KernelKey{1, 1, VT_, CS_, false, 5}), unproject_one_kernel, VT_, CS_, false, true, bf16_t) \
+    SP3D_ROW(OneFn, (KernelKey{1, 1, VT_, CS_, true, 5}), unproject_one_kernel, VT_, CS_, true, true, bf16_t)
+static int find_one_h_train_kernel(const KernelKey &key, const void *&fn, const char *&name)
+{
+    SP3D_ONE_H_TRAIN(1, 4) SP3D_ONE_H_TRAIN(2, 4) SP3D_ONE_H_TRAIN(3, 4) SP3D_ONE_H_TRAIN(4, 4) SP3D_ONE_H_TRAIN(5, 4)
+    SP3D_ONE_H_TRAIN(6, 4) SP3D_ONE_H_TRAIN(8, 4) SP3D_ONE_H_TRAIN(10, 8) SP3D_ONE_H_TRAIN(12, 8) SP3D_ONE_H_TRAIN(16, 8)
+    return SP3D_EUNSUPPORTED;
+}
+
 int find_one_kernel(const KernelKey &key, const void *&fn, const char *&name)
 {
     SP3D_ONE(1, 4) SP3D_ONE(2, 4) SP3D_ONE(3, 4) SP3D_ONE(4, 4) SP3D_ONE(5, 4) SP3D_ONE(6, 4) SP3D_ONE(8, 4) SP3D_ONE(10, 8)
     SP3D_ONE(12, 8) SP3D_ONE(16, 8)
+    if (key.io == 5) return find_one_h_train_kernel(key, fn, name);
     return find_one_h_kernel(key, fn, name);
 }
 

@@ -110,6 +110,13 @@ class CuboidProposalNet(nn.Module):
         self.project_layer.bf16_maps = bool(on)
         return self
 
+    def use_bf16_training(self, on: bool = True):
+        """train through bf16 heat-maps: maps that are bf16 and carry a gradient are read as bf16 by the masked training
+        forwards, every result stays fp32 and the gradient leaves as bf16 (``ProjectLayer.bf16_train``); fp32 maps and
+        inference are untouched"""
+        self.project_layer.bf16_train = bool(on)
+        return self
+
     def forward(self, all_heatmaps, meta, flip_xcoords=None):
         if self.rootnet_roothm:                                   # root-joint channel only (:103-108)
             hms = [a[:, self.root_id:self.root_id + 1] for a in all_heatmaps]      # a view: read in place with ProjectLayer.one_channel, copied otherwise

@@ -68,6 +68,13 @@ class CuboidProposalNetSoft(nn.Module):
         self.project_layer.bf16_maps = bool(on)
         return self
 
+    def use_bf16_training(self, on: bool = True):
+        """train through bf16 heat-maps: maps that are bf16 and carry a gradient are read as bf16 by the masked training
+        forwards, every result stays fp32 and the gradient leaves as bf16 (``ProjectLayer.bf16_train``); fp32 maps and
+        inference are untouched"""
+        self.project_layer.bf16_train = bool(on)
+        return self
+
     # -- shared: heat-maps -> root cubes ---------------------------------------------------------------
     def _root_cubes(self, hms, meta, flip_xcoords, fronts=()):
         # of the fused z-spectrum fronts this net takes the one-channel one alone (get_grid_centres; the synthetic-root branch

@@ -55,6 +55,14 @@ class MultiPersonPoseNet(nn.Module):
             self.backbone.bf16_heatmaps = bool(on)
         return self
 
+    def use_bf16_training(self, on: bool = True):
+        """the root and pose nets train through heat-maps handed to them as bf16 with a gradient (``ProjectLayer.bf16_train``).
+        The backbone is not touched: ``PoseResNet.bf16_heatmaps`` stays an inference switch"""
+        if not self.train_only_2d:
+            self.root_net.use_bf16_training(on)
+            self.pose_net.use_bf16_training(on)
+        return self
+
     def heatmaps(self, views, input_heatmaps):
         if views is None:
             return input_heatmaps

@@ -88,6 +88,14 @@ class MultiPersonPoseNetSSV(nn.Module):
             net.bf16_heatmaps = bool(on)
         return self
 
+    def use_bf16_training(self, on: bool = True):
+        """the root and pose nets train through heat-maps handed to them as bf16 with a gradient (``ProjectLayer.bf16_train``).
+        The backbone is not touched: ``PoseResNet.bf16_heatmaps`` stays an inference switch"""
+        for name in ("root_net", "pose_net"):
+            if hasattr(self, name):
+                getattr(self, name).use_bf16_training(on)
+        return self
+
     def _heatmaps(self, views, input_heatmaps):
         if views is None:
             return input_heatmaps

@@ -50,6 +50,13 @@ class PoseRegressionNet(nn.Module):
         self.project_layer.bf16_maps = bool(on)
         return self
 
+    def use_bf16_training(self, on: bool = True):
+        """train through bf16 heat-maps: maps that are bf16 and carry a gradient are read as bf16 by the masked training
+        forwards, the person cubes stay fp32 and the gradient leaves as bf16 (``ProjectLayer.bf16_train``); fp32 maps and
+        inference are untouched"""
+        self.project_layer.bf16_train = bool(on)
+        return self
+
     @torch.no_grad()
     def forward_batched(self, all_heatmaps, meta, grid_centers, flip_xcoords=None, max_cubes_per_call: int = 8):
         """All person proposals of a batch at once (inference): grid_centers (B,K,5) -> pred (B,K,J,3).
@@ -138,7 +145,11 @@ class PoseRegressionNet(nn.Module):
             flags = grid_centers[:, :, 3].detach().cpu()
         pairs = [(b, n) for n in range(K) for b in range(B) if float(flags[b, n]) >= 0]       # slot-major
         P, ns = len(pairs), len(sets)
-        preds = [torch.zeros(B, K, J, 3, device=device, dtype=sets[0][0][0].dtype) for _ in sets]
+        # the cubes' type, known before they exist: the kernels write ``io_dtype`` whatever the maps' type (bf16 maps: fp32
+        # cubes), and a float64 caller gets float64 back (_UnprojectFn)
+        maps_dtype = sets[0][0][0].dtype
+        cube_dtype = maps_dtype if maps_dtype == torch.float64 else self.project_layer.io_dtype
+        preds = [torch.zeros(B, K, J, 3, device=device, dtype=cube_dtype) for _ in sets]
         if P == 0:
             return preds
         bi = torch.tensor([b for b, _ in pairs], device=device)
@@ -156,10 +167,11 @@ class PoseRegressionNet(nn.Module):
         planar = self.v2v_net.wants_planar_input() and sets[0][0][0].is_cuda
         cl = self.channels_last and not planar
         cubes, grids = [], []
-        fused_sa = sets[0][0][0].dtype == torch.float32 and next(self.v2v_net.parameters()).dtype == torch.float32   # HIP pair: fp32
+        fused_sa = cube_dtype == torch.float32 and next(self.v2v_net.parameters()).dtype == torch.float32   # HIP pair: fp32
         for heatmaps, meta, flip in sets:
             c, g = self.project_layer.get_voxel(heatmaps, meta, self.grid_size, centers, self.cube_size, flip_xcoords=flip,
                                                 want_grids=not fused_sa, pad_channels=not planar, channels_last=cl, sample_of=bi)
+            assert c.dtype == cube_dtype, (c.dtype, cube_dtype)
             cubes.append(c)
             grids.append(g)
         x = cubes[0] if ns == 1 else torch.cat(cubes, 0)

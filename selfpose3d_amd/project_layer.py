@@ -249,12 +249,15 @@ class _UnprojectFn(torch.autograd.Function):
         else:
             wide = tuple
         if route.backward == "one":
-            grads = _lib.unproject_one_bwd(cam, centers, valid, grad_cubes, ctx.mask, batch, nv, h, w, cube_size, grid_size,
-                                           layer.img_size, sample_of=ctx.sample_of, deterministic=layer.deterministic_backward)
+            one_args = (cam, centers, valid, grad_cubes, ctx.mask, batch, nv, h, w, cube_size, grid_size, layer.img_size)
+            one_kw = dict(sample_of=ctx.sample_of, deterministic=layer.deterministic_backward)
+            grads = _lib.unproject_one_bwd(*one_args, **one_kw) if route.elem == torch.float32 else \
+                _lib.unproject_one_bwd_rounded(*one_args, **one_kw, out_dtype=route.elem)
         elif route.backward in ("mask16", "mask2x16"):
             grads = _lib.unproject_bwd_packed(cam, centers, valid, grad_cubes, ctx.mask, batch, nv, J, route.jp, h, w, cube_size,
                                               grid_size, layer.img_size, sample_of=ctx.sample_of,
-                                              deterministic=layer.deterministic_backward, wide=route.backward == "mask2x16")
+                                              deterministic=layer.deterministic_backward, wide=route.backward == "mask2x16",
+                                              out_dtype=route.elem)
         else:
             grads = _lib.unproject_bwd(hms, cam, centers, valid, grad_cubes, cube_size, grid_size, layer.img_size,
                                        sample_of=ctx.sample_of)
@@ -310,6 +313,14 @@ class ProjectLayer(nn.Module):
         # a heat-map gradient ignores the switch, and a request no bf16 kernel covers widens the maps and takes the fp32 path.
         # Not to be combined with ``io_dtype`` (bf16 cubes), which keeps its meaning and its refusals.
         self.bf16_maps = _lib.env_switch("SP3D_BF16_MAPS", False)
+        # opt-in (SP3D_BF16_TRAIN=1 / ``bf16_train = True``; the model classes' ``use_bf16_training()``): bf16 heat-maps WITH a
+        # heat-map gradient are read as bf16 by the masked training forwards (SP3D_HM_BF16_TRAIN: fp32 cubes, the same pass
+        # mask) and the gradient leaves as bf16, rounded once - instead of widening every view, packing fp32 pixels and having
+        # autograd cast each fp32 gradient view back.  Acts only when every map is bf16, ``io_dtype`` is fp32 and the path is
+        # NHWC, for 13..16 joints, 17..32 with ``wide_grad`` and one channel with ``one_channel_grad``; anything else takes
+        # the route it took.  Same cubes and same deterministic gradient bits; off until tools/bench_bf16_train.py has
+        # recorded that it is faster in every leg
+        self.bf16_train = _lib.env_switch("SP3D_BF16_TRAIN", False)
 
     # -- the route: one pure decision (no device access; CPU tensors classify the same way) --------------
     def route(self, heatmaps, SZ=None, want_grids=True, pad_channels=False, channels_last=False, out=False) -> Route:
@@ -358,6 +369,14 @@ class ProjectLayer(nn.Module):
             widen = heatmaps[0].dtype == torch.bfloat16
             if widen and J == 1 and self.one_channel:
                 probe = [torch.empty_strided(tuple(x.shape), x.stride(), dtype=x.dtype, device="meta").float() for x in heatmaps]
+        if self.bf16_train and fp32 and grad_hm and all(x.dtype == torch.bfloat16 for x in heatmaps):
+            # bf16 pixels into the masked training forwards, the gradient out as bf16: no widened copy, no fp32 pack
+            one = one_channel_source(heatmaps, torch.bfloat16) if (J == 1 and self.one_channel_grad) else None
+            if one:
+                return Route("one", one[0], one[1], torch.bfloat16, "cubes", J_one, channels_last, backward="one", autograd=True)
+            if masked and jp in (16, 32):
+                return Route("packed", _lib.LAYOUT_NHWC, jp, torch.bfloat16, "cubes", jp if pad_channels else J, channels_last,
+                             backward="mask2x16" if jp == 32 else "mask16", autograd=True)
         if one_grad:
             return Route("one", one_grad[0], one_grad[1], torch.float32, "cubes", J_one, channels_last, backward="one", autograd=True)
         one = one_channel_source(probe) if (fp32 and J == 1 and self.one_channel and not grad_hm) else None
