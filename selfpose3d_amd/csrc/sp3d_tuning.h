@@ -29,17 +29,19 @@ int sp3d_unproject_fwd_variant(const float *const *hm_views, int Jp, const float
                                int X, int Y, int Z, const float *grid_size, int W_in, int H_in, int variant,
                                void *stream);
 /* The launches a forward-unprojection request resolves to, for a request given as shapes: launches nothing, makes no HIP
- * call, runs without a GPU.  The entry points go through the same resolve function; their own argument checks (null
- * pointers, each entry's refusals) are not repeated here.
+ * call, runs without a GPU.  The plan answers what the entry answers: the entries and this function decode their arguments
+ * with the same function (decode_fwd, sp3d_unproject.hip), which holds every refusal once; this function only has no
+ * pointers - it states what an entry reads from them: all there, the result 128-byte aligned, no grids, SZ = 28 - and copies
+ * the launches out instead of running them.
  *   entry        which entry point asks: _INDEXED (hm_layout with its flag bits as in include/sp3d.h), _STRIDED (the same,
- *                with out_strides, NULL = dense), _TRAIN (the same, with a pass mask), _ZDFT, _TUNING (NHWC fp32 and the
- *                word `variant`, bit 24 included; `variant` is read for this entry only), _ONE_TRAIN
- *                (sp3d_unproject_one_fwd_train: SP3D_HM_ONE_CHANNEL implied, with a pass mask).  SP3D_OUT_ZSPECTRUM in
- *                hm_layout is planned for _INDEXED and refused for the other entries, as the entry points refuse it; _ZDFT
- *                refuses Jp != 16 as sp3d_unproject_fwd_zdft does.  SP3D_HM_ONE_ZSPECTRUM likewise: planned for _INDEXED (one
- *                launch of unproject_one_zd_kernel, P * (X/4) * (Y/4) workgroups of 320 threads, 1280 bytes of LDS), refused
- *                for every other entry.  SP3D_HM_BF16_TRAIN (bf16 maps into the training forwards) is planned for _TRAIN and
- *                _ONE_TRAIN - the bf16-tap kernels with the geometry of the fp32 plan - and refused for every other entry
+ *                with out_strides, NULL = dense), _TRAIN (the same, with a pass mask), _ONE_TRAIN
+ *                (sp3d_unproject_one_fwd_train: SP3D_HM_ONE_CHANNEL implied, with a pass mask), and the two entries that
+ *                take no layout word: _ZDFT (sp3d_unproject_fwd_zdft) and _TUNING (sp3d_unproject_fwd_variant: NHWC fp32
+ *                and the word `variant`, bit 24 included; `variant` is read for this entry only).  For these two the layout
+ *                byte of hm_layout is not read and a word with flag bits is answered by one rule each (ENTRY_RULES,
+ *                sp3d_unproject.hip): _ZDFT refuses SP3D_HM_WIDE_MASK, SP3D_HM_ONE_ZSPECTRUM, SP3D_HM_BF16_IN and
+ *                SP3D_HM_BF16_TRAIN and ignores every other flag; _TUNING refuses SP3D_HM_BF16_TRAIN and ignores every other
+ *                flag.  With hm_layout = 0 they answer exactly what their entries answer
  *   names        SP3D_PLAN_NAME bytes per launch: the kernel with its template arguments, as a kernel trace prints it
  *                without namespaces and parameter list
  *   fields       SP3D_PLAN_FIELDS int32 per launch: workgroups, workgroup size, dynamic LDS bytes, number of kernel

@@ -22,7 +22,7 @@
 namespace sp3d {
 
 // ------------------------------------------------------------------------------------------
-// Forward unprojection, host side: request (fwd_request) -> resolve_fwd() -> launch records -> launch_fwd().
+// Forward unprojection, host side: an entry's arguments -> decode_fwd() -> FwdRequest -> resolve_fwd() -> launch records -> launch_fwd().
 // ------------------------------------------------------------------------------------------
 // The tuning word of sp3d_unproject_fwd_variant, decoded: one field per bit group documented in sp3d_tuning.h (the only
 // place the word's layout is written down).  All int, no padding: tunings compare with memcmp.
@@ -80,17 +80,28 @@ static FwdTuning default_tuning(const Geom &g, bool out_cl)
     return default_tuning(out_cl ? FWD_BRICK_EACH : (g.Z % 32 == 0 ? FWD_BRICK_STACKS : FWD_PIPE));
 }
 
-// what a forward entry point asks for; `g` carries J, the image, the grid, the result strides and the pass mask
+// What a forward entry asks for, in the terms the kernels are chosen by (decode_fwd below writes it, from an entry's arguments
+// or from the plan entry's).  `g` carries J, the image, the grid and the result strides; the entry adds sample_of and pass_mask.
+enum Read { READ_PLANAR, READ_PACKED, READ_ONE_PLANAR, READ_ONE_PACKED, READ_UNKNOWN };    // READ_ONE_*: SP3D_HM_ONE_CHANNEL / _ONE_ZSPECTRUM
+enum Result { RESULT_PLANAR, RESULT_CHANNELS_LAST, RESULT_ZSPECTRUM };                    // planar: dense or strided, Geom has the strides
+enum Mask { MASK_NONE, MASK_ONE_PLANE, MASK_TWO_PLANES };                                  // two: SP3D_HM_WIDE_MASK, a plane per channel group
 struct FwdRequest {
-    int layout, Jp;      // SP3D_LAYOUT_* without the flag bits; channels (pixel stride) of a packed pixel
-    int io;              // bit 0 = the heat-maps are bf16, bit 1 = the cubes are bf16
-    bool one, out_cl, zd, out_aligned;   // one-channel read; channels-last result; z-spectrum result; result 16-byte aligned
-    bool one_train;      // one-channel read that also writes the pass mask (sp3d_unproject_one_fwd_train)
-    bool wide_mask;      // SP3D_HM_WIDE_MASK: the pass mask has two planes of P * N words, one per channel group of Jp = 32
-    bool one_zd;         // SP3D_HM_ONE_ZSPECTRUM: the one-channel read with the z-spectrum result
-    bool hm16;           // SP3D_HM_BF16_IN: bf16 maps into an fp32 result, next to exactly one of zd, one, one_zd
-    bool hm16_train;     // SP3D_HM_BF16_TRAIN: bf16 maps into the fp32 results and the pass mask of the two training forwards
+    int entry;              // SP3D_PLAN_*: which entry asks
+    Read read; Result result; Mask mask;
+    int taps16, cubes16;    // element types of the kernels: 2-byte taps (SP3D_HM_BF16, _BF16_IN, _BF16_TRAIN), 2-byte result (SP3D_OUT_BF16)
+    int Jp;                 // packed: elements of a pixel; one channel: pixel stride (packed) or channel count (planar)
     Geom g;
+};
+static bool one_channel(const FwdRequest &rq) { return rq.read == READ_ONE_PLANAR || rq.read == READ_ONE_PACKED; }
+// the pipelined kernels clamp a 2x2 block (needs a 2x2 image) and form pixel indices with 24-bit multiplies
+static bool has_2x2(const Geom &g) { return g.w >= 2 && g.h >= 2; }
+static bool pipelined_image(const Geom &g) { return has_2x2(g) && (int64_t)g.h * g.w <= (1 << 24); }
+
+// What an entry knows from its pointers and the plan entry can only state (all there, aligned, no grids, SZ as built)
+struct CallFacts {
+    bool ptrs, views, grids;    // every required pointer but the views is there; hm_views and its V entries are there; `grids` was given
+    unsigned misaligned;        // the result address modulo 128
+    int SZ;                     // sp3d_unproject_fwd_zdft only: the length of the z transform asked for
 };
 
 // one kernel launch.  scalar[0..nscalars): the kernel arguments after Geom, each in a 64-bit slot - an `int` parameter
@@ -129,11 +140,11 @@ static int default_xcd_chunk(const Geom &g, int tiles)
 static int default_xcd_order(const Geom &g) { return g.B <= 2 ? 1 : 0; }
 
 // One NHWC launch of `jp` channels read at a pixel stride of `ps`: brick, pipe or tile kernel, its grid and its Geom.
-// `t` is final here (resolve_fwd applied the downgrades).
+// `t` is final here (resolve_fwd applied the downgrades).  A missing table row is the refusal.
 static int resolve_group(const FwdRequest &rq, const FwdTuning &t, const Geom &g, int jp, int ps, Launch &L)
 {
     const int wlds = jp * WOSTR > WREC ? jp * WOSTR : WREC;      // per-wave LDS floats of the pipe and brick kernels
-    const int io = rq.io | ((rq.hm16 || rq.hm16_train) ? 1 : 0);  // bf16 taps: the storage flag, or either mixed flag (fp32 results)
+    const int cl = rq.result == RESULT_CHANNELS_LAST;
     L.g = g;
     if (t.brick) {   // 4x4x4 voxels per wave, a z-stack of `zw` bricks per workgroup
         const int nbx = (g.X + BR - 1) / BR, nby = (g.Y + BR - 1) / BR, nwz = (g.Z + BR - 1) / BR;
@@ -151,156 +162,114 @@ static int resolve_group(const FwdRequest &rq, const FwdTuning &t, const Geom &g
         // view-synchronous workgroups only when every wave of every workgroup lies inside the volume, so that all of them
         // reach the per-view barrier
         if (t.view_sync && nwz % zw == 0 && nzc * zw == nwz) L.g.xcd_order |= 4;
-        if (rq.zd && (rq.io || rq.out_cl || g.Z != ZDZ || nzc != 1 || zw != ZDZ / BR || (g.X % BR) || (g.Y % BR) || g.pass_mask))
-            return SP3D_EUNSUPPORTED;
         set_launch(L, block_grid ? block_grid : xcd_grid_blocks(g.B, wgs, L.g.xcd_chunk), 64 * zw,
                    (size_t)zw * wlds * sizeof(float) + (size_t)t.ballast * 20480, 4, wgs, nby, nzc, zw);
-        return find_brick_kernel(KernelKey{jp, ps, rq.zd, 0, rq.out_cl, io}, L.fn, L.name);
+        return find_brick_kernel(KernelKey{.jp = jp, .ps = ps, .cl = cl, .taps16 = rq.taps16, .cubes16 = rq.cubes16, .zd = rq.result == RESULT_ZSPECTRUM}, L.fn, L.name);
     }
     if (t.pipe) {    // 64 consecutive voxels per wave
         const int nw = t.one_wave ? 1 : 4;
         const int ptiles = (g.N + 64 * nw - 1) / (64 * nw), ptotal = ptiles * g.B;
         set_xcd_fields(L.g, ptiles);
         set_launch(L, t.no_xcd_map ? ptotal : xcd_grid_blocks(g.B, ptiles, g.xcd_chunk), 64 * nw, 0, 2, ptiles, ptotal);
-        return find_pipe_kernel(KernelKey{jp, ps, !t.no_xcd_map, nw, rq.out_cl, io}, L.fn, L.name);
+        return find_pipe_kernel(KernelKey{.jp = jp, .ps = ps, .cl = cl, .taps16 = rq.taps16, .cubes16 = rq.cubes16, .xcd = !t.no_xcd_map, .waves = nw}, L.fn, L.name);
     }
     const int tiles = (g.N + TILE - 1) / TILE, total = tiles * g.B;
     set_launch(L, t.no_xcd_map ? total : xcd_grid_blocks(g.B, tiles, g.xcd_chunk), TILE,
                (size_t)(jp * OSTR + 2 * g.V * TILE + TILE) * sizeof(float), 2, tiles, total);
-    return find_tile_kernel(KernelKey{jp, ps, !t.no_xcd_map, t.unroll, rq.out_cl, rq.io}, L.fn, L.name);
+    return find_tile_kernel(KernelKey{.jp = jp, .ps = ps, .cl = cl, .taps16 = rq.taps16, .cubes16 = rq.cubes16, .xcd = !t.no_xcd_map, .unroll = t.unroll}, L.fn, L.name);
 }
 
-// SP3D_HM_ONE_CHANNEL (include/sp3d.h): g.J = channels written (1, or 4 = value + three zero channels), g.sB.. = planar
-// result strides (dense or strided).  The pipe kernel's tile map: 64-voxel tiles dealt to a sample's XCDs in chunks.
-static int resolve_one(const FwdRequest &rq, Launch &L)
+// The one-channel reads (SP3D_HM_ONE_CHANNEL, SP3D_HM_ONE_ZSPECTRUM; include/sp3d.h).  Their kernels take the sample stride, the
+// row stride and the pixel stride of the tensor the channel lies in, and exist per view-slot count, gathered in chunks.
+static int64_t one_px(const FwdRequest &rq) { return rq.read == READ_ONE_PACKED ? rq.Jp : 1; }
+static void set_one_launch(const FwdRequest &rq, Launch &L, unsigned grid, unsigned block, size_t lds)
 {
-    Geom &g = L.g;
-    if ((rq.layout != SP3D_LAYOUT_PLANAR && rq.layout != SP3D_LAYOUT_NHWC) || rq.Jp < 1) return SP3D_EINVAL;
-    if (rq.io || (g.pass_mask && !rq.one_train) || (rq.hm16 && rq.one_train)) return SP3D_EUNSUPPORTED;
-    if (!(g.J == 4 || (g.J == 1 && !rq.out_cl))) return SP3D_EUNSUPPORTED;
-    if (g.w < 2 || g.h < 2 || (int64_t)g.h * g.w > (1 << 24)) return SP3D_EUNSUPPORTED;
-    if (rq.out_cl && !rq.out_aligned) return SP3D_EUNSUPPORTED;
-    const int64_t px = rq.layout == SP3D_LAYOUT_NHWC ? rq.Jp : 1, row = (int64_t)g.w * px;
-    // 24-bit multiplies form the tap offset, a 32-bit byte offset addresses it (bf16 maps: 2-byte elements)
-    if (row >= (1 << 24) || (int64_t)g.h * row * ((rq.hm16 || rq.hm16_train) ? 2 : 4) > (int64_t)0x7fffffff) return SP3D_EUNSUPPORTED;
-    const int ptiles = (g.N + 63) / 64;
-    g.xcd_order = default_xcd_order(g);
-    g.xcd_chunk = default_xcd_chunk(g, ptiles);
-    set_xcd_fields(g, ptiles);
-    const int64_t sample = rq.layout == SP3D_LAYOUT_NHWC ? (int64_t)g.h * row : (int64_t)rq.Jp * g.h * g.w;
-    set_launch(L, xcd_grid_blocks(g.B, ptiles, g.xcd_chunk), 64, 0, 3, sample, (int)row, (int)px);
-    const int vt = g.V <= 6 ? g.V : (g.V <= 8 ? 8 : (g.V <= 10 ? 10 : (g.V <= 12 ? 12 : 16)));
-    return find_one_kernel(KernelKey{1, 1, vt, vt > 8 ? 8 : 4, rq.out_cl, g.pass_mask ? (rq.hm16_train ? 5 : 4) : (rq.hm16 ? 1 : 0)}, L.fn, L.name);
+    const Geom &g = L.g;
+    const int64_t row = g.w * one_px(rq);
+    set_launch(L, grid, block, lds, 3, rq.read == READ_ONE_PACKED ? g.h * row : (int64_t)rq.Jp * g.h * g.w, (int)row, (int)one_px(rq));
 }
-
-// SP3D_HM_ONE_ZSPECTRUM (include/sp3d.h): the one-channel read with the z-spectrum result of the brick ZD form at J = 1,
-// unproject_one_zd_kernel.  One workgroup of ZDZ / BR waves per 4 x 4 tile of z columns, exactly P * tiles of them (the kernel
-// deals them to the XCDs itself), a slab of 16 x ZDZ floats of LDS.  Nothing may stand next to the flag.
-static int resolve_one_zd(const FwdRequest &rq, Launch &L)
+static KernelKey one_slots_key(const FwdRequest &rq)
 {
-    Geom &g = L.g;
-    if ((rq.layout != SP3D_LAYOUT_PLANAR && rq.layout != SP3D_LAYOUT_NHWC) || rq.Jp < 1) return SP3D_EINVAL;
-    if (rq.io || rq.one || rq.out_cl || rq.wide_mask || rq.zd || rq.one_train || g.pass_mask) return SP3D_EUNSUPPORTED;
-    if (g.J != 1 || g.Z != ZDZ || (g.X % BR) || (g.Y % BR) || !g.dense) return SP3D_EUNSUPPORTED;
-    if (g.w < 2 || g.h < 2 || (int64_t)g.h * g.w > (1 << 24)) return SP3D_EUNSUPPORTED;
-    const int64_t px = rq.layout == SP3D_LAYOUT_NHWC ? rq.Jp : 1, row = (int64_t)g.w * px;
-    // 24-bit multiplies form the tap offset, a 32-bit byte offset addresses it (bf16 maps: 2-byte elements)
-    if (row >= (1 << 24) || (int64_t)g.h * row * (rq.hm16 ? 2 : 4) > (int64_t)0x7fffffff) return SP3D_EUNSUPPORTED;
-    const int nby = g.Y / BR, tiles = (g.X / BR) * nby;
-    set_xcd_fields(g, tiles);
-    set_brick_fields(g, tiles, nby);
-    const int64_t sample = rq.layout == SP3D_LAYOUT_NHWC ? (int64_t)g.h * row : (int64_t)rq.Jp * g.h * g.w;
-    set_launch(L, (unsigned)(g.B * tiles), 64 * (ZDZ / BR), (size_t)16 * ZDZ * sizeof(float), 3, sample, (int)row, (int)px);
-    L.grids = false;
-    const int vt = g.V <= 6 ? g.V : (g.V <= 8 ? 8 : (g.V <= 10 ? 10 : (g.V <= 12 ? 12 : 16)));
-    return find_one_zd_kernel(KernelKey{1, 1, vt, vt > 8 ? 8 : 4, false, rq.hm16 ? 9 : 8}, L.fn, L.name);
+    const int V = rq.g.V, vt = V <= 6 ? V : (V <= 8 ? 8 : (V <= 10 ? 10 : (V <= 12 ? 12 : 16)));
+    return KernelKey{.jp = 1, .ps = 1, .cl = rq.result == RESULT_CHANNELS_LAST, .taps16 = rq.taps16, .zd = rq.result == RESULT_ZSPECTRUM,
+                     .views = vt, .chunk = vt > 8 ? 8 : 4, .mask = rq.mask != MASK_NONE};
 }
 
-// Jp = 32 (17..32 joints: the 17 COCO joints of the Shelf / Campus configurations).  A packed fp32 pixel is exactly one
-// 128-byte line.  It is gathered as two channel groups, one launch each, both reading pixels at a stride of PS = 32:
-//   group 0   channels 0-15 through the JP = 16 kernel;
-//   group 1   channels 16..J-1 through a launch of width ceil4(J - 16) (16 with bf16 maps or cubes, whose kernels
-//             exist at JP = 16 only).  Its view pointers start 16 channels into the pixel (the wave-uniform row base moves,
-//             no VGPR does), its result pointer 16 channel planes further, and its Geom has J - 16 channels.
-// The per-channel arithmetic is the 16-channel kernels', so each group is bit-identical to the oracle by construction.  Only
-// group 0 writes grids; a sample that `valid` skips gets zeros in each group.  Planar results only (dense or strided: the
-// strided path already carries full-volume strides), the two planar defaults only (pipe / brick stacks).  A pass mask only
-// with SP3D_HM_WIDE_MASK (sp3d_unproject_fwd_train): each group writes the 16-bit words of its own channels into its own
-// plane of P * N words - group 1's mask pointer lies P * N words further, bit j of its words being channel 16 + j.
-// SP3D_OUT_ZSPECTRUM (rq.zd): the same two groups through the ZD brick kernels.  The spectrum is (P, J, K, X/4, Y/4, 16)
-// complex over ALL J channels, so the sample stride comes from here (Geom.sB, in complex elements - the ZD form reads no
-// other result stride) and group 1 starts 16 channel planes = 16 * K * (X/4) * (Y/4) * 16 complex values further.
-
-// The one place a forward request becomes launches: every downgrade and refusal, in this order.  Pure host arithmetic.
+// The one place a decoded request becomes launches: the downgrades, and the refusals of packed pixels that follow from the
+// tuning and the kernel tables.  Pure host arithmetic.
 static int resolve_fwd(const FwdRequest &rq, FwdTuning t, Launch (&plan)[SP3D_PLAN_RECORDS], int &n)
 {
     n = 1;
     Launch &L = plan[0];
     L = Launch{};
-    L.g = rq.g; L.grid_y = 1; L.grids = !rq.zd;      // a z-spectrum launch writes no grids (its entries take none)
-    // bf16 maps into a training forward (SP3D_HM_BF16_TRAIN): a form of the two entries that write a pass mask and of nothing
-    // else - not of the bf16 storage pair, of the inference flag or of either spectrum; packed pixels of 16 elements, or of 32
-    // with the two-plane mask, on the kernels that clamp a 2x2 block; the one-channel read has resolve_one's limits
-    if (rq.hm16_train) {
-        if (!rq.g.pass_mask || rq.io || rq.hm16 || rq.zd || rq.one_zd) return SP3D_EUNSUPPORTED;
-        if (!rq.one && (rq.layout == SP3D_LAYOUT_PLANAR || (rq.layout == SP3D_LAYOUT_NHWC && rq.Jp != (rq.wide_mask ? WIDE_PS : 16)) ||
-                        rq.g.w < 2 || rq.g.h < 2 || (int64_t)rq.g.h * rq.g.w > (1 << 24)))
-            return SP3D_EUNSUPPORTED;
-    }
-    if (rq.one_zd) return resolve_one_zd(rq, L);
-    // bf16 maps into an fp32 result (SP3D_HM_BF16_IN): a form of the z-spectrum result and of the one-channel read, of nothing
-    // else - not of the bf16 storage pair, not of the two-plane mask, channels-last only from the one-channel kernel
-    if (rq.hm16 && (!(rq.zd || rq.one) || rq.io || rq.wide_mask || (rq.out_cl && !rq.one))) return SP3D_EUNSUPPORTED;
-    // the two-plane mask belongs to the Jp = 32 training forward with a planar fp32 result, and to nothing else
-    if (rq.wide_mask && (rq.one || !rq.g.pass_mask || rq.layout != SP3D_LAYOUT_NHWC || rq.Jp != WIDE_PS || rq.out_cl || rq.io))
-        return SP3D_EUNSUPPORTED;
-    // the z-spectrum result: packed fp32 maps at Jp = 16 or 32, the one grid shape the z-DFT is built for, nothing else next to it
-    if (rq.zd && (rq.one || rq.wide_mask || rq.layout != SP3D_LAYOUT_NHWC || rq.io || rq.out_cl || rq.g.pass_mask ||
-                  (rq.Jp != 16 && rq.Jp != WIDE_PS) || rq.g.Z != ZDZ || (rq.g.X % BR) || (rq.g.Y % BR)))
-        return SP3D_EUNSUPPORTED;
-    if (rq.one) return resolve_one(rq, L);
-    if (rq.layout == SP3D_LAYOUT_PLANAR) {
-        if (rq.out_cl || rq.io) return SP3D_EUNSUPPORTED;
-        set_launch(L, (rq.g.N + TILE - 1) / TILE, TILE, 0, 0, 0, 0);
-        L.grid_y = rq.g.B;
-        const int jc = rq.g.J == 1 ? 1 : (rq.g.J <= 4 ? 4 : 16);
-        return find_planar_kernel(KernelKey{jc, jc, 0, 0, 0, 0}, L.fn, L.name);
-    }
-    if (rq.layout != SP3D_LAYOUT_NHWC) return SP3D_EINVAL;
+    L.g = rq.g; L.grid_y = 1; L.grids = rq.result != RESULT_ZSPECTRUM;      // a z-spectrum launch writes no grids (its entries take none)
     Geom g = rq.g;
+    if (one_channel(rq) && rq.result == RESULT_ZSPECTRUM) {
+        // unproject_one_zd_kernel: one workgroup of ZDZ / BR waves per 4 x 4 tile of z columns, exactly P * tiles of them (the
+        // kernel deals them to the XCDs itself), a slab of 16 x ZDZ floats of LDS
+        const int nby = g.Y / BR, tiles = (g.X / BR) * nby;
+        set_xcd_fields(L.g, tiles);
+        set_brick_fields(L.g, tiles, nby);
+        set_one_launch(rq, L, (unsigned)(g.B * tiles), 64 * (ZDZ / BR), (size_t)16 * ZDZ * sizeof(float));
+        return find_one_zd_kernel(one_slots_key(rq), L.fn, L.name);
+    }
+    if (one_channel(rq)) {
+        // unproject_one_kernel: g.J = channels written (1, or 4 = value + three zero channels), the pipe kernel's tile map -
+        // 64-voxel tiles dealt to a sample's XCDs in chunks
+        const int ptiles = (g.N + 63) / 64;
+        L.g.xcd_order = default_xcd_order(g);
+        L.g.xcd_chunk = default_xcd_chunk(g, ptiles);
+        set_xcd_fields(L.g, ptiles);
+        set_one_launch(rq, L, xcd_grid_blocks(g.B, ptiles, L.g.xcd_chunk), 64, 0);
+        return find_one_kernel(one_slots_key(rq), L.fn, L.name);
+    }
+    if (rq.read == READ_PLANAR) {
+        set_launch(L, (g.N + TILE - 1) / TILE, TILE, 0, 0, 0, 0);
+        L.grid_y = g.B;
+        const int jc = g.J == 1 ? 1 : (g.J <= 4 ? 4 : 16);
+        return find_planar_kernel(KernelKey{.jp = jc, .ps = jc}, L.fn, L.name);
+    }
     g.xcd_order = (t.plain_sweep ? 0 : default_xcd_order(g)) | (t.z_fastest ? 2 : 0);
     g.xcd_chunk = t.forced_chunk ? 1 << (t.forced_chunk - 1) : default_xcd_chunk(g, (g.N + 63) / 64);
     const FwdTuning asked = t, pipe = default_tuning(FWD_PIPE), stacks = default_tuning(FWD_BRICK_STACKS);
-    // the pipelined kernels clamp a 2x2 block (needs a 2x2 image) and form pixel indices with 24-bit multiplies
-    const bool tile_only = g.w < 2 || g.h < 2 || (int64_t)g.h * g.w > (1 << 24);
-    if (rq.zd) {
-        if (tile_only) return SP3D_EUNSUPPORTED;
-        g.sB = (long long)g.J * (ZDSZ / 2 + 1) * (g.X / BR) * (g.Y / BR) * 16;
-    }
+    const bool tile_only = !pipelined_image(g);
+    if (rq.result == RESULT_ZSPECTRUM) g.sB = (long long)g.J * (ZDSZ / 2 + 1) * (g.X / BR) * (g.Y / BR) * 16;
     if (tile_only) t.pipe = t.brick = 0;
     if (t.brick) t.pipe = 1;
-    if (rq.io || rq.hm16_train) t.one_wave = 1;    // bf16 taps: one wave per workgroup only
-    if (rq.Jp == WIDE_PS) {
-        if (g.J > WIDE_PS || rq.out_cl || (g.pass_mask && !rq.wide_mask) || tile_only) return SP3D_EUNSUPPORTED;
-        if (memcmp(&asked, &pipe, sizeof(t)) && memcmp(&asked, &stacks, sizeof(t))) return SP3D_EUNSUPPORTED;
-        Geom gg = g;
-        gg.J = g.J < 16 ? g.J : 16;
-        int rc = resolve_group(rq, t, gg, 16, WIDE_PS, L);
-        if (rc || g.J <= 16) return rc;
-        Launch &L1 = plan[n++];
-        L1 = L;
-        gg.J = g.J - 16;
-        if (g.pass_mask) gg.pass_mask = g.pass_mask + (size_t)g.B * g.N;
-        L1.view_off = 16 * (((rq.io & 1) || rq.hm16 || rq.hm16_train) ? 2 : 4);
-        L1.out_off = rq.zd ? (size_t)16 * (ZDSZ / 2 + 1) * (g.X / BR) * (g.Y / BR) * 16 * 8
-                           : (size_t)16 * g.sJ * ((rq.io & 2) ? 2 : 4);
-        L1.grids = false;
-        return resolve_group(rq, t, gg, (rq.io || rq.hm16 || rq.hm16_train) ? 16 : (gg.J + 3) / 4 * 4, WIDE_PS, L1);
+    if (rq.taps16 || rq.cubes16) t.one_wave = 1;    // bf16 taps or cubes: one wave per workgroup only
+    if (rq.Jp != WIDE_PS) {
+        if (rq.Jp < g.J || (rq.Jp & 3) || rq.Jp > 16) return SP3D_EUNSUPPORTED;
+        return resolve_group(rq, t, g, rq.Jp, rq.Jp, L);
     }
-    if (rq.Jp < g.J || (rq.Jp & 3) || rq.Jp > 16) return SP3D_EUNSUPPORTED;
-    if (rq.out_cl && (g.J & 3)) return SP3D_EUNSUPPORTED;        // channels-last rows must be 16-B multiples
-    if (rq.io && !t.pipe) return SP3D_EUNSUPPORTED;
-    return resolve_group(rq, t, g, rq.Jp, rq.Jp, L);
+    // Jp = 32 (17..32 joints: the 17 COCO joints of the Shelf / Campus configurations).  A packed fp32 pixel is exactly one
+    // 128-byte line.  It is gathered as two channel groups, one launch each, both reading pixels at a stride of PS = 32:
+    //   group 0   channels 0-15 through the JP = 16 kernel;
+    //   group 1   channels 16..J-1 through a launch of width ceil4(J - 16) (16 with bf16 maps or cubes, whose kernels
+    //             exist at JP = 16 only).  Its view pointers start 16 channels into the pixel (the wave-uniform row base moves,
+    //             no VGPR does), its result pointer 16 channel planes further, and its Geom has J - 16 channels.
+    // The per-channel arithmetic is the 16-channel kernels', so each group is bit-identical to the oracle by construction.  Only
+    // group 0 writes grids; a sample that `valid` skips gets zeros in each group.  Planar results only (dense or strided: the
+    // strided path already carries full-volume strides), the two planar defaults only (pipe / brick stacks).  A pass mask only
+    // in two planes (SP3D_HM_WIDE_MASK): each group writes the 16-bit words of its own channels into its own plane of P * N
+    // words - group 1's mask pointer lies P * N words further, bit j of its words being channel 16 + j.
+    // RESULT_ZSPECTRUM: the same two groups through the ZD brick kernels.  The spectrum is (P, J, K, X/4, Y/4, 16) complex over
+    // ALL J channels, so the sample stride comes from here (Geom.sB, in complex elements - the ZD form reads no other result
+    // stride) and group 1 starts 16 channel planes = 16 * K * (X/4) * (Y/4) * 16 complex values further.
+    if (g.J > WIDE_PS || rq.result == RESULT_CHANNELS_LAST || rq.mask == MASK_ONE_PLANE || tile_only) return SP3D_EUNSUPPORTED;
+    if (memcmp(&asked, &pipe, sizeof(t)) && memcmp(&asked, &stacks, sizeof(t))) return SP3D_EUNSUPPORTED;
+    Geom gg = g;
+    gg.J = g.J < 16 ? g.J : 16;
+    int rc = resolve_group(rq, t, gg, 16, WIDE_PS, L);
+    if (rc || g.J <= 16) return rc;
+    Launch &L1 = plan[n++];
+    L1 = L;
+    gg.J = g.J - 16;
+    if (g.pass_mask) gg.pass_mask = g.pass_mask + (size_t)g.B * g.N;
+    L1.view_off = 16 * (rq.taps16 ? 2 : 4);
+    L1.out_off = rq.result == RESULT_ZSPECTRUM ? (size_t)16 * (ZDSZ / 2 + 1) * (g.X / BR) * (g.Y / BR) * 16 * 8
+                                               : (size_t)16 * g.sJ * (rq.cubes16 ? 2 : 4);
+    L1.grids = false;
+    return resolve_group(rq, t, gg, (rq.taps16 || rq.cubes16) ? 16 : (gg.J + 3) / 4 * 4, WIDE_PS, L1);
 }
 
 // the one place a forward kernel is launched
@@ -321,46 +290,8 @@ static int launch_fwd(Launch L, Views v, const float *cam, const float *centers,
     return launch_status();
 }
 
-// The steps every forward entry point starts with: the Geom, the null check (`ptrs`: all its required pointers are there)
-// and the flag bits of hm_layout.
-static int fwd_request(FwdRequest &rq, int hm_layout, int Jp, bool ptrs, int B, int V, int J, int h, int w, int X,
-                       int Y, int Z, const float *grid_size, int W_in, int H_in)
-{
-    const int rc = make_geom(rq.g, B, V, J, h, w, X, Y, Z, grid_size, W_in, H_in);
-    if (rc) return rc;
-    if (!ptrs) return SP3D_ENULL;
-    rq.layout = hm_layout & 0xff; rq.Jp = Jp;
-    rq.io = ((hm_layout & SP3D_HM_BF16) ? 1 : 0) | ((hm_layout & SP3D_OUT_BF16) ? 2 : 0);
-    rq.one = (hm_layout & SP3D_HM_ONE_CHANNEL) != 0;
-    rq.out_cl = (hm_layout & SP3D_OUT_CHANNELS_LAST) != 0;
-    rq.wide_mask = (hm_layout & SP3D_HM_WIDE_MASK) != 0;
-    rq.zd = (hm_layout & SP3D_OUT_ZSPECTRUM) != 0;
-    rq.one_zd = (hm_layout & SP3D_HM_ONE_ZSPECTRUM) != 0;
-    rq.hm16 = (hm_layout & SP3D_HM_BF16_IN) != 0;
-    rq.hm16_train = (hm_layout & SP3D_HM_BF16_TRAIN) != 0;
-    rq.out_aligned = true; rq.one_train = false;
-    return SP3D_OK;
-}
-
-// ... and end with: the views, the plan, its launches
-static int run_fwd(const FwdRequest &rq, const FwdTuning &t, const float *const *hm_views, const float *cam, const float *centers,
-                   const uint8_t *valid, float *cubes, float *grids, void *stream)
-{
-    Views v;
-    int rc = load_views(v, hm_views, rq.g.V);
-    if (rc) return rc;
-    Launch plan[SP3D_PLAN_RECORDS];
-    int n;
-    rc = resolve_fwd(rq, t, plan, n);
-    // SP3D_HM_WIDE_MASK at J <= 16: no second group, so nobody writes plane 1 - it is zeros
-    if (!rc && rq.wide_mask && n == 1)
-        rc = (int)hipMemsetAsync(rq.g.pass_mask + (size_t)rq.g.B * rq.g.N, 0, (size_t)rq.g.B * rq.g.N * sizeof(uint16_t), (hipStream_t)stream);
-    for (int i = 0; !rc && i < n; ++i) rc = launch_fwd(plan[i], v, cam, centers, valid, cubes, grids, (hipStream_t)stream);
-    return rc;
-}
-
-// result strides of sp3d_unproject_fwd_strided into the Geom; `cubes` decides whether 16-byte pieces are allowed
-static int set_result_strides(Geom &g, const int64_t *out_strides, const void *cubes)
+// result strides of sp3d_unproject_fwd_strided into the Geom; 16-byte pieces are allowed on a 16-byte aligned result only
+static int set_result_strides(Geom &g, const int64_t *out_strides, unsigned misaligned)
 {
     const int64_t sB = out_strides[0], sJ = out_strides[1], sX = out_strides[2], sY = out_strides[3];
     // the planes must not overlap and must fit 32-bit in-plane offsets
@@ -370,8 +301,145 @@ static int set_result_strides(Geom &g, const int64_t *out_strides, const void *c
     g.dense = (sY == g.Z && sX == (int64_t)g.Y * g.Z && sJ == (int64_t)g.N && sB == (int64_t)g.J * g.N) ? 1 : 0;
     // 16-byte pieces need 4-element aligned rows (and a 16-byte aligned base pointer); otherwise the kernels take their
     // scalar store path, which is correct for any stride but slow
-    g.vec4 = ((g.dense || ((sY | sX | sJ | sB) & 3) == 0) && ((uintptr_t)cubes & 15) == 0) ? 1 : 0;
+    g.vec4 = ((g.dense || ((sY | sX | sJ | sB) & 3) == 0) && (misaligned & 15) == 0) ? 1 : 0;
     return SP3D_OK;
+}
+
+// ------------------------------------------------------------------------------------------
+// The rules: which request an entry's arguments spell, or why none (include/sp3d.h gives the same rules as prose, flag by flag).
+// Two tables of plain ints and two functions for what a table cannot hold.  Every entry and the plan entry decode through them.
+// ------------------------------------------------------------------------------------------
+enum : int { F_CL = SP3D_OUT_CHANNELS_LAST, F_HB = SP3D_HM_BF16, F_OB = SP3D_OUT_BF16, F_ONE = SP3D_HM_ONE_CHANNEL, F_WM = SP3D_HM_WIDE_MASK,
+             F_ZS = SP3D_OUT_ZSPECTRUM, F_OZ = SP3D_HM_ONE_ZSPECTRUM, F_IN16 = SP3D_HM_BF16_IN, F_TR16 = SP3D_HM_BF16_TRAIN, F_ALL = 0x1ff00 };
+
+// Per entry, in the order of SP3D_PLAN_*: the layout byte it reads (-1: the caller's), the flags it implies, the flags it does not
+// read, the flags it refuses outright, and whether it writes a pass mask.  The last two entries take no layout word; what their
+// plans answer for a word with flag bits is written here, and nowhere else: the word's layout byte is not read, sp3d_unproject_fwd_zdft
+// refuses four flags and ignores the rest, sp3d_unproject_fwd_variant refuses one, ignores the rest and takes F_CL from its tuning word.
+struct EntryRule { int layout, implied, unread, refused, mask; };
+static const EntryRule ENTRY_RULES[] = {
+    /* _INDEXED   */ {-1, 0, 0, 0, 0},
+    /* _STRIDED   */ {-1, 0, 0, F_CL | F_ZS | F_OZ, 0},
+    /* _TRAIN     */ {-1, 0, 0, F_HB | F_OB | F_ONE | F_ZS | F_OZ | F_IN16, 1},
+    /* _ZDFT      */ {SP3D_LAYOUT_NHWC, F_ZS, F_CL | F_HB | F_OB | F_ONE | F_ZS, F_WM | F_OZ | F_IN16 | F_TR16, 0},
+    /* _TUNING    */ {SP3D_LAYOUT_NHWC, 0, F_ALL & ~F_TR16, F_TR16, 0},
+    /* _ONE_TRAIN */ {-1, F_ONE, 0, F_ZS | F_OZ | F_IN16, 1},
+};
+// Per flag: the flags that may stand next to it, the flags one of which must, and whether it needs an entry with a pass mask.
+// Rows 0-3 are answered before the layout byte is (SP3D_EINVAL), the others after it - see decode_fwd.
+struct FlagRule { int flag, beside, one_of, mask; };
+static const FlagRule FLAG_RULES[] = {
+    {F_TR16, F_CL | F_ONE | F_WM, 0, 1},
+    {F_IN16, F_CL | F_ONE | F_ZS | F_OZ, F_ONE | F_ZS | F_OZ, 0},
+    {F_WM, F_TR16, 0, 1},
+    {F_ZS, F_IN16, 0, 0},
+    {F_OZ, F_IN16, 0, 0},
+    {F_ONE, F_CL | F_IN16 | F_TR16, 0, 0},
+    {F_CL, F_HB | F_OB | F_ONE | F_IN16 | F_TR16, 0, 0},
+    {F_HB, F_CL | F_OB, 0, 0},
+    {F_OB, F_CL | F_HB, 0, 0},
+};
+
+// the one-channel kernels form the tap offset with 24-bit multiplies and address it with a 32-bit byte offset
+static bool one_addressable(const FwdRequest &rq)
+{
+    const int64_t row = rq.g.w * one_px(rq);
+    return pipelined_image(rq.g) && row < (1 << 24) && rq.g.h * row * (rq.taps16 ? 2 : 4) <= (int64_t)0x7fffffff;
+}
+// the layout, Jp, J, image and grid a flag needs
+static bool flag_needs(int flag, const FwdRequest &rq, const CallFacts &f)
+{
+    const Geom &g = rq.g;
+    const bool zgrid = g.Z == ZDZ && g.X % BR == 0 && g.Y % BR == 0;         // the one grid shape the z-DFT is built for
+    switch (flag) {
+    case F_CL: return rq.read != READ_PLANAR && (g.J & 3) == 0 && (!one_channel(rq) || (f.misaligned & 15) == 0);   // rows of 16-B multiples
+    case F_HB: case F_OB: return rq.read == READ_PACKED;
+    case F_ONE: return (g.J == 1 || g.J == 4) && one_addressable(rq);
+    case F_WM: return rq.read == READ_PACKED && rq.Jp == WIDE_PS;
+    case F_ZS: return rq.read == READ_PACKED && (rq.Jp == 16 || rq.Jp == WIDE_PS) && zgrid && pipelined_image(g);
+    case F_OZ: return g.J == 1 && zgrid && g.dense && one_addressable(rq);
+    case F_TR16:     // the one-channel read has F_ONE's limits; packed pixels of 16 elements, or of 32 with the two-plane mask
+        return rq.read != READ_PLANAR && (rq.read != READ_PACKED || (rq.Jp == (rq.mask == MASK_TWO_PLANES ? WIDE_PS : 16) && pipelined_image(g)));
+    default: return true;
+    }
+}
+static bool breaks(const FlagRule &r, int flags, const FwdRequest &rq, const CallFacts &f)
+{
+    return (flags & r.flag) && ((flags & ~r.flag & ~r.beside) || (r.one_of && !(flags & r.one_of)) || (r.mask && rq.mask == MASK_NONE) ||
+                                !flag_needs(r.flag, rq, f));
+}
+// what an entry needs beyond its row: of its layout byte, its image and its pointers
+static bool entry_needs(const FwdRequest &rq, int flags, const CallFacts &f)
+{
+    switch (rq.entry) {
+    case SP3D_PLAN_INDEXED: return !(flags & (F_ZS | F_OZ)) || (!f.grids && !f.misaligned);    // a spectrum: whole 128-byte lines, no grids
+    case SP3D_PLAN_STRIDED: return (rq.read == READ_PACKED || (flags & F_ONE)) && has_2x2(rq.g);   // the one-channel read takes either layout
+    case SP3D_PLAN_TRAIN: return rq.read == READ_PACKED && has_2x2(rq.g);
+    case SP3D_PLAN_ZDFT: return rq.Jp == 16 && f.SZ == ZDSZ && !f.misaligned && flag_needs(F_ZS, rq, f);
+    default: return true;
+    }
+}
+
+struct Shape { int B, V, J, h, w, X, Y, Z; const float *grid_size; int W_in, H_in; };      // the shape arguments every entry has
+// (entry, its arguments, the facts about its pointers) -> the request and its tuning, or the refusal.  The order is the order of
+// the return codes: the shape (make_geom), required pointers, the entry's own rule, the result strides, the views, the flags
+// answered before the layout byte, the layout byte, everything else.
+static int decode_fwd(FwdRequest &rq, FwdTuning &t, int entry, int hm_layout, int Jp, const int64_t *out_strides, int variant,
+                      const CallFacts &f, const Shape &s)
+{
+    int rc = make_geom(rq.g, s.B, s.V, s.J, s.h, s.w, s.X, s.Y, s.Z, s.grid_size, s.W_in, s.H_in);
+    if (rc) return rc;
+    if (!f.ptrs) return SP3D_ENULL;
+    const EntryRule &e = ENTRY_RULES[entry];
+    const int layout = e.layout < 0 ? (hm_layout & 0xff) : e.layout;
+    const int flags = (hm_layout & F_ALL & ~e.unread) | e.implied | ((entry == SP3D_PLAN_TUNING && (variant & SP3D_TUNING_CHANNELS_LAST)) ? F_CL : 0);
+    const bool one = (flags & (F_ONE | F_OZ)) != 0;
+    rq.entry = entry; rq.Jp = Jp;
+    rq.read = layout == SP3D_LAYOUT_PLANAR ? (one ? READ_ONE_PLANAR : READ_PLANAR)
+                                           : (layout == SP3D_LAYOUT_NHWC ? (one ? READ_ONE_PACKED : READ_PACKED) : READ_UNKNOWN);
+    rq.result = (flags & (F_ZS | F_OZ)) ? RESULT_ZSPECTRUM : ((flags & F_CL) ? RESULT_CHANNELS_LAST : RESULT_PLANAR);
+    rq.mask = !e.mask ? MASK_NONE : ((flags & F_WM) ? MASK_TWO_PLANES : MASK_ONE_PLANE);
+    rq.taps16 = (flags & (F_HB | F_IN16 | F_TR16)) ? 1 : 0;
+    rq.cubes16 = (flags & F_OB) ? 1 : 0;
+    // a spectrum: the brick stacks as sp3d_unproject_fwd_zdft (the one-channel form has one kernel, the tuning is not read)
+    t = rq.result == RESULT_ZSPECTRUM ? default_tuning(one ? FWD_PIPE : FWD_BRICK_STACKS) : default_tuning(rq.g, rq.result == RESULT_CHANNELS_LAST);
+    if (entry == SP3D_PLAN_TUNING) t = decode_tuning(variant);
+    if ((hm_layout & e.refused) || !entry_needs(rq, flags, f)) return SP3D_EUNSUPPORTED;
+    if (entry == SP3D_PLAN_STRIDED && out_strides && (rc = set_result_strides(rq.g, out_strides, f.misaligned))) return rc;
+    if (!f.views) return SP3D_ENULL;
+    const int early = (flags & F_OZ) ? 1 : 4;       // the one-channel spectrum answers its layout byte before its other refusals
+    for (int i = 0; i < early; ++i)
+        if (breaks(FLAG_RULES[i], flags, rq, f)) return SP3D_EUNSUPPORTED;
+    if (rq.read == READ_UNKNOWN || (one && Jp < 1)) return SP3D_EINVAL;
+    for (const FlagRule &r : FLAG_RULES)
+        if (breaks(r, flags, rq, f)) return SP3D_EUNSUPPORTED;
+    return SP3D_OK;
+}
+
+// What every forward entry is: the facts about its pointers, decode_fwd, the two pointers the Geom carries, the views, the plan,
+// its launches.  `ptrs`: every required pointer but the views is there.
+static int run_entry(int entry, int hm_layout, int Jp, const int64_t *out_strides, int variant, int SZ, const Shape &s, bool ptrs,
+                     const float *const *hm_views, const float *cam, const int32_t *sample_of, const float *centers, const uint8_t *valid,
+                     float *cubes, float *grids, uint16_t *pass_mask, void *stream)
+{
+    bool views = hm_views != nullptr;
+    for (int c = 0; views && c < s.V && c < SP3D_MAX_VIEWS; ++c) views = hm_views[c] != nullptr;
+    FwdRequest rq;
+    FwdTuning t;
+    int rc = decode_fwd(rq, t, entry, hm_layout, Jp, out_strides, variant,
+                        CallFacts{ptrs && cam && centers && valid && cubes, views, grids != nullptr, (unsigned)((uintptr_t)cubes & 127), SZ}, s);
+    if (rc) return rc;
+    rq.g.sample_of = sample_of;
+    rq.g.pass_mask = pass_mask;
+    Views v;
+    Launch plan[SP3D_PLAN_RECORDS];
+    int n;
+    if ((rc = load_views(v, hm_views, s.V)) || (rc = resolve_fwd(rq, t, plan, n))) return rc;
+    // two mask planes at J <= 16: no second group, so nobody writes plane 1 - it is zeros
+    if (rq.mask == MASK_TWO_PLANES && n == 1)
+        rc = (int)hipMemsetAsync(pass_mask + (size_t)s.B * rq.g.N, 0, (size_t)s.B * rq.g.N * sizeof(uint16_t), (hipStream_t)stream);
+    for (int i = 0; !rc && i < n; ++i) rc = launch_fwd(plan[i], v, cam, centers, valid, cubes, grids, (hipStream_t)stream);
+    return rc;
 }
 
 } // namespace sp3d
@@ -423,26 +491,14 @@ extern "C" const char *sp3d_error_string(int code)
     }
 }
 
+// The forward entries (include/sp3d.h): each is run_entry with its own SP3D_PLAN_* value; every rule is decode_fwd's.
 extern "C" int sp3d_unproject_fwd_indexed(const float *const *hm_views, int hm_layout, int Jp, const float *cam,
                                           const int32_t *sample_of, const float *centers, const uint8_t *valid,
                                           float *cubes, float *grids, int P, int V, int J, int h, int w, int X, int Y,
                                           int Z, const float *grid_size, int W_in, int H_in, void *stream)
 {
-    FwdRequest rq;
-    const int rc = fwd_request(rq, hm_layout, Jp, cam && centers && valid && cubes, P, V, J, h, w, X, Y, Z,
-                               grid_size, W_in, H_in);
-    if (rc) return rc;
-    rq.g.sample_of = sample_of;
-    rq.out_aligned = ((uintptr_t)cubes & 15) == 0;
-    if (rq.one_zd) {    // SP3D_HM_ONE_ZSPECTRUM: `cubes` is the spectrum of the one channel, whole 128-byte lines, no grids
-        if (grids || ((uintptr_t)cubes & 127)) return SP3D_EUNSUPPORTED;
-        return run_fwd(rq, default_tuning(FWD_PIPE), hm_views, cam, centers, valid, cubes, nullptr, stream);
-    }
-    if (rq.zd) {    // SP3D_OUT_ZSPECTRUM: `cubes` is the spectrum, whole 128-byte lines; the brick stacks as sp3d_unproject_fwd_zdft
-        if (grids || ((uintptr_t)cubes & 127)) return SP3D_EUNSUPPORTED;
-        return run_fwd(rq, default_tuning(FWD_BRICK_STACKS), hm_views, cam, centers, valid, cubes, nullptr, stream);
-    }
-    return run_fwd(rq, default_tuning(rq.g, rq.out_cl), hm_views, cam, centers, valid, cubes, grids, stream);
+    return run_entry(SP3D_PLAN_INDEXED, hm_layout, Jp, nullptr, 0, ZDSZ, Shape{P, V, J, h, w, X, Y, Z, grid_size, W_in, H_in}, true, hm_views,
+                     cam, sample_of, centers, valid, cubes, grids, nullptr, stream);
 }
 
 extern "C" int sp3d_unproject_fwd_strided(const float *const *hm_views, int hm_layout, int Jp, const float *cam,
@@ -450,31 +506,16 @@ extern "C" int sp3d_unproject_fwd_strided(const float *const *hm_views, int hm_l
                                           float *cubes, const int64_t *out_strides, int P, int V, int J, int h, int w,
                                           int X, int Y, int Z, const float *grid_size, int W_in, int H_in, void *stream)
 {
-    FwdRequest rq;
-    int rc = fwd_request(rq, hm_layout, Jp, cam && centers && valid && cubes && out_strides, P, V, J, h, w,
-                         X, Y, Z, grid_size, W_in, H_in);
-    if (rc) return rc;
-    // the one-channel read takes either layout
-    if ((!rq.one && rq.layout != SP3D_LAYOUT_NHWC) || rq.out_cl || rq.zd || rq.one_zd || w < 2 || h < 2) return SP3D_EUNSUPPORTED;
-    rc = set_result_strides(rq.g, out_strides, cubes);
-    if (rc) return rc;
-    rq.g.sample_of = sample_of;
-    return run_fwd(rq, default_tuning(rq.g, false), hm_views, cam, centers, valid, cubes, nullptr, stream);
+    return run_entry(SP3D_PLAN_STRIDED, hm_layout, Jp, out_strides, 0, ZDSZ, Shape{P, V, J, h, w, X, Y, Z, grid_size, W_in, H_in},
+                     out_strides != nullptr, hm_views, cam, sample_of, centers, valid, cubes, nullptr, nullptr, stream);
 }
 
 extern "C" int sp3d_unproject_fwd_zdft(const float *const *hm_views, int Jp, const float *cam, const float *centers,
                                        const uint8_t *valid, float *spec, int B, int V, int J, int h, int w, int X, int Y,
                                        int Z, const float *grid_size, int W_in, int H_in, int SZ, void *stream)
 {
-    FwdRequest rq;
-    const int rc = fwd_request(rq, SP3D_LAYOUT_NHWC, Jp, cam && centers && valid && spec, B, V, J, h, w, X, Y, Z,
-                               grid_size, W_in, H_in);
-    if (rc) return rc;
-    if (Jp != 16 || Z != ZDZ || SZ != ZDSZ || (X % BR) || (Y % BR) || w < 2 || h < 2 || (int64_t)h * w > (1 << 24) ||
-        ((uintptr_t)spec & 127))
-        return SP3D_EUNSUPPORTED;
-    rq.zd = true;
-    return run_fwd(rq, default_tuning(FWD_BRICK_STACKS), hm_views, cam, centers, valid, spec, nullptr, stream);
+    return run_entry(SP3D_PLAN_ZDFT, 0, Jp, nullptr, 0, SZ, Shape{B, V, J, h, w, X, Y, Z, grid_size, W_in, H_in}, true, hm_views, cam, nullptr,
+                     centers, valid, spec, nullptr, nullptr, stream);
 }
 
 extern "C" int sp3d_unproject_fwd(const float *const *hm_views, int hm_layout, int Jp, const float *cam,
@@ -493,14 +534,12 @@ extern "C" int sp3d_unproject_fwd_variant(const float *const *hm_views, int Jp, 
                                           int h, int w, int X, int Y, int Z, const float *grid_size, int W_in,
                                           int H_in, int variant, void *stream)
 {
-    FwdRequest rq;
-    const int rc = fwd_request(rq, SP3D_LAYOUT_NHWC | ((variant & SP3D_TUNING_CHANNELS_LAST) ? SP3D_OUT_CHANNELS_LAST : 0),
-                               Jp, cam && centers && valid && cubes, B, V, J, h, w, X, Y, Z, grid_size, W_in, H_in);
-    if (rc) return rc;
-    return run_fwd(rq, decode_tuning(variant), hm_views, cam, centers, valid, cubes, grids, stream);
+    return run_entry(SP3D_PLAN_TUNING, 0, Jp, nullptr, variant, ZDSZ, Shape{B, V, J, h, w, X, Y, Z, grid_size, W_in, H_in}, true, hm_views, cam,
+                     nullptr, centers, valid, cubes, grids, nullptr, stream);
 }
 
-// Measurement only (sp3d_tuning.h): the launches resolve_fwd() decides on for a request given as shapes.  No HIP call.
+// Measurement only (sp3d_tuning.h): the launches an entry's request resolves to, for a request given as shapes.  An entry without
+// pointers: their facts are stated (all there, aligned, no grids), the launches are copied out instead of run.  No HIP call.
 extern "C" int sp3d_unproject_fwd_plan(int entry, int hm_layout, int Jp, const int64_t *out_strides, int B, int V, int J, int h,
                                        int w, int X, int Y, int Z, int variant, char *names, int32_t *fields, int32_t *tuning,
                                        int32_t *records)
@@ -508,24 +547,11 @@ extern "C" int sp3d_unproject_fwd_plan(int entry, int hm_layout, int Jp, const i
     if (!names || !fields || !tuning || !records) return SP3D_ENULL;
     if (entry < SP3D_PLAN_INDEXED || entry > SP3D_PLAN_ONE_TRAIN) return SP3D_EINVAL;
     const float grid_size[3] = {1.0f, 1.0f, 1.0f};
-    const bool hm16_train = (hm_layout & SP3D_HM_BF16_TRAIN) != 0;       // as asked: two entries below rewrite the word
-    if (entry == SP3D_PLAN_ZDFT) hm_layout = SP3D_LAYOUT_NHWC | (hm_layout & (SP3D_HM_WIDE_MASK | SP3D_HM_ONE_ZSPECTRUM | SP3D_HM_BF16_IN));     // the entry has no layout word; the flags are kept to be refused
-    if (entry == SP3D_PLAN_TUNING) hm_layout = SP3D_LAYOUT_NHWC | ((variant & SP3D_TUNING_CHANNELS_LAST) ? SP3D_OUT_CHANNELS_LAST : 0);
-    if (entry == SP3D_PLAN_ONE_TRAIN) hm_layout |= SP3D_HM_ONE_CHANNEL;
     FwdRequest rq;
-    int rc = fwd_request(rq, hm_layout, Jp, true, B, V, J, h, w, X, Y, Z, grid_size, 1, 1);
-    if (!rc && entry == SP3D_PLAN_STRIDED && out_strides) rc = set_result_strides(rq.g, out_strides, nullptr);
+    FwdTuning t;
+    int rc = decode_fwd(rq, t, entry, hm_layout, Jp, out_strides, variant, CallFacts{true, true, false, 0, ZDSZ},
+                        Shape{B, V, J, h, w, X, Y, Z, grid_size, 1, 1});
     if (rc) return rc;
-    // SP3D_OUT_ZSPECTRUM belongs to the indexed entry alone; sp3d_unproject_fwd_zdft keeps its own Jp == 16
-    if ((rq.zd || rq.one_zd) && entry != SP3D_PLAN_INDEXED) return SP3D_EUNSUPPORTED;
-    if (entry == SP3D_PLAN_ZDFT && (Jp != 16 || rq.hm16)) return SP3D_EUNSUPPORTED;
-    if ((entry == SP3D_PLAN_TRAIN || entry == SP3D_PLAN_ONE_TRAIN) && rq.hm16) return SP3D_EUNSUPPORTED;     // as the two entries answer
-    if (hm16_train && entry != SP3D_PLAN_TRAIN && entry != SP3D_PLAN_ONE_TRAIN) return SP3D_EUNSUPPORTED;   // no pass mask, no such form
-    rq.one_train = entry == SP3D_PLAN_ONE_TRAIN;
-    if (entry == SP3D_PLAN_TRAIN || rq.one_train) rq.g.pass_mask = reinterpret_cast<uint16_t *>(records);    // "there is one": never dereferenced
-    rq.zd = rq.zd || entry == SP3D_PLAN_ZDFT;
-    const FwdTuning t = entry == SP3D_PLAN_TUNING ? decode_tuning(variant)
-                                                  : (rq.zd ? default_tuning(FWD_BRICK_STACKS) : default_tuning(rq.g, rq.out_cl));
     memcpy(tuning, &t, sizeof(t));
     Launch plan[SP3D_PLAN_RECORDS];
     rc = resolve_fwd(rq, t, plan, *records);
@@ -546,42 +572,27 @@ extern "C" int sp3d_unproject_fwd_plan(int entry, int hm_layout, int Jp, const i
 }
 
 // forward with the gradient pass mask (uint16 per voxel, bit j = channel j passes gradient) for
-// sp3d_unproject_bwd_packed.  NHWC input only (the pipelined kernels): fp32 pixels, or bf16 pixels with SP3D_HM_BF16_TRAIN
-// (resolve_fwd holds that flag's refusals).
+// sp3d_unproject_bwd_packed.  NHWC input only (the pipelined kernels): fp32 pixels, or bf16 pixels with SP3D_HM_BF16_TRAIN.
 extern "C" int sp3d_unproject_fwd_train(const float *const *hm_views, int hm_layout, int Jp, const float *cam,
                                         const int32_t *sample_of, const float *centers, const uint8_t *valid,
                                         float *cubes, float *grids, uint16_t *pass_mask, int P, int V, int J, int h,
                                         int w, int X, int Y, int Z, const float *grid_size, int W_in, int H_in,
                                         void *stream)
 {
-    FwdRequest rq;
-    const int rc = fwd_request(rq, hm_layout, Jp, cam && centers && valid && cubes && pass_mask, P, V, J, h, w,
-                               X, Y, Z, grid_size, W_in, H_in);
-    if (rc) return rc;
-    if (rq.layout != SP3D_LAYOUT_NHWC || rq.io || rq.one || rq.zd || rq.one_zd || rq.hm16 || w < 2 || h < 2) return SP3D_EUNSUPPORTED;
-    rq.g.sample_of = sample_of;
-    rq.g.pass_mask = pass_mask;
-    return run_fwd(rq, default_tuning(rq.g, rq.out_cl), hm_views, cam, centers, valid, cubes, grids, stream);
+    return run_entry(SP3D_PLAN_TRAIN, hm_layout, Jp, nullptr, 0, ZDSZ, Shape{P, V, J, h, w, X, Y, Z, grid_size, W_in, H_in}, pass_mask != nullptr,
+                     hm_views, cam, sample_of, centers, valid, cubes, grids, pass_mask, stream);
 }
 
 // One-channel training forward: sp3d_unproject_fwd_indexed with SP3D_HM_ONE_CHANNEL (implied) + the pass mask at J = 1, in
-// the words of sp3d_unproject_fwd_train.  The refusals are resolve_one's; SP3D_HM_BF16_TRAIN reads 2-byte taps.
+// the words of sp3d_unproject_fwd_train.  SP3D_HM_BF16_TRAIN reads 2-byte taps.
 extern "C" int sp3d_unproject_one_fwd_train(const float *const *hm_views, int hm_layout, int Jp, const float *cam,
                                             const int32_t *sample_of, const float *centers, const uint8_t *valid,
                                             float *cubes, float *grids, uint16_t *pass_mask, int P, int V, int J, int h,
                                             int w, int X, int Y, int Z, const float *grid_size, int W_in, int H_in,
                                             void *stream)
 {
-    FwdRequest rq;
-    const int rc = fwd_request(rq, hm_layout | SP3D_HM_ONE_CHANNEL, Jp, cam && centers && valid && cubes && pass_mask, P, V,
-                               J, h, w, X, Y, Z, grid_size, W_in, H_in);
-    if (rc) return rc;
-    if (rq.zd || rq.one_zd || rq.hm16) return SP3D_EUNSUPPORTED;
-    rq.one_train = true;
-    rq.g.sample_of = sample_of;
-    rq.g.pass_mask = pass_mask;
-    rq.out_aligned = ((uintptr_t)cubes & 15) == 0;
-    return run_fwd(rq, default_tuning(rq.g, rq.out_cl), hm_views, cam, centers, valid, cubes, grids, stream);
+    return run_entry(SP3D_PLAN_ONE_TRAIN, hm_layout, Jp, nullptr, 0, ZDSZ, Shape{P, V, J, h, w, X, Y, Z, grid_size, W_in, H_in}, pass_mask != nullptr,
+                     hm_views, cam, sample_of, centers, valid, cubes, grids, pass_mask, stream);
 }
 
 // measurement only: one thread writes the chip-wide 100 MHz clock (s_memrealtime) to *slot.  Two of them around a kernel

@@ -484,15 +484,15 @@ __global__ __launch_bounds__(512, ZD ? SP3D_ZD_MINW : SP3D_BRICK_MINW) void unpr
 }
 
 #define SP3D_BRICK(JP_, CL_, TI_, TO_, ZD_, PS_) \
-    SP3D_ROW(BrickFn, (KernelKey{JP_, PS_, ZD_, 0, CL_, io_of<TI_, TO_>()}), unproject_brick_kernel, JP_, CL_, TI_, TO_, ZD_, PS_)
+    SP3D_ROW(BrickFn, (KernelKey{.jp = JP_, .ps = PS_, .cl = CL_, .taps16 = is16<TI_>(), .cubes16 = is16<TO_>(), .zd = ZD_}), unproject_brick_kernel, JP_, CL_, TI_, TO_, ZD_, PS_)
 // bf16 heat-maps: two lanes per pixel, 16 channels
 #define SP3D_BRICK_H(CL_, TO_, PS_) \
-    SP3D_ROW(BrickFn, (KernelKey{16, PS_, false, 0, CL_, 1 | io_of<float, TO_>()}), unproject_brick_h_kernel, CL_, TO_, PS_)
+    SP3D_ROW(BrickFn, (KernelKey{.jp = 16, .ps = PS_, .cl = CL_, .taps16 = 1, .cubes16 = is16<TO_>()}), unproject_brick_h_kernel, CL_, TO_, PS_)
 // bf16 maps with the z-spectrum result (SP3D_HM_BF16_IN next to SP3D_OUT_ZSPECTRUM): 13..16 joints at PS = 16, both channel
 // groups of a 32-element pixel at PS = 32 (group 1 has width 16 as well, its g.J = J - 16 channels picked by the epilogue).
 // A table of its own, for the reason given below; planned by tests/test_bf16_front_host.py, run by tests/test_gpu_bf16_front.py.
 #define SP3D_BRICK_H_ZD(PS_) \
-    SP3D_ROW(BrickFn, (KernelKey{16, PS_, true, 0, false, 1}), unproject_brick_h_kernel, false, float, PS_, true)
+    SP3D_ROW(BrickFn, (KernelKey{.jp = 16, .ps = PS_, .taps16 = 1, .zd = true}), unproject_brick_h_kernel, false, float, PS_, true)
 static int find_brick_h_zspectrum_kernel(const KernelKey &key, const void *&fn, const char *&name)
 {
     SP3D_BRICK_H_ZD(16) SP3D_BRICK_H_ZD(32)

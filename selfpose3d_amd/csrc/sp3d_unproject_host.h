@@ -83,18 +83,22 @@ inline int load_views(Views &v, const float *const *hm_views, int V)
 // without namespace and parameter list), all three from the same template arguments.  A missing row is SP3D_EUNSUPPORTED.
 // The tables are written as functions, a row being one `if`: an array of kernel pointers and names in a shared object is
 // relocated, hence writable, data, and the library keeps none (tests/test_host_cabi.py).
+// A key is plain ints compared with memcmp.  It is spelled with its field names, in the order below; a field that is not named
+// is zero - a family names exactly what its template varies in.
 struct KernelKey {
-    int jp, ps;          // channels gathered; channels between pixels
-    int a, b;            // tile: XCD map, unroll; pipe: XCD map, waves; brick: z-spectrum, 0; one-channel: views, chunk; else 0, 0
-    int cl, io;          // channels-last result; FwdRequest::io (one-channel: 4 = the kernel that also writes the pass mask, 5 = that kernel with bf16 taps, 8 = the z-spectrum form)
+    int jp, ps, cl;         // channels gathered; channels between pixels; channels-last result
+    int taps16, cubes16;    // 2-byte (bf16) heat-map taps; 2-byte result
+    int xcd, unroll, waves; // tile, pipe: XCD-aware tile map; tile: voxels in flight per lane; pipe: waves per workgroup
+    int zd;                 // brick, one-channel: z-spectrum result
+    int views, chunk, mask; // one-channel: view slots; how many of them a gather chunk holds; the kernel that also writes the pass mask
 };
+template <typename T> constexpr int is16() { return sizeof(T) == 2 ? 1 : 0; }
 using PackFn = void (*)(Views, float *, int, int, int);
 using PlanarFn = void (*)(Views, const float *, const float *, const uint8_t *, float *, float *, Geom);
 using TileFn = void (*)(Views, const float *, const float *, const uint8_t *, float *, float *, Geom, int, int);   // tile and pipe
 using BrickFn = void (*)(Views, const float *, const float *, const uint8_t *, float *, float *, Geom, int, int, int, int);
 using OneFn = void (*)(Views, const float *, const float *, const uint8_t *, float *, float *, Geom, long long, int, int);
 
-template <typename TI, typename TO> constexpr int io_of() { return (sizeof(TI) == 2 ? 1 : 0) | (sizeof(TO) == 2 ? 2 : 0); }
 inline bool same_key(const KernelKey &a, const KernelKey &b) { return !memcmp(&a, &b, sizeof(a)); }
 
 #define SP3D_ROW(FN_, KEY_, K_, ...) \

@@ -378,14 +378,14 @@ __global__ __launch_bounds__(64) void unproject_one_bwd_kernel(const float *__re
 }
 
 // one-channel kernel: VT view slots gathered in chunks of CS
-#define SP3D_ONE(VT_, CS_) SP3D_ROW(OneFn, (KernelKey{1, 1, VT_, CS_, false, 0}), unproject_one_kernel, VT_, CS_, false) \
-    SP3D_ROW(OneFn, (KernelKey{1, 1, VT_, CS_, true, 0}), unproject_one_kernel, VT_, CS_, true) \
-    SP3D_ROW(OneFn, (KernelKey{1, 1, VT_, CS_, false, 4}), unproject_one_kernel, VT_, CS_, false, true) \
-    SP3D_ROW(OneFn, (KernelKey{1, 1, VT_, CS_, true, 4}), unproject_one_kernel, VT_, CS_, true, true)
-// bf16 maps (SP3D_HM_BF16_IN): the same ladder, planar and channels-last results, no pass mask; key.io = 1.  Tables of their
+#define SP3D_ONE(VT_, CS_) SP3D_ROW(OneFn, (KernelKey{.jp = 1, .ps = 1, .views = VT_, .chunk = CS_}), unproject_one_kernel, VT_, CS_, false) \
+    SP3D_ROW(OneFn, (KernelKey{.jp = 1, .ps = 1, .cl = true, .views = VT_, .chunk = CS_}), unproject_one_kernel, VT_, CS_, true) \
+    SP3D_ROW(OneFn, (KernelKey{.jp = 1, .ps = 1, .views = VT_, .chunk = CS_, .mask = true}), unproject_one_kernel, VT_, CS_, false, true) \
+    SP3D_ROW(OneFn, (KernelKey{.jp = 1, .ps = 1, .cl = true, .views = VT_, .chunk = CS_, .mask = true}), unproject_one_kernel, VT_, CS_, true, true)
+// bf16 maps (SP3D_HM_BF16_IN): the same ladder, planar and channels-last results, no pass mask.  Tables of their
 // own behind the fp32 ones, as find_brick_zspectrum32_kernel is behind find_brick_kernel
-#define SP3D_ONE_H(VT_, CS_) SP3D_ROW(OneFn, (KernelKey{1, 1, VT_, CS_, false, 1}), unproject_one_kernel, VT_, CS_, false, false, bf16_t) \
-    SP3D_ROW(OneFn, (KernelKey{1, 1, VT_, CS_, true, 1}), unproject_one_kernel, VT_, CS_, true, false, bf16_t)
+#define SP3D_ONE_H(VT_, CS_) SP3D_ROW(OneFn, (KernelKey{.jp = 1, .ps = 1, .taps16 = 1, .views = VT_, .chunk = CS_}), unproject_one_kernel, VT_, CS_, false, false, bf16_t) \
+    SP3D_ROW(OneFn, (KernelKey{.jp = 1, .ps = 1, .cl = true, .taps16 = 1, .views = VT_, .chunk = CS_}), unproject_one_kernel, VT_, CS_, true, false, bf16_t)
 static int find_one_h_kernel(const KernelKey &key, const void *&fn, const char *&name)
 {
     SP3D_ONE_H(1, 4) SP3D_ONE_H(2, 4) SP3D_ONE_H(3, 4) SP3D_ONE_H(4, 4) SP3D_ONE_H(5, 4) SP3D_ONE_H(6, 4) SP3D_ONE_H(8, 4)
@@ -394,10 +394,10 @@ static int find_one_h_kernel(const KernelKey &key, const void *&fn, const char *
 }
 
 // bf16 maps into the training forward (SP3D_HM_BF16_TRAIN on sp3d_unproject_one_fwd_train): the MASK = true kernels with 2-byte
-// taps, planar and channels-last results; key.io = 5 (the pass mask's 4 + bf16 taps).  Behind the inference rows, as they are
+// taps, planar and channels-last results.  Behind the inference rows, as they are
 // behind the fp32 ones; planned by tests/test_bf16_train_host.py, run by tests/test_gpu_bf16_train.py.
-#define SP3D_ONE_H_TRAIN(VT_, CS_) SP3D_ROW(OneFn, (KernelKey{1, 1, VT_, CS_, false, 5}), unproject_one_kernel, VT_, CS_, false, true, bf16_t) \
-    SP3D_ROW(OneFn, (KernelKey{1, 1, VT_, CS_, true, 5}), unproject_one_kernel, VT_, CS_, true, true, bf16_t)
+#define SP3D_ONE_H_TRAIN(VT_, CS_) SP3D_ROW(OneFn, (KernelKey{.jp = 1, .ps = 1, .taps16 = 1, .views = VT_, .chunk = CS_, .mask = true}), unproject_one_kernel, VT_, CS_, false, true, bf16_t) \
+    SP3D_ROW(OneFn, (KernelKey{.jp = 1, .ps = 1, .cl = true, .taps16 = 1, .views = VT_, .chunk = CS_, .mask = true}), unproject_one_kernel, VT_, CS_, true, true, bf16_t)
 static int find_one_h_train_kernel(const KernelKey &key, const void *&fn, const char *&name)
 {
     SP3D_ONE_H_TRAIN(1, 4) SP3D_ONE_H_TRAIN(2, 4) SP3D_ONE_H_TRAIN(3, 4) SP3D_ONE_H_TRAIN(4, 4) SP3D_ONE_H_TRAIN(5, 4)
@@ -409,14 +409,14 @@ int find_one_kernel(const KernelKey &key, const void *&fn, const char *&name)
 {
     SP3D_ONE(1, 4) SP3D_ONE(2, 4) SP3D_ONE(3, 4) SP3D_ONE(4, 4) SP3D_ONE(5, 4) SP3D_ONE(6, 4) SP3D_ONE(8, 4) SP3D_ONE(10, 8)
     SP3D_ONE(12, 8) SP3D_ONE(16, 8)
-    if (key.io == 5) return find_one_h_train_kernel(key, fn, name);
+    if (key.mask) return find_one_h_train_kernel(key, fn, name);
     return find_one_h_kernel(key, fn, name);
 }
 
-// the z-spectrum form (SP3D_HM_ONE_ZSPECTRUM): the same view slots and chunks; key.io = 8
-#define SP3D_ONE_ZD(VT_, CS_) SP3D_ROW(OneFn, (KernelKey{1, 1, VT_, CS_, false, 8}), unproject_one_zd_kernel, VT_, CS_)
-// ... and with bf16 maps (SP3D_HM_BF16_IN next to it); key.io = 9
-#define SP3D_ONE_ZD_H(VT_, CS_) SP3D_ROW(OneFn, (KernelKey{1, 1, VT_, CS_, false, 9}), unproject_one_zd_kernel, VT_, CS_, bf16_t)
+// the z-spectrum form (SP3D_HM_ONE_ZSPECTRUM): the same view slots and chunks
+#define SP3D_ONE_ZD(VT_, CS_) SP3D_ROW(OneFn, (KernelKey{.jp = 1, .ps = 1, .zd = true, .views = VT_, .chunk = CS_}), unproject_one_zd_kernel, VT_, CS_)
+// ... and with bf16 maps (SP3D_HM_BF16_IN next to it)
+#define SP3D_ONE_ZD_H(VT_, CS_) SP3D_ROW(OneFn, (KernelKey{.jp = 1, .ps = 1, .taps16 = 1, .zd = true, .views = VT_, .chunk = CS_}), unproject_one_zd_kernel, VT_, CS_, bf16_t)
 static int find_one_zd_h_kernel(const KernelKey &key, const void *&fn, const char *&name)
 {
     SP3D_ONE_ZD_H(1, 4) SP3D_ONE_ZD_H(2, 4) SP3D_ONE_ZD_H(3, 4) SP3D_ONE_ZD_H(4, 4) SP3D_ONE_ZD_H(5, 4) SP3D_ONE_ZD_H(6, 4)

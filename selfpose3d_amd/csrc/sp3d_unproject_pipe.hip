@@ -195,7 +195,7 @@ __global__ __launch_bounds__(64 * NW) void unproject_pipe_kernel(Views hm, const
 }
 
 #define SP3D_PIPE(JP_, XCD_, NW_, CL_, TI_, TO_, PS_) \
-    SP3D_ROW(TileFn, (KernelKey{JP_, PS_, XCD_, NW_, CL_, io_of<TI_, TO_>()}), unproject_pipe_kernel, JP_, XCD_, NW_, CL_, TI_, TO_, PS_)
+    SP3D_ROW(TileFn, (KernelKey{.jp = JP_, .ps = PS_, .cl = CL_, .taps16 = is16<TI_>(), .cubes16 = is16<TO_>(), .xcd = XCD_, .waves = NW_}), unproject_pipe_kernel, JP_, XCD_, NW_, CL_, TI_, TO_, PS_)
 #define SP3D_PIPES(JP_, NW_, TI_, TO_) SP3D_PIPE(JP_, true, NW_, false, TI_, TO_, JP_) SP3D_PIPE(JP_, false, NW_, false, TI_, TO_, JP_) \
     SP3D_PIPE(JP_, true, NW_, true, TI_, TO_, JP_) SP3D_PIPE(JP_, false, NW_, true, TI_, TO_, JP_)
 int find_pipe_kernel(const KernelKey &key, const void *&fn, const char *&name)

@@ -300,7 +300,7 @@ __global__ __launch_bounds__(TILE) void unproject_nhwc_kernel(Views hm, const fl
     }
 }
 
-#define SP3D_TILE(JP_, XCD_, U_) SP3D_ROW(TileFn, (KernelKey{JP_, JP_, XCD_, U_, 0, 0}), unproject_nhwc_kernel, JP_, XCD_, U_)
+#define SP3D_TILE(JP_, XCD_, U_) SP3D_ROW(TileFn, (KernelKey{.jp = JP_, .ps = JP_, .xcd = XCD_, .unroll = U_}), unproject_nhwc_kernel, JP_, XCD_, U_)
 #define SP3D_TILES(JP_) SP3D_TILE(JP_, true, 1) SP3D_TILE(JP_, false, 1) SP3D_TILE(JP_, true, 2) SP3D_TILE(JP_, false, 2) \
     SP3D_TILE(JP_, true, 4) SP3D_TILE(JP_, false, 4)
 int find_tile_kernel(const KernelKey &key, const void *&fn, const char *&name)
@@ -309,14 +309,14 @@ int find_tile_kernel(const KernelKey &key, const void *&fn, const char *&name)
     return SP3D_EUNSUPPORTED;
 }
 
-#define SP3D_PLANAR(JC_) SP3D_ROW(PlanarFn, (KernelKey{JC_, JC_, 0, 0, 0, 0}), unproject_planar_kernel, JC_)
+#define SP3D_PLANAR(JC_) SP3D_ROW(PlanarFn, (KernelKey{.jp = JC_, .ps = JC_}), unproject_planar_kernel, JC_)
 int find_planar_kernel(const KernelKey &key, const void *&fn, const char *&name)
 {
     SP3D_PLANAR(1) SP3D_PLANAR(4) SP3D_PLANAR(16)
     return SP3D_EUNSUPPORTED;
 }
 
-#define SP3D_PACK(JP_, TI_, TO_) SP3D_ROW(PackFn, (KernelKey{JP_, JP_, 0, 0, 0, io_of<TI_, TO_>()}), pack_nhwc_kernel, JP_, TI_, TO_)
+#define SP3D_PACK(JP_, TI_, TO_) SP3D_ROW(PackFn, (KernelKey{.jp = JP_, .ps = JP_, .taps16 = is16<TI_>(), .cubes16 = is16<TO_>()}), pack_nhwc_kernel, JP_, TI_, TO_)
 int find_pack_kernel(const KernelKey &key, const void *&fn, const char *&name)
 {
     SP3D_PACK(4, float, float) SP3D_PACK(8, float, float) SP3D_PACK(12, float, float) SP3D_PACK(16, float, float)
@@ -344,7 +344,7 @@ extern "C" int sp3d_pack_heatmaps_ex(const void *const *hm_views, void *packed, 
     float *pk = reinterpret_cast<float *>(packed);
     const void *fn;
     const char *name;
-    if (find_pack_kernel(KernelKey{Jp, Jp, 0, 0, 0, (in_bf16 ? 1 : 0) | (out_bf16 ? 2 : 0)}, fn, name)) return SP3D_EUNSUPPORTED;
+    if (find_pack_kernel(KernelKey{.jp = Jp, .ps = Jp, .taps16 = in_bf16 ? 1 : 0, .cubes16 = out_bf16 ? 1 : 0}, fn, name)) return SP3D_EUNSUPPORTED;
     void *args[] = {&v, &pk, &B, &J, &HW};
     (void)hipLaunchKernel(fn, grid, block, args, 0, s);
     return launch_status();

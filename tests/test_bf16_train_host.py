@@ -176,8 +176,11 @@ def test_plan_refusals(lib):
         assert plan(h16, entry=entry, jp=16, J=15)[0] == EUNSUPPORTED
         assert plan(h16, entry=entry, layout=PLANAR, jp=15, J=1)[0] == EUNSUPPORTED
         assert plan(h16 | one, entry=entry, layout=PLANAR, jp=15, J=1)[0] == EUNSUPPORTED
-    # an unknown layout byte or a pixel stride below 1 keeps its own code
-    assert plan(t, layout=7, jp=16, J=15)[0] == plan(0, layout=7, jp=16, J=15)[0] == -1
+    # an unknown layout byte or a pixel stride below 1 keeps its own code: where the entry has one - sp3d_unproject_fwd_train
+    # takes SP3D_LAYOUT_NHWC and answers every other layout byte alike (tests/test_fwd_request_census.py: the plan answers what
+    # the entry answers)
+    assert plan(t, layout=7, jp=16, J=15)[0] == plan(0, layout=7, jp=16, J=15)[0] == plan(0, layout=PLANAR, jp=16, J=15)[0] == EUNSUPPORTED
+    assert plan(t, layout=7, jp=16, J=1, entry="one_train")[0] == plan(0, layout=7, jp=16, J=1, entry="one_train")[0] == -1
     assert plan(t, layout=PLANAR, jp=0, J=1, entry="one_train")[0] == plan(0, layout=PLANAR, jp=0, J=1, entry="one_train")[0] == -1
 
 

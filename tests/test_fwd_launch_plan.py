@@ -80,12 +80,14 @@ def test_census_equals_the_previous_dispatcher(lib):
 def test_images_the_pipelined_kernels_cannot_index_take_the_tile_kernel(lib, h, w):
     """below 2 x 2 pixels (the clamped 2 x 2 block) and above 2^24 pixels (24-bit multiplies): the tile kernel, whatever the
     default or the word says; bf16 storage, which only the pipelined kernels have, is refused"""
-    for kw in (dict(), dict(cube=(24, 16, 32)), dict(entry="variant", word=120), dict(entry="variant", word=56 | (1 << 22)),
-               dict(entry="strided"), dict(entry="train")):
+    for kw in (dict(), dict(cube=(24, 16, 32)), dict(entry="variant", word=120), dict(entry="variant", word=56 | (1 << 22))):
         rc, launches, _ = plan(h=h, w=w, **kw)
         assert rc == 0 and [l["name"] for l in launches] == ["unproject_nhwc_kernel<16, true, 1>"], (kw, rc, launches)
         tiles = -(-24 * 16 * kw.get("cube", (0, 0, 20))[2] // 256)
         assert (launches[0]["block"], launches[0]["s0"], launches[0]["s1"]) == (256, tiles, 2 * tiles)
+    for entry in ("strided", "train"):      # sp3d_unproject_fwd_strided and _fwd_train refuse an image below 2 x 2; above 2^24 pixels they
+        rc, launches, _ = plan(h=h, w=w, entry=entry)                                     # answer as the indexed entry does
+        assert (rc, launches) == (EUNSUPPORTED, []) if min(h, w) < 2 else [l["name"] for l in launches] == ["unproject_nhwc_kernel<16, true, 1>"]
     assert plan(h=h, w=w, entry="variant", word=6)[1][0]["name"] == "unproject_nhwc_kernel<16, false, 4>"
     for flags in (_lib.HM_BF16, _lib.OUT_BF16, _lib.HM_BF16 | _lib.OUT_BF16):
         assert plan(h=h, w=w, flags=flags)[0] == EUNSUPPORTED
