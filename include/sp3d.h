@@ -320,7 +320,8 @@ int sp3d_unproject_bwd_packed(const float *cam, const int32_t *sample_of, const 
  *   scale       DEVICE float: a power of two 2^k; a contribution v is added as round(v * scale).
  *               REQUIRED: |v * scale| < 2^50 for every contribution (the merge kernel rounds with the 1.5*2^52 mantissa
  *               trick, exact only below that; beyond it the two kernels stop agreeing).  The intended choice is k from
- *               max|grad_cubes| so that |v * scale| <= 2^40: 2^23 contributions per pixel then still fit in 63 bits.
+ *               max|grad_cubes| so that |v * scale| <= 2^40: 2^23 contributions per pixel then still fit in 63 bits
+ *               (the Python binding takes up to 2^49 where 4 N P, the most a pixel can receive, leaves the room).
  * sp3d_fixed_to_float(acc, out, scale, n) converts: out[i] = (float)(acc[i] / scale).
  */
 int sp3d_unproject_bwd_packed_det(const float *cam, const int32_t *sample_of, const float *centers, const uint8_t *valid,

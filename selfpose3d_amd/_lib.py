@@ -750,6 +750,18 @@ def channel_shift_act_(y: torch.Tensor, shift: torch.Tensor, mode: int, residual
     return y
 
 
+def _fixed_point_scale(gmax: torch.Tensor, taps: int) -> torch.Tensor:
+    """the scale of the deterministic scatters, (1,) fp32 on the device (no host synchronisation): 2^(s - ceil(log2 max|g|)),
+    so that 2^s steps span the largest gradient.  A pixel receives at most ``taps`` = 4 N P contributions (4 taps of every voxel
+    of every cube), each below 2^s steps, and their sum must fit in 63 bits: s = 61 - ceil(log2 taps), at least 40 (what every
+    call took before, and what the root grid at batch 4 and anything larger still takes: the same bits there) and at most 49
+    (include/sp3d.h: the merge kernel's rounding needs every contribution below 2^50 steps).  Small calls get a finer step: a channel whose
+    gradient is 2^-17 of the call's largest then still lands within the fp32 scatter's error bound."""
+    s = max(40, min(49, 61 - max(int(taps) - 1, 1).bit_length()))
+    k = torch.ceil(torch.log2(gmax.clamp_min(1e-30)))
+    return torch.exp2((float(s) - k).clamp_max(126.0)).to(torch.float32).reshape(1)
+
+
 def unproject_bwd_packed(cam, centers, valid, grad_cubes: torch.Tensor, pass_mask: torch.Tensor, batch: int,
                          num_views: int, J: int, jp: int, h: int, w: int, cube_size, grid_size, img_size,
                          sample_of: Optional[torch.Tensor] = None, deterministic: bool = False, return_packed: bool = False,
@@ -773,9 +785,7 @@ def unproject_bwd_packed(cam, centers, valid, grad_cubes: torch.Tensor, pass_mas
         scatter = int(scatter) | SCATTER_WIDE
     gc = grad_cubes[:, :J].float().contiguous()
     if deterministic:
-        # scale = 2^(40 - ceil(log2 max|g|)): computed on the device, no host synchronisation
-        gmax = gc.abs().amax().clamp_min(1e-30)
-        scale = torch.exp2(40.0 - torch.ceil(torch.log2(gmax))).to(torch.float32).reshape(1)
+        scale = _fixed_point_scale(gc.abs().amax(), 4 * P * X * Y * Z)
         fixed = torch.zeros((num_views, batch, h, w, jp), dtype=torch.int64, device=dev)
         rc = lib.sp3d_unproject_bwd_packed_det(cam.data_ptr(), _opt(sample_of), centers.data_ptr(), valid.data_ptr(),
                                                gc.data_ptr(), pass_mask.data_ptr(), fixed.data_ptr(), scale.data_ptr(),
@@ -830,7 +840,7 @@ def unproject_one_bwd(cam, centers, valid, grad_cubes: torch.Tensor, pass_mask: 
     """one-channel scatter: channel 0 of ``grad_cubes`` (P,C,X,Y,Z) -> list[V] of (B,1,h,w) gradient views of one dense
     (V,B,h,w) buffer.  A contiguous planar fp32 gradient is read in place at its cube stride (C*N: no slice copy); anything
     else (channels-last, another dtype, a view) is reduced to channel 0 first.
-    ``deterministic``: 64-bit fixed point with integer atomics, scale = 2^(40 - ceil(log2 max|g|)) of that channel, as
+    ``deterministic``: 64-bit fixed point with integer atomics, scale = ``_fixed_point_scale`` of that channel's max|g|, as
     ``unproject_bwd_packed`` builds it: bit-identical run to run, and to channel 0 of the packed deterministic scatter."""
     out = _unproject_one_bwd_dense(cam, centers, valid, grad_cubes, pass_mask, batch, num_views, h, w, cube_size, grid_size, img_size,
                                    sample_of, deterministic)
@@ -865,9 +875,7 @@ def _unproject_one_bwd_dense(cam, centers, valid, grad_cubes, pass_mask, batch, 
     else:
         gc, stride = grad_cubes[:, :1].float().contiguous(), N
     if deterministic:
-        # scale = 2^(40 - ceil(log2 max|g|)): computed on the device, no host synchronisation
-        gmax = gc[:, 0].abs().amax().clamp_min(1e-30)
-        scale = torch.exp2(40.0 - torch.ceil(torch.log2(gmax))).to(torch.float32).reshape(1)
+        scale = _fixed_point_scale(gc[:, 0].abs().amax(), 4 * P * N)
         fixed = torch.zeros((num_views, batch, h, w), dtype=torch.int64, device=dev)
         rc = lib.sp3d_unproject_one_bwd_det(cam.data_ptr(), _opt(sample_of), centers.data_ptr(), valid.data_ptr(), gc.data_ptr(),
                                             stride, pass_mask.data_ptr(), fixed.data_ptr(), scale.data_ptr(), int(batch), P,
